@@ -15,13 +15,15 @@ JSON line and exits non-zero if any rank fails.  Under torchrun (WORLD_SIZE set)
 is a rank; --gpus must then equal WORLD_SIZE.  Asking for more ranks than the box has GPUs
 is an error unless --rehearse is given (all ranks on the GPUs that exist, gloo exchange).
 
-Timing.  W warm-up steps, then the K-step region -- barrier + torch.cuda.synchronize() on both
-sides, MAX over ranks -- is timed R >= 5 times (more until ~0.3 s have been timed, the region
-of the default workload is only a few ms) and the MEDIAN region gives `ms_per_step` / `value`.
+Timing.  W warm-up steps (more until --warmup-s seconds have passed), then ONE region of exactly K steps -- barrier +
+torch.cuda.synchronize() on both sides, MAX over ranks -- gives `ms_per_step` (region / K) and `value`.
 
-Rank 0 prints ONE JSON line carrying, besides the throughput, `roofline` (dominant kernel,
-HIP-event timed on the stream it is launched on) and `cpu_baseline` (the restated reference
-float path on the host cores, N = 1 only).
+Rank 0 prints ONE JSON line.  A plain run measures the headline and nothing else.  `--full` adds what is measured
+beside it in the same run: `roofline` and `kernels` (every launch HIP-event timed on the stream it is launched on),
+`cpu_baseline` (the restated reference float path on the host cores, N = 1 only), the other first-layer entries, the
+product call, the north-star targets, the cache-resident and one-gather-per-batch figures and the ring check (N > 1).
+`--dump-outputs DIR` writes what the last timed step returned -- the network's output for its batch, gathered over the
+ranks for N > 1 -- to DIR/output.npy (float32); the inputs are seeded, so equal arguments give equal inputs.
 """
 import argparse
 import importlib
@@ -59,7 +61,10 @@ def parse_args(argv=None):
     ap.add_argument("--batch", type=int, default=BATCH)
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                     help="weak: --batch images per GPU; strong: --batch images in all, cut into contiguous shards")
-    ap.add_argument("--repeats", type=int, default=5, help="minimum number of timed K-step regions (median reported)")
+    ap.add_argument("--warmup-s", type=float, default=0.5,
+                    help="after the --warmup steps, keep warming up until this many seconds have passed")
+    ap.add_argument("--repeats", type=int, default=5,
+                    help="--full: minimum number of timed K-step regions of the figures beside the headline (median)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--graph", type=int, default=1, help="replay the forward from a hipGraph")
     ap.add_argument("--inflight", type=int, default=0,
@@ -86,6 +91,11 @@ def parse_args(argv=None):
                          "RCCL path, headline workload: 1 -> 43.4 M, 4 -> 54.0 M, 16 -> 56.0 M img/s; no exchange 59.6 M)")
     ap.add_argument("--rehearse", action="store_true",
                     help="allow more ranks than GPUs (ranks share devices, logits exchanged over gloo)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline (roofline, per-kernel times, CPU baseline, "
+                         "other entries and workloads, product call, reference comparison)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy")
     return ap.parse_args(argv)
 
 
@@ -409,6 +419,106 @@ class RingSchedule:
                 self.works[k] = None
 
 
+def per_kernel_times(torch, abi, model, x, N, cf, fused, u8, step):
+    """--full: every launch of one forward, HIP-event timed on the stream it is launched on (`roofline`, `kernels`)."""
+    for _ in range(3):
+        step()
+    torch.cuda.synchronize()
+    per_kernel = []
+    if fused:
+        cur, hh, ww = x, cf.dim, cf.dim
+        for si, st in enumerate(model.steps):
+            kh, kw, cin, cout = st["w"].shape
+            if si == len(model.steps) - 2 and model.run_head(cur, N, hh, ww) is not None:
+                # the last conv group and the classifier run as ONE launch (qnn_conv2d_dense_forward): bytes = the conv's
+                # packed input + the float32 logits, MACs of both layers
+                dn = model.steps[-1]["w"].shape
+                nb_in = step_bytes(abi, dict(st, out_store=abi.STORE_F32, pool=1), N, hh, ww)[0] - N * hh * ww * cout * 4
+                ms, b2b, outs = time_launch(torch, lambda cur=cur, hh=hh, ww=ww: model.run_head(cur, N, hh, ww))
+                per_kernel.append(dict(kernel=abi.last_kernel(), ms=ms, b2b_ms=b2b, bytes=nb_in + N * dn[3] * 4, launches=1,
+                                       pipe="i8", macs=N * hh * ww * kh * kw * cin * cout + N * dn[2] * dn[3]))
+                break
+            nbytes, ho, wo = step_bytes(abi, st, N, hh, ww, x_elem_bytes=1 if (u8 and si == 0) else 4)
+            ms, b2b, outs = time_launch(torch, lambda si=si, cur=cur, hh=hh, ww=ww: model.run_step(si, cur, N, hh, ww)[0])
+            kname = abi.last_kernel()
+            # the integer first-layer kernels (uint8 entry, "image", "fixed") run the problem's MACs on the int8 pipe:
+            # priced like every other integer layer, so HBM bounds them; the exact first layer is an f32-pipe kernel
+            per_kernel.append(dict(kernel=kname, ms=ms, b2b_ms=b2b, bytes=nbytes, launches=1,
+                                   pipe="f32" if kname.startswith("mfma_f32") or kname.startswith("dense_f32") else "i8",
+                                   macs=N * (ho * wo * st["pool"] ** 2 if st["kind"] == "conv" else 1)
+                                   * kh * kw * cin * cout))
+            cur, hh, ww = outs, ho, wo
+    else:
+        # residual topology: ~130 launches per forward.  Every launch is captured with its operands and
+        # re-issued back to back for timing; launches of the same kernel on the same shape form one group
+        model.capture = []
+        model(x)
+        torch.cuda.synchronize()
+        groups = {}
+        for c in model.capture:
+            ms, _, _ = time_launch(torch, c["launch"], reps=8, lead=2, rounds=1)
+            g = groups.setdefault((c["kernel"], c["shape"]), dict(kernel=c["kernel"], shape=c["shape"], ms_total=0.0,
+                                                                  launches=0, bytes=c["bytes"], macs=c["macs"],
+                                                                  pipe=c["pipe"]))
+            g["ms_total"] += ms
+            g["launches"] += 1
+        model.capture = None
+        for g in groups.values():
+            per_kernel.append(dict(kernel=g["kernel"], shape=g["shape"], ms=g["ms_total"] / g["launches"],
+                                   launches=g["launches"], bytes=g["bytes"], macs=g["macs"], pipe=g["pipe"]))
+    return per_kernel
+
+
+def roofline(per_kernel, ms_per_step, traffic_key):
+    """--full: the dominant kernel against its roof (HBM or matrix pipe), the whole step against the sum of every launch's
+    own roofline time, and the per-kernel table."""
+    dom = max(range(len(per_kernel)), key=lambda i: per_kernel[i]["ms"] * per_kernel[i]["launches"])
+    d = per_kernel[dom]
+    hbm_gbs = d["bytes"] / (d["ms"] * 1e-3) / 1e9
+    tkey = d["kernel"] + (":%s" % d["shape"][-1] if d.get("shape") and str(d["shape"][-1]).startswith("res_") else "")
+    traffic, rocprof_name = load_traffic(tkey, traffic_key)
+    common = {"kernel": d["kernel"], "rocprof_kernel": rocprof_name, "layer_index": dom,
+              "launches_per_step": d["launches"], "avg_launch_ms": d["ms"],
+              "back_to_back_launch_ms": d.get("b2b_ms"),
+              "algorithmic_bytes_per_launch": d["bytes"], "traffic": traffic}
+    if d["kernel"].startswith("mfma_") and 2.0 * d["macs"] / (MFMA_PEAK_TFLOPS["f32" if d["pipe"] == "f32" else "i8"] * 1e12) \
+            >= d["bytes"] / (HBM_PEAK_GBS * 1e9):
+        kind = "f32" if d["pipe"] == "f32" else "i8"
+        achieved = 2.0 * d["macs"] / (d["ms"] * 1e-3) / 1e12
+        roof = dict(common, bound="mfma", achieved=achieved, peak=MFMA_PEAK_TFLOPS[kind], unit="TFLOP/s",
+                    frac=achieved / MFMA_PEAK_TFLOPS[kind], mfma_dtype=kind,
+                    algorithmic_flops_per_launch=2.0 * d["macs"], hbm_GBps=hbm_gbs,
+                    hbm_frac=hbm_gbs / HBM_PEAK_GBS)
+    else:
+        roof = dict(common, bound="hbm", achieved=hbm_gbs, peak=HBM_PEAK_GBS, unit="GB/s",
+                    frac=hbm_gbs / HBM_PEAK_GBS)
+    # one end-to-end fraction: the sum of every launch's own roofline time over the measured step
+    roof_ms = sum(layer_roof_ms(k) * k["launches"] for k in per_kernel)
+    roof["pipeline_roof_ms"] = roof_ms
+    roof["pipeline_frac"] = roof_ms / ms_per_step
+    kernels = [{"kernel": k["kernel"], "launches": k["launches"], "ms": round(k["ms"], 5),
+                "GBps": round(k["bytes"] / (k["ms"] * 1e-3) / 1e9, 2),
+                "TMACps": round(k["macs"] / (k["ms"] * 1e-3) / 1e12, 3),
+                "roof_ms": round(layer_roof_ms(k), 5),
+                **({"shape": list(k["shape"])} if "shape" in k else {})} for k in per_kernel]
+    return roof, kernels
+
+
+def dump_outputs(path, arrays, budget=64 << 20):
+    """--dump-outputs: every array to `path`/<name>.npy as float32 (float64 kept), at most `budget` bytes in all; an array
+    over its share keeps a fixed, seeded sample of its rows (in order)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    share = budget // max(1, len(arrays))
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        a = a if a.dtype == np.float64 else a.astype(np.float32)
+        if a.nbytes > share:
+            keep = max(1, share // max(1, a.nbytes // a.shape[0]))
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def main_rank(args):
     import numpy as np
     import torch
@@ -488,53 +598,8 @@ def main_rank(args):
             return shard.gather_logits(y.cpu())
         return shard.gather_logits(y)
 
-    # ---- per-kernel HIP-event timing (same stream the kernels are launched on) ----
-    for _ in range(3):
-        step()
-    torch.cuda.synchronize()
-    per_kernel = []
-    if fused:
-        cur, hh, ww = x, cf.dim, cf.dim
-        for si, st in enumerate(model.steps):
-            kh, kw, cin, cout = st["w"].shape
-            if si == len(model.steps) - 2 and model.run_head(cur, N, hh, ww) is not None:
-                # the last conv group and the classifier run as ONE launch (qnn_conv2d_dense_forward): bytes = the conv's
-                # packed input + the float32 logits, MACs of both layers
-                dn = model.steps[-1]["w"].shape
-                nb_in = step_bytes(abi, dict(st, out_store=abi.STORE_F32, pool=1), N, hh, ww)[0] - N * hh * ww * cout * 4
-                ms, b2b, outs = time_launch(torch, lambda cur=cur, hh=hh, ww=ww: model.run_head(cur, N, hh, ww))
-                per_kernel.append(dict(kernel=abi.last_kernel(), ms=ms, b2b_ms=b2b, bytes=nb_in + N * dn[3] * 4, launches=1,
-                                       pipe="i8", macs=N * hh * ww * kh * kw * cin * cout + N * dn[2] * dn[3]))
-                break
-            nbytes, ho, wo = step_bytes(abi, st, N, hh, ww, x_elem_bytes=1 if (u8 and si == 0) else 4)
-            ms, b2b, outs = time_launch(torch, lambda si=si, cur=cur, hh=hh, ww=ww: model.run_step(si, cur, N, hh, ww)[0])
-            kname = abi.last_kernel()
-            # the integer first-layer kernels (uint8 entry, "image", "fixed") run the problem's MACs on the int8 pipe:
-            # priced like every other integer layer, so HBM bounds them; the exact first layer is an f32-pipe kernel
-            per_kernel.append(dict(kernel=kname, ms=ms, b2b_ms=b2b, bytes=nbytes, launches=1,
-                                   pipe="f32" if kname.startswith("mfma_f32") or kname.startswith("dense_f32") else "i8",
-                                   macs=N * (ho * wo * st["pool"] ** 2 if st["kind"] == "conv" else 1)
-                                   * kh * kw * cin * cout))
-            cur, hh, ww = outs, ho, wo
-    else:
-        # residual topology: ~130 launches per forward.  Every launch is captured with its operands and
-        # re-issued back to back for timing; launches of the same kernel on the same shape form one group
-        model.capture = []
-        model(x)
-        torch.cuda.synchronize()
-        groups = {}
-        for c in model.capture:
-            ms, _, _ = time_launch(torch, c["launch"], reps=8, lead=2, rounds=1)
-            g = groups.setdefault((c["kernel"], c["shape"]), dict(kernel=c["kernel"], shape=c["shape"], ms_total=0.0,
-                                                                  launches=0, bytes=c["bytes"], macs=c["macs"],
-                                                                  pipe=c["pipe"]))
-            g["ms_total"] += ms
-            g["launches"] += 1
-        model.capture = None
-        for g in groups.values():
-            per_kernel.append(dict(kernel=g["kernel"], shape=g["shape"], ms=g["ms_total"] / g["launches"],
-                                   launches=g["launches"], bytes=g["bytes"], macs=g["macs"], pipe=g["pipe"]))
-    dom = max(range(len(per_kernel)), key=lambda i: per_kernel[i]["ms"] * per_kernel[i]["launches"])
+    # ---- per-kernel HIP-event timing (same stream the kernels are launched on): --full only ----
+    per_kernel = per_kernel_times(torch, abi, model, x, N, cf, fused, u8, step) if args.full else None
 
     # ---- the product's pipeline (engine.Pipelined: one hipGraph of the forward per lane, lanes replayed round-robin
     # on their own streams; what nets.Model.predict runs on).  bench.py only adds what belongs to the measurement: the
@@ -590,10 +655,11 @@ def main_rank(args):
     counter = [0]
     rotate_on = [True]
     every1 = [False]
+    last = [None]           # what the latest step returned (a tensor; a (lane, slot) of the rings when pipelined)
 
     def run_step():
         if graph is None:
-            step()
+            last[0] = step()
             return
         ln = lanes[counter[0] % len(lanes)]
         counter[0] += 1
@@ -602,9 +668,8 @@ def main_rank(args):
                 r = ln["rot"] % ln["nin"] if rotate_on[0] else 0
                 ln["rot"] += 1
                 (ln["graphs"][r] if "graphs" in ln else ln["graph"]).replay()
-                if use_dist:
-                    yr = ln["ys"][r] if "ys" in ln else ln["y"]
-                    shard.gather_logits(yr.cpu() if backend == "gloo" else yr)
+                yr = ln["ys"][r] if "ys" in ln else ln["y"]
+                last[0] = shard.gather_logits(yr.cpu() if backend == "gloo" else yr) if use_dist else yr
                 return
             sch = ln["sched"]
             if every1[0]:
@@ -629,6 +694,7 @@ def main_rank(args):
                 ln["graph"].replay()
                 ln["ring"][j * ln["B"]:(j + 1) * ln["B"]].copy_(ln["y"], non_blocking=True)
             sch.end_step(j)
+            last[0] = (ln, j)
 
     def drain():
         """Gather what the timed steps left in a partly filled ring and wait for every gather.  Every rank is at the same
@@ -667,28 +733,57 @@ def main_rank(args):
             dt = float(t.item())
         return dt
 
+    def last_output():
+        """What the latest step returned, on the host; N > 1: the block of every rank, gathered."""
+        o = last[0]
+        if isinstance(o, tuple):
+            ln, j = o
+            k, s, B = j // G, j % G, ln["B"]
+            rows = ln["gathered"][k].view((world, G * B) + tuple(ln["y"].shape[1:]))[:, s * B:(s + 1) * B]
+            o = rows.reshape((world * B,) + tuple(ln["y"].shape[1:]))
+        return o.detach().cpu().numpy()
+
+    # warm-up: the W steps, then more in chunks until --warmup-s have passed -- the GPU idled through the set-up and its
+    # clocks need a few hundred ms of load to come back (the first ~30 ms of work run ~7 % slower).  Every rank runs as
+    # many chunks as rank 0 decides, so that the collectives of the N > 1 path stay matched.
+    t_w = time.perf_counter()
+    warm_steps = args.warmup
     for _ in range(args.warmup):
         run_step()
     drain()
-    regions = []
-    # the number of regions must be the same on every rank: rank 0 decides, from max-over-ranks times
+    torch.cuda.synchronize()
     while True:
-        regions.append(timed_region())
-        more = len(regions) < args.repeats or (sum(regions) < 0.3 and len(regions) < 50)
+        more = time.perf_counter() - t_w < args.warmup_s
         if world > 1:
             flag = torch.tensor([1 if more else 0], dtype=torch.int32, device="cpu" if backend == "gloo" else "cuda")
             dist.broadcast(flag, src=0)
             more = bool(flag.item())
         if not more:
             break
-    dt = float(np.median(regions))
+        for _ in range(max(8, args.warmup)):
+            run_step()
+        warm_steps += max(8, args.warmup)
+        drain()
+        torch.cuda.synchronize()
+    warm_s = time.perf_counter() - t_w
+    # the timed steps start at lane 0, input batch 0, ring slot 0 whatever the warm-up ran: the same arguments give the
+    # same batch to every timed step (and the same output to --dump-outputs)
+    counter[0] = 0
+    for ln in lanes:
+        ln["rot"] = 0
+        if pipelined:
+            ln["sched"].count = 0
+    dt = timed_region()
+    outputs = {"output": last_output()} if args.dump_outputs and rank == 0 else None
     # "image" / "fixed" / "auto": every input of the run was inside the byte kernel's domain (raises otherwise: a replay
     # loop, unlike Pipelined.forward, recomputes nothing)
     (pipe if pipe is not None else model).check_domain()
+    if outputs is not None:
+        dump_outputs(args.dump_outputs, outputs)
 
     # the cache-resident figure beside the headline: the same replay loop on ONE input batch per lane
     cache_resident = None
-    if lanes and R > 1 and not pipelined:
+    if args.full and lanes and R > 1 and not pipelined:
         rotate_on[0] = False
         for _ in range(args.warmup):
             run_step()
@@ -698,7 +793,7 @@ def main_rank(args):
                           "note": "every lane replays ONE 50 MB input batch, which stays in the 256 MB Infinity Cache"}
 
     ring_check = None
-    if pipelined and rank == 0:
+    if args.full and pipelined and rank == 0:
         # a gathered block must hold this rank's ring at its own offset, bit for bit and finite; and a ring slot the
         # region wrote must be what the eager forward gives for that slot's input batch
         torch.cuda.synchronize()
@@ -714,7 +809,7 @@ def main_rank(args):
         ring_check = "gathered == ring (finite, bit for bit); slot 0 == eager forward of its input batch"
 
     gather_every_1 = None
-    if pipelined and G > 1:
+    if args.full and pipelined and G > 1:
         every1[0] = True
         for _ in range(args.warmup):
             run_step()
@@ -738,31 +833,6 @@ def main_rank(args):
     if rank == 0:
         ms_per_step = dt / args.steps * 1e3
         value = global_batch * args.steps / dt
-        d = per_kernel[dom]
-        hbm_gbs = d["bytes"] / (d["ms"] * 1e-3) / 1e9
-        tkey = d["kernel"] + (":%s" % d["shape"][-1] if d.get("shape") and str(d["shape"][-1]).startswith("res_") else "")
-        traffic, rocprof_name = load_traffic(tkey, args.workload + ("" if (args.first_layer == "exact" or not fused)
-                                                                    else "+first_" + args.first_layer))
-        common = {"kernel": d["kernel"], "rocprof_kernel": rocprof_name, "layer_index": dom,
-                  "launches_per_step": d["launches"], "avg_launch_ms": d["ms"],
-                  "back_to_back_launch_ms": d.get("b2b_ms"),
-                  "algorithmic_bytes_per_launch": d["bytes"], "traffic": traffic}
-        if d["kernel"].startswith("mfma_") and 2.0 * d["macs"] / (MFMA_PEAK_TFLOPS["f32" if d["pipe"] == "f32" else "i8"] * 1e12) \
-                >= d["bytes"] / (HBM_PEAK_GBS * 1e9):
-            kind = "f32" if d["pipe"] == "f32" else "i8"
-            achieved = 2.0 * d["macs"] / (d["ms"] * 1e-3) / 1e12
-            roof = dict(common, bound="mfma", achieved=achieved, peak=MFMA_PEAK_TFLOPS[kind], unit="TFLOP/s",
-                        frac=achieved / MFMA_PEAK_TFLOPS[kind], mfma_dtype=kind,
-                        algorithmic_flops_per_launch=2.0 * d["macs"], hbm_GBps=hbm_gbs,
-                        hbm_frac=hbm_gbs / HBM_PEAK_GBS)
-        else:
-            roof = dict(common, bound="hbm", achieved=hbm_gbs, peak=HBM_PEAK_GBS, unit="GB/s",
-                        frac=hbm_gbs / HBM_PEAK_GBS)
-        # one end-to-end fraction: the sum of every launch's own roofline time over the measured step
-        roof_ms = sum(layer_roof_ms(k) * k["launches"] for k in per_kernel)
-        per_gpu_step_ms = ms_per_step
-        roof["pipeline_roof_ms"] = roof_ms
-        roof["pipeline_frac"] = roof_ms / per_gpu_step_ms
         m1_bytes = M1_BYTES[idx] - (3 * cf.dim * cf.dim * cf.channels if u8 else 0)     # bytes instead of float32 images
         out = {
             "metric": "images/sec @ batch 4096, CIFAR-10 VGG full-qnn 4/4; % HBM roofline",
@@ -787,20 +857,17 @@ def main_rank(args):
                        "cache_resident": cache_resident, "gather_every_1": gather_every_1,
                        "logits_gather": ("one all-gather per %d batches of a lane, asynchronous" % G) if pipelined
                        else ("per batch" if use_dist else None),
-                       "timed_regions": len(regions),
-                       "region_ms_min_median_max": [round(min(regions) * 1e3, 4), round(dt * 1e3, 4),
-                                                    round(max(regions) * 1e3, 4)],
+                       "timed_regions": 1, "region_ms": round(dt * 1e3, 4),
+                       "warmup_steps_run": warm_steps, "warmup_seconds": round(warm_s, 3),
                        # the metric's "% HBM roofline" for what the fused engine really moves: M1 bytes per
-                       # image x images/s per GPU over 8 TB/s (the path is compute-bound, see roofline)
+                       # image x images/s per GPU over 8 TB/s (the path is compute-bound, see roofline under --full)
                        "m1_hbm_frac": value / world * m1_bytes / (HBM_PEAK_GBS * 1e9)},
-            "roofline": roof,
-            "kernels": [{"kernel": k["kernel"], "launches": k["launches"], "ms": round(k["ms"], 5),
-                         "GBps": round(k["bytes"] / (k["ms"] * 1e-3) / 1e9, 2),
-                         "TMACps": round(k["macs"] / (k["ms"] * 1e-3) / 1e12, 3),
-                         "roof_ms": round(layer_roof_ms(k), 5),
-                         **({"shape": list(k["shape"])} if "shape" in k else {})} for k in per_kernel],
         }
-        if world == 1 and fused and lanes and not use_dist and not args.no_alternatives:
+        if args.full:
+            out["roofline"], out["kernels"] = roofline(
+                per_kernel, ms_per_step,
+                args.workload + ("" if (args.first_layer == "exact" or not fused) else "+first_" + args.first_layer))
+        if args.full and world == 1 and fused and lanes and not use_dist and not args.no_alternatives:
             # the same workload through the other first-layer entries, same graphs-in-flight scheme and the same number
             # of steps per region (NOT the headline; `config.first_layer` names the one `value` was measured with)
             alts = {}
@@ -860,7 +927,7 @@ def main_rank(args):
                 del mp, xb, yb
             except Exception as exc:  # pragma: no cover
                 out["model_predict_resident"] = {"error": str(exc)}
-        if args.workload == "vgg64_full_qnn_w4a4":
+        if args.full and args.workload == "vgg64_full_qnn_w4a4":
             # the first layer's codes on THESE 4096 images against the reference's own first conv group, as generated by
             # tests/golden/make_fixtures_from_reference.py and asserted on the GPU by tests/test_gpu_u8.py
             try:
@@ -880,12 +947,12 @@ def main_rank(args):
                               "these counts on the GPU (fixed-point entry not covered)"}
             except Exception as exc:  # pragma: no cover
                 out["first_layer_vs_reference"] = {"error": str(exc)}
-        if world == 1 and not use_dist and not args.no_targets and args.workload == "vgg64_full_qnn_w4a4":
+        if args.full and world == 1 and not use_dist and not args.no_targets and args.workload == "vgg64_full_qnn_w4a4":
             try:
                 out["targets"] = measure_targets(torch, pkg, args)
             except Exception as exc:  # pragma: no cover
                 out["targets"] = {"error": str(exc)}
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             try:
                 out["cpu_baseline"] = importlib.import_module("oracle.cpu_baseline").run(cf, spec, seconds=12.0)
             except Exception as exc:  # pragma: no cover

@@ -143,7 +143,11 @@ def _build():
 def test_argument_checks_and_error_paths_under_asan_ubsan():
     lib, rt = _build()
     assert rt, "libclang_rt.asan-x86_64.so not found next to hipcc's clang"
-    env = dict(os.environ, QNN_LIB=lib, LD_PRELOAD=rt,
+    # the child drives the no-device paths: on a machine with a GPU it must not see it (an ASan host process does not
+    # initialise the device); the ASan runtime goes in front of whatever the environment already preloads
+    preload = os.environ.get("LD_PRELOAD")
+    env = dict(os.environ, QNN_LIB=lib, LD_PRELOAD=rt + (":" + preload if preload else ""),
+               HIP_VISIBLE_DEVICES="-1", ROCR_VISIBLE_DEVICES="-1",
                ASAN_OPTIONS="detect_leaks=0:halt_on_error=1:abort_on_error=0:exitcode=99",
                UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1:exitcode=98")
     p = subprocess.run([sys.executable, "-c", CHILD], env=env, capture_output=True, text=True, timeout=600)

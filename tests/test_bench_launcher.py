@@ -136,3 +136,26 @@ def test_supervise_real_children_success_relays_last_line(capsys):
     r1 = subprocess.Popen([sys.executable, "-c", "pass"])
     assert bench.supervise([r0, r1], deadline_s=60.0) == 0
     assert capsys.readouterr().out.strip().splitlines() == ['{"n_gpus": 2}']
+
+
+def test_plain_run_is_the_default_and_full_is_an_option():
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.steps == 7 and a.warmup == 2 and a.full is False and a.dump_outputs is None
+    a = bench.parse_args(["--full", "--dump-outputs", "out"])
+    assert a.full is True and a.dump_outputs == "out"
+
+
+def test_dump_outputs_writes_float_arrays_within_the_budget(tmp_path):
+    """--dump-outputs: float32 (float64 kept) .npy files; an array over the budget keeps a fixed, seeded sample of its
+    rows, the same on every call."""
+    import numpy as np
+    small = np.arange(40, dtype=np.int32).reshape(4, 10)
+    wide = np.random.default_rng(1).standard_normal((1000, 64))
+    bench.dump_outputs(str(tmp_path / "a"), {"small": small, "wide": wide}, budget=2 * 64 * 8 * 100)
+    bench.dump_outputs(str(tmp_path / "b"), {"small": small, "wide": wide}, budget=2 * 64 * 8 * 100)
+    s = np.load(tmp_path / "a" / "small.npy")
+    assert s.dtype == np.float32 and np.array_equal(s, small)
+    w = np.load(tmp_path / "a" / "wide.npy")
+    assert w.dtype == np.float64 and w.shape == (100, 64) and w.nbytes <= 64 * 8 * 100
+    assert np.array_equal(w, np.load(tmp_path / "b" / "wide.npy"))
+    assert all(any(np.array_equal(r, q) for q in wide) for r in w[:5])

@@ -125,8 +125,8 @@ def test_pipelined_residual_and_ternary_networks():
     np.testing.assert_array_equal(model.predict(x, batch_size=16), want)   # batch statistics per 16-image batch
 
 
-def test_bench_default_line_carries_the_contract_and_the_round3_blocks():
-    """bench.py end to end at a small batch (a subprocess, as the driver runs it): one JSON line with the contract's
+def test_bench_full_line_carries_the_contract_and_the_round3_blocks():
+    """bench.py --full end to end at a small batch (a subprocess, as the benchmark is run): one JSON line with the contract's
     keys, `roofline`, `cpu_baseline`, the first-layer alternatives, the product-call figure and the targets block."""
     import json
     import os
@@ -134,7 +134,7 @@ def test_bench_default_line_carries_the_contract_and_the_round3_blocks():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "4", "--warmup", "2", "--batch", "512",
-                        "--repeats", "2"], capture_output=True, text=True, timeout=900)
+                        "--repeats", "2", "--full"], capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.strip()]
     assert len(lines) == 1
@@ -151,6 +151,38 @@ def test_bench_default_line_carries_the_contract_and_the_round3_blocks():
     t = out["targets"]
     assert t["xnor_m0_hbm_frac"] > 0 and t["int8_mfma_frac"]["layers"] == 8
     assert set(t["images_per_s"]) == {"vgg64_full_bnn", "vgg_large_full_qnn_w8a8", "imagenet224_resnet10_w4a4"}
+
+
+def test_bench_plain_line_times_the_steps_and_dumps_the_last_output(tmp_path):
+    """A plain bench.py run: the contract's keys, ONE region of exactly --steps steps and nothing measured beside the
+    headline; --dump-outputs writes the logits of the last timed step, which (one lane, one input batch) are the eager
+    forward of the run's seeded batch, bit for bit."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--batch", "512",
+                        "--inflight", "1", "--rotate", "1", "--dump-outputs", str(tmp_path)],
+                       capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [l for l in p.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1
+    out = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+              "vs_baseline", "dtype", "data", "config"):
+        assert k in out, k
+    assert out["steps"] == 3 and out["config"]["timed_regions"] == 1 and out["ms_per_step"] > 0
+    assert abs(out["value"] * out["ms_per_step"] * 1e-3 - 512) < 1e-6 * 512
+    assert not {"roofline", "kernels", "cpu_baseline", "targets", "first_layer_alternatives", "model_predict_resident",
+                "first_layer_vs_reference"} & set(out), sorted(out)
+    assert os.listdir(tmp_path) == ["output.npy"]
+    got = np.load(os.path.join(tmp_path, "output.npy"))
+    cf = nets.baseline_config(2)
+    spec = nets.build_spec(cf, nets.SEED_BASE + 2)
+    want = host(engine.FusedModel(spec)(dev(nets.synthetic_images(cf, 512, nets.SEED_BASE + 2))))
+    assert got.dtype == np.float32 and got.shape == want.shape == (512, 10)
+    np.testing.assert_array_equal(got, want)
 
 
 # ---------------------------------------------------------------------------------------------------------------

@@ -6,7 +6,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/pmc_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-ARGS="--steps 8 --warmup 2 --no-cpu-baseline $*"
+ARGS="--full --steps 8 --warmup 2 --no-cpu-baseline $*"
 i=0
 while read -r CTRS; do
   [ -z "$CTRS" ] && continue

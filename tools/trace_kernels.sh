@@ -6,7 +6,7 @@ D=quantizedneuralnetworks-keras-tensorflow_amd/csrc
 ROOT=$(pwd)
 cp $D/libqnn_hip.so /tmp/orig.so
 cd /tmp && export TMPDIR=/tmp
-run() { rm -rf /tmp/tr_$1; rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/tr_$1 -- python3 $ROOT/bench.py --steps 20 --warmup 5 --no-cpu-baseline > /tmp/tr_$1.log 2>&1; python3 - $1 <<'PY'
+run() { rm -rf /tmp/tr_$1; rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/tr_$1 -- python3 $ROOT/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > /tmp/tr_$1.log 2>&1; python3 - $1 <<'PY'
 import csv, glob, sys, collections
 tag = sys.argv[1]
 f = glob.glob("/tmp/tr_%s/**/*kernel_trace.csv" % tag, recursive=True)[0]
