@@ -98,6 +98,12 @@ extern "C" {
 #define QNN_FN_QUANTIZED_TANH  2   /* quantized_ops.py:87-100 (= quantize_op)    */
 #define QNN_FN_TERNARY_TANH    3   /* ternary_ops.py:52-54                      */
 #define QNN_FN_GRID            4   /* input is already on the grid: encode only  */
+/* Keras LeakyReLU() at its default alpha = float32(0.3) (models/model_factory.py:27,34,43,54; the checkpoints store
+ * alpha 0.30000001192092896): v >= 0 ? v : v * 0.3f, one rounding.  Fused only with out_store = QNN_STORE_F32, no fold,
+ * no in-launch projection and no QNN_STORE_U8 input; k_conv_generic and the float32-activation matrix-pipe kernel
+ * implement it, every other kernel declines a call that carries it.  Added without an ABI version step: callers that
+ * never pass it see no change. */
+#define QNN_FN_LEAKY_RELU      5
 
 typedef struct qnn_weights qnn_weights_t;   /* opaque prepacked layer weights */
 typedef struct qnn_fold qnn_fold_t;         /* opaque: one layer's epilogue folded over its accumulator domain (below) */
@@ -112,7 +118,7 @@ typedef struct qnn_fold qnn_fold_t;         /* opaque: one layer's epilogue fold
  *   v = (res[pixel][c] + v) * post_scale      residual merge of models/resnet.py:127-128:
  *                                             keras.layers.add([x, y]) then Lambda(x*0.5);
  *                                             only if res != NULL (pool must be 1)
- *   v = fn(v)                                 binary_tanh / quantized_tanh(act_bits)
+ *   v = fn(v)                                 binary_tanh / quantized_tanh(act_bits) / leaky_relu
  *   v = max over a pool x pool window         MaxPooling2D(2,2) (vgg.py:23,30,37)
  *   store as out_store (F32 value, or packed code)
  * bn_inv / bn_shift are device pointers to per-channel float32 constants formed

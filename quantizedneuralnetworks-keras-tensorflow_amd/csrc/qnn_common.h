@@ -65,6 +65,7 @@ struct qnn_weights {
     uint32_t* d_head;     // dense 1024 -> <= 16 int4 heads: the per-lane table of the fused conv + classifier kernel
     uint32_t* h_flag;     // domain flag (pinned, device-visible host word; qnn_weights_check) or nullptr
     uint32_t* d_flag;     // the same word through the device's address space
+    float* d_f32act;      // float32-activation kernel (qnn_f32act.hip): filters k-step major [cout/16][K/4][64 lanes], or nullptr
 };
 
 struct ConvGeom;
@@ -77,6 +78,9 @@ int qnn_head_prepare(qnn_weights* w, hipStream_t s);
 int qnn_try_launch_stem(const ConvGeom& g, const EpiArgs& e, const void* x, const float* wq, void* y, hipStream_t s);
 int qnn_try_launch_first_fixed(const ConvGeom& g, const EpiArgs& e, const void* x, const qnn_weights* w, void* y,
                                hipStream_t s);
+int qnn_f32act_prepare(qnn_weights* w, hipStream_t s);
+int qnn_try_launch_f32act(const ConvGeom& g, const EpiArgs& e, const void* x, const qnn_weights* w, void* y,
+                          hipStream_t s, char* name, size_t name_len);
 int qnn_try_launch_first_u8(const ConvGeom& g, const EpiArgs& e, const void* x, const qnn_weights* w, void* y,
                             hipStream_t s, bool f32in);
 
@@ -200,6 +204,11 @@ __device__ __forceinline__ float qnn_quant_code_f(float x, float m) {
 __device__ __forceinline__ float qnn_quantized_tanh(float x, float m) {
     const float inv_m = __uint_as_float(0x7F000000u - __float_as_uint(m));
     return __fmul_rn(qnn_quant_code_f(x, m), inv_m);
+}
+
+// Keras LeakyReLU() at its default alpha = float32(0.3): one rounding, as torch.where(v >= 0, v, v * 0.3) computes it
+__device__ __forceinline__ float qnn_leaky_relu(float v) {
+    return v >= 0.0f ? v : __fmul_rn(v, 0.3f);
 }
 
 // ---- dot products on packed words ----------------------------------------------

@@ -281,6 +281,7 @@ __global__ __launch_bounds__(kBlock) void k_conv_generic(ConvGeom g, EpiArgs e, 
                 v = qnn_epi_residual(v, (long)q, c, e);
                 if (e.fn == QNN_FN_BINARY_TANH) v = qnn_binary_tanh(v);
                 else if (e.fn == QNN_FN_QUANTIZED_TANH) v = qnn_quantized_tanh(v, e.act_m);
+                else if (e.fn == QNN_FN_LEAKY_RELU) v = qnn_leaky_relu(v);
                 best = (s == 0) ? v : fmaxf(best, v);
             }
             ((float*)y)[i] = best;
@@ -1122,8 +1123,11 @@ int check_epilogue(const qnn_weights* w, const qnn_epilogue_t* epi, int xshift, 
     e->out_store = epi->out_store;
     e->act_m = 1.0f;
     QNN_REQUIRE(epi->fn == QNN_FN_NONE || epi->fn == QNN_FN_BINARY_TANH ||
-                    epi->fn == QNN_FN_QUANTIZED_TANH,
+                    epi->fn == QNN_FN_QUANTIZED_TANH || epi->fn == QNN_FN_LEAKY_RELU,
                 QNN_EINVAL, "epilogue: fn=%d cannot be fused", epi->fn);
+    QNN_REQUIRE(epi->fn != QNN_FN_LEAKY_RELU ||
+                    (epi->out_store == QNN_STORE_F32 && !epi->fold && !epi->proj && x_store != QNN_STORE_U8),
+                QNN_EINVAL, "epilogue: leaky_relu needs a float32 output, no fold, no projection and no QNN_STORE_U8 input");
     if (epi->fn == QNN_FN_QUANTIZED_TANH) {
         QNN_REQUIRE(epi->act_bits >= 2 && epi->act_bits <= 24, QNN_EINVAL,
                     "epilogue: act_bits=%d", epi->act_bits);
@@ -1299,6 +1303,8 @@ int conv_forward(const qnn_weights* w, const void* x, int x_store, int x_bits, i
     const bool trick = e.trick_s != 0.0f;
     QNN_REQUIRE(!(trick && dense), QNN_EINVAL, "dense_forward: the reference's Dense layers have no identity trick");
     const int pref = trick ? 1 : qnn_conv_impl_pref();
+    // leaky_relu: only k_conv_generic and the float32-activation matrix-pipe kernel implement it
+    const bool leaky = e.fn == QNN_FN_LEAKY_RELU;
     bool launched = false;
     if (e.proj_x) {
         // the in-launch projection shortcut: the row-walking strip kernel or nothing (the caller keeps two launches)
@@ -1309,7 +1315,7 @@ int conv_forward(const qnn_weights* w, const void* x, int x_store, int x_bits, i
         QNN_HIP(hipGetLastError());
         return QNN_OK;
     }
-    if (dense && !e.res && x_store != QNN_STORE_F32 && e.out_store == QNN_STORE_F32 && (w->kwords % 4) == 0) {
+    if (!leaky && dense && !e.res && x_store != QNN_STORE_F32 && e.out_store == QNN_STORE_F32 && (w->kwords % 4) == 0) {
         int rc2 = x_store == QNN_STORE_BIN  ? launch_dense<QNN_STORE_BIN>(x, w, e, y, N, s)
                   : x_store == QNN_STORE_T2 ? launch_dense<QNN_STORE_T2>(x, w, e, y, N, s)
                   : x_store == QNN_STORE_I4 ? launch_dense<QNN_STORE_I4>(x, w, e, y, N, s)
@@ -1320,7 +1326,7 @@ int conv_forward(const qnn_weights* w, const void* x, int x_store, int x_bits, i
                                                      : x_store == QNN_STORE_I4 ? "i4" : "i8");
         }
     }
-    if (!launched && dense && !e.res && x_store == QNN_STORE_F32 && e.out_store == QNN_STORE_F32 && w->d_wq &&
+    if (!launched && !leaky && dense && !e.res && x_store == QNN_STORE_F32 && e.out_store == QNN_STORE_F32 && w->d_wq &&
         (long)N * g.cout < 2000000000L) {
         const unsigned blocks = (unsigned)((long)N * g.cout);
         hipLaunchKernelGGL(k_dense_f32in, dim3(blocks), dim3(64), 0, s, e, N, g.cin, g.cout,
@@ -1328,7 +1334,7 @@ int conv_forward(const qnn_weights* w, const void* x, int x_store, int x_bits, i
         launched = true;
         snprintf(name, sizeof(name), "dense_f32");
     }
-    if (!launched && !dense && !trick && x_store == QNN_STORE_I4 && try_launch_pw_f32(g, e, x, w, y, s) == 0) {
+    if (!launched && !leaky && !dense && !trick && x_store == QNN_STORE_I4 && try_launch_pw_f32(g, e, x, w, y, s) == 0) {
         launched = true;
         snprintf(name, sizeof(name), "pw_i4_f32");
     }
@@ -1347,20 +1353,23 @@ int conv_forward(const qnn_weights* w, const void* x, int x_store, int x_bits, i
         return QNN_OK;
     }
     // opt-in: float32 images that are bytes / 255 on the byte kernels (qnn_first_u8.hip, F32IN; also the ResNet stem)
-    if (!launched && pref != 1 && !dense && x_store == QNN_STORE_F32 && first_mode == 1 &&
+    if (!launched && !leaky && pref != 1 && !dense && x_store == QNN_STORE_F32 && first_mode == 1 &&
         qnn_try_launch_first_u8(g, e, x, w, y, s, true) == 0) {
         launched = true;
         snprintf(name, sizeof(name), "mfma_i8_first_img255");
     }
-    if (!launched && pref != 1 && !dense && x_store == QNN_STORE_F32 && qnn_try_launch_stem(g, e, x, w->d_wq, y, s) == 0) {
+    if (!launched && !leaky && pref != 1 && !dense && x_store == QNN_STORE_F32 && qnn_try_launch_stem(g, e, x, w->d_wq, y, s) == 0) {
         launched = true;                           // float-input layer with few filters (ResNet stem)
         snprintf(name, sizeof(name), "mfma_f32_stem_cin%d", g.cin);
     }
-    if (!launched && pref != 1 && !dense)          // residual epilogues: only where the MFMA kernel has one
+    if (!launched && !leaky && pref != 1 && !dense)   // residual epilogues: only where the MFMA kernel has one
         launched = qnn_try_launch_mfma(g, e, x_store, x, w, y, s, name, sizeof(name)) == 0;
-    if (!launched && x_store == QNN_STORE_BIN && !dense && !e.res && !trick)
+    if (!launched && !leaky && x_store == QNN_STORE_BIN && !dense && !e.res && !trick)
         launched = try_launch_xnor_pk(g, e, x, w, y, s, name, sizeof(name)) == 0;
-    if (!launched) launched = try_launch_ps(g, e, x_store, x, w, y, s, name, sizeof(name)) == 0;
+    if (!launched && !leaky) launched = try_launch_ps(g, e, x_store, x, w, y, s, name, sizeof(name)) == 0;
+    // float32 activations with 16 / 32 / 64 channels (the LeakyReLU networks): the f32 matrix pipe, same FMA chain
+    if (!launched && pref != 1 && !dense && x_store == QNN_STORE_F32 && first_mode == 0)
+        launched = qnn_try_launch_f32act(g, e, x, w, y, s, name, sizeof(name)) == 0;
     if (launched) {
         qnn_set_kernel_name(name);
     } else {
@@ -1485,7 +1494,8 @@ extern "C" int qnn_prepack_weights(int wkind, int wbits, float H, const float* k
         }
     }
     PREPACK_HIP(hipGetLastError());
-    if (qnn_mfma_prepare_weights(w, s) != QNN_OK || qnn_head_prepare(w, s) != QNN_OK) {
+    if (qnn_mfma_prepare_weights(w, s) != QNN_OK || qnn_head_prepare(w, s) != QNN_OK ||
+        qnn_f32act_prepare(w, s) != QNN_OK) {
         qnn_free_weights(w);
         return QNN_EHIP;
     }
@@ -1498,6 +1508,7 @@ extern "C" int qnn_free_weights(qnn_weights_t* w) {
     if (!w) return QNN_OK;
     if (w->d_packed) (void)hipFree(w->d_packed);
     if (w->d_wq) (void)hipFree(w->d_wq);
+    if (w->d_f32act) (void)hipFree(w->d_f32act);
     if (w->d_bias) (void)hipFree(w->d_bias);
     if (w->d_corr) (void)hipFree(w->d_corr);
     if (w->d_mfma_own) (void)hipFree(w->d_mfma_own);
@@ -1556,8 +1567,10 @@ extern "C" int qnn_conv2d_forward_f32in(const qnn_weights_t* w, const float* x, 
     QNN_REQUIRE(in_fn == QNN_FN_BINARY_TANH || in_fn == QNN_FN_QUANTIZED_TANH || in_fn == QNN_FN_GRID,
                 QNN_EINVAL, "qnn_conv2d_forward_f32in: in_fn=%d", in_fn);
     const int x_bits = w->store == QNN_STORE_BIN ? 1 : in_bits;
+    // the fused binarize + XNOR kernel implements fn NONE / BINARY_TANH / QUANTIZED_TANH; leaky_relu goes the packed
+    // route, where conv_forward hands it to k_conv_generic
     if (w->store == QNN_STORE_BIN && epi->out_store == QNN_STORE_F32 && epi->pool == 1 && N > 0 &&
-        !epi->res && epi->trick_s == 0.0f && qnn_conv_impl_pref() != 2) {
+        !epi->res && epi->trick_s == 0.0f && epi->fn != QNN_FN_LEAKY_RELU && qnn_conv_impl_pref() != 2) {
         ConvGeom g;
         g.N = N; g.H = H; g.W = W;
         g.cin = w->cin; g.cout = w->cout; g.kh = w->kh; g.kw = w->kw; g.stride = w->stride;

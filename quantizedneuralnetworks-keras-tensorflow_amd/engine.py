@@ -892,6 +892,32 @@ class ResidualFusedModel:
                 return c, None
             return None
 
+        def leaky_on_f32_kernel(ci):
+            """True if conv `ci` reads float32 activations that only the float32-activation kernel or k_conv_generic take
+            (not the images, not 1 or 3 channels): those two implement FN_LEAKY_RELU, so fusing it costs nothing."""
+            src = ev(self.srcs[ci][0])
+            return not isinstance(src, _Packed) and src is not memo["input"] and src.shape[-1] not in (1, 3)
+
+        def leaky_plan(pre_name):
+            """LeakyReLU(alpha = 0.3) inside the launch of the conv behind it: conv -> bn -> leaky, or
+            conv -> bn -> add(shortcut) -> [scale] -> leaky with the float32 shortcut in the epilogue.
+            (conv index, bn index, shortcut name or None, post_scale), or None = not fusable."""
+            cb = conv_bn_of(pre_name)
+            if cb is not None:
+                return (cb[0], cb[1], None, 1.0) if leaky_on_f32_kernel(cb[0]) else None
+            sc_i = self._single(pre_name, "scale")
+            add_name = self.srcs[sc_i][0] if sc_i is not None else pre_name
+            post = float(self.spec[sc_i]["value"]) if sc_i is not None else 1.0
+            ad_i = self._single(add_name, "add")
+            if ad_i is None:
+                return None
+            a_n, b_n = self.srcs[ad_i]
+            for main, short in ((b_n, a_n), (a_n, b_n)):
+                cb = conv_bn_of(main)
+                if cb is not None and leaky_on_f32_kernel(cb[0]):
+                    return cb[0], cb[1], short, post
+            return None
+
         def ev(name):
             if name in memo:
                 return memo[name]
@@ -942,6 +968,11 @@ class ResidualFusedModel:
                         else:
                             out = (binary_ops.binary_tanh(pre) if fn == _abi.FN_BINARY_TANH
                                    else quantized_ops.quantized_tanh(pre, bits))
+                elif op["fn"] == "leaky_relu" and F32(op.get("alpha", 0.3)) == F32(0.3) and \
+                        (plan := leaky_plan(pre_name)) is not None:
+                    ci, bn_i, short, post = plan
+                    res = ev(short) if short is not None else None
+                    out = conv_call(ci, bn_i, res, post, _abi.FN_LEAKY_RELU, 0, _abi.STORE_F32)
                 else:
                     pre = f32(pre_name)
                     fnn = op["fn"]

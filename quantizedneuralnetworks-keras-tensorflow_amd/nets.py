@@ -440,7 +440,11 @@ def spec_from_keras_npz(path, wbits=None, abits=None):
     embedded model_config, so the shipped results/RESNET3/*.hdf5 files -- saved from an older
     ResNet variant with use_bias=True and without the 0.5 scaling -- load as they were trained.
     `nb` is not serialised by the reference (get_config omits it, quantized_layers.py:91-96):
-    pass wbits / abits (the two-character code of the file name: '44' -> 4, 4)."""
+    pass wbits / abits (the two-character code of the file name: '44' -> 4, 4).
+    TernaryConv2D / TernaryDense (the tnn / full-tnn / qtnn checkpoints 'tf', 'tt', 't2', 't4', 't8') become
+    kind "ternary" with the stored H and kernel_lr_multiplier.  For qtnn ('t2' / 't4' / 't8') the quantized
+    activation's `nb` is `abits` as passed: the reference's own loader maps all three codes to abits = 4
+    (test_resnet.py:18-41), so pass abits=4 to load them as the reference evaluates them."""
     import json
     d = np.load(path)
     cfg = json.loads(bytes(d["model_config_json"]).decode())
@@ -465,6 +469,12 @@ def spec_from_keras_npz(path, wbits=None, abits=None):
                   "klm": np.float32(c.get("kernel_lr_multiplier") or 1.0)}
             if kind == "quantized":
                 op["nb"] = int(wbits)
+        elif cls in ("TernaryConv2D", "TernaryDense"):
+            op = {"op": "conv" if cls == "TernaryConv2D" else "dense", "kind": "ternary",
+                  "kernel": d[name + "/kernel"], "bias": d[name + "/bias"] if c.get("use_bias", True) else None,
+                  "H": float(c.get("H", 1.0)), "klm": np.float32(c.get("kernel_lr_multiplier") or 1.0)}
+            if cls == "TernaryConv2D":
+                op["strides"], op["padding"] = tuple(c["strides"]), c["padding"]
         elif cls in ("QuantizedDense", "BinaryDense", "Dense"):
             kind = {"QuantizedDense": "quantized", "BinaryDense": "binary", "Dense": "float"}[cls]
             op = {"op": "dense", "kind": kind, "kernel": d[name + "/kernel"],
@@ -505,7 +515,7 @@ def spec_from_keras_npz(path, wbits=None, abits=None):
         op["dst"] = name
         spec.append(op)
         first = False
-        if cls in ("QuantizedDense", "BinaryDense", "Dense") and c.get("activation") == "softmax":
+        if cls in ("QuantizedDense", "BinaryDense", "TernaryDense", "Dense") and c.get("activation") == "softmax":
             spec.append({"op": "softmax", "src": name, "dst": name + "_softmax"})
     return spec
 
