@@ -71,8 +71,6 @@ struct qnn_weights {
 struct ConvGeom;
 struct EpiArgs;
 int qnn_mfma_prepare_weights(qnn_weights* w, hipStream_t s);
-int qnn_try_launch_mfma(const ConvGeom& g, const EpiArgs& e, int x_store, const void* x,
-                        const qnn_weights* w, void* y, hipStream_t s, char* name, size_t name_len);
 int qnn_conv_impl_pref();
 int qnn_head_prepare(qnn_weights* w, hipStream_t s);
 int qnn_try_launch_stem(const ConvGeom& g, const EpiArgs& e, const void* x, const float* wq, void* y, hipStream_t s);
@@ -145,6 +143,23 @@ struct EpiArgs {
     float proj_scale;          // 2^-(wshift + x_bits - 1) of the projection
     int proj_cin, proj_H, proj_W;
 };
+
+// One conv call as every route of the dispatch sees it: validated, geometry and epilogue filled in once
+// (conv_describe, qnn_conv.hip).
+struct ConvCall {
+    ConvGeom g;
+    EpiArgs e;
+    const qnn_weights* w;
+    const void* x;
+    int x_store;               // QNN_STORE_F32 also for the typed float32 stores: their domain is e.first_mode
+    void* y;
+    hipStream_t s;
+    bool dense;
+};
+// the matrix-pipe routes of qnn_mfma.hip: 0 = launched (and `name` set), 1 = declined
+int qnn_route_first_f32(const ConvCall& c, char* name, size_t name_len);
+int qnn_route_strip(const ConvCall& c, char* name, size_t name_len);
+int qnn_route_gemm(const ConvCall& c, char* name, size_t name_len);
 
 #ifdef __HIPCC__
 #define QNN_HD __host__ __device__

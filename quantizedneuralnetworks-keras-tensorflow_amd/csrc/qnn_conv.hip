@@ -1227,11 +1227,13 @@ int check_epilogue(const qnn_weights* w, const qnn_epilogue_t* epi, int xshift, 
     return QNN_OK;
 }
 
-int conv_forward(const qnn_weights* w, const void* x, int x_store, int x_bits, int N, int H,
-                 int W, const qnn_epilogue_t* epi, void* y, void* stream, bool dense) {
+// Validates one conv call and describes it in `c`: geometry, epilogue arguments, input store.  The argument checks of
+// qnn_conv2d_forward / qnn_dense_forward, in their order; the other entries call it after their own.
+int conv_describe(ConvCall* c, const qnn_weights* w, const void* x, int x_store, int x_bits, int N, int H, int W,
+                  const qnn_epilogue_t* epi, void* y, void* stream, bool dense) {
     QNN_REQUIRE(w && x && y && epi, QNN_EINVAL, "conv_forward: null pointer");
     QNN_REQUIRE(N >= 0 && H > 0 && W > 0, QNN_EINVAL, "conv_forward: N=%d H=%d W=%d", N, H, W);
-    // float32 input with a declared domain (the typed entry of this call): handed to the first-layer dispatch in the
+    // float32 input with a declared domain (the typed entry of this call): handed to the first-layer routes in the
     // epilogue arguments
     int first_mode = 0;
     if (x_store == QNN_STORE_F32_IMAGE || x_store == QNN_STORE_F32_UNIT) {
@@ -1262,7 +1264,7 @@ int conv_forward(const qnn_weights* w, const void* x, int x_store, int x_bits, i
             xshift = x_bits - 1;
         }
     }
-    ConvGeom g;
+    ConvGeom& g = c->g;
     g.N = N; g.H = H; g.W = W;
     g.cin = w->cin; g.cout = w->cout; g.kh = w->kh; g.kw = w->kw; g.stride = w->stride;
     qnn_same_pad(H, w->kh, w->stride, w->same_pad, &g.Ho, &g.pt);
@@ -1278,7 +1280,7 @@ int conv_forward(const qnn_weights* w, const void* x, int x_store, int x_bits, i
                 QNN_EUNSUPPORTED, "conv_forward: more than 2^31 output pixels in one call");
     g.fd_wp = qnn_fastdiv((uint32_t)g.Wp);
     g.fd_hp = qnn_fastdiv((uint32_t)g.Hp);
-    EpiArgs e;
+    EpiArgs& e = c->e;
     int rc = check_epilogue(w, epi, xshift, &e, x_store, first_mode);
     if (rc != QNN_OK) return rc;
     e.first_mode = first_mode;
@@ -1293,95 +1295,139 @@ int conv_forward(const qnn_weights* w, const void* x, int x_store, int x_bits, i
                       "exact first layer or QNN_STORE_U8 input");
         return QNN_EINVAL;
     }
-    if (N == 0) return QNN_OK;
+    c->w = w; c->x = x; c->x_store = x_store; c->y = y; c->s = (hipStream_t)stream; c->dense = dense;
+    return QNN_OK;
+}
 
-    hipStream_t s = (hipStream_t)stream;
-    char name[64];
-    // the pixel-stationary kernel needs whole pool windows (even Ho/Wo are not
-    // required: the remainder row/column is simply never produced)
-    // "faithful" output-side trick: only the kernels whose epilogue is qnn_epi_value implement it
-    const bool trick = e.trick_s != 0.0f;
-    QNN_REQUIRE(!(trick && dense), QNN_EINVAL, "dense_forward: the reference's Dense layers have no identity trick");
-    const int pref = trick ? 1 : qnn_conv_impl_pref();
-    // leaky_relu: only k_conv_generic and the float32-activation matrix-pipe kernel implement it
-    const bool leaky = e.fn == QNN_FN_LEAKY_RELU;
-    bool launched = false;
-    if (e.proj_x) {
-        // the in-launch projection shortcut: the row-walking strip kernel or nothing (the caller keeps two launches)
-        const bool ok = !dense && qnn_try_launch_mfma(g, e, x_store, x, w, y, s, name, sizeof(name)) == 0;
-        QNN_REQUIRE(ok, QNN_EUNSUPPORTED, "conv_forward: no kernel computes a projection shortcut for this layer "
-                    "(3x3 stride-1 int4, cin = cout in {32, 64}, proj cin = cin / 2, output ceil(H/2) x ceil(W/2) of the block input)");
-        qnn_set_kernel_name(name);
-        QNN_HIP(hipGetLastError());
-        return QNN_OK;
+// ---- the routes: 0 = launched (and `name` set), 1 = declined --------------------------------------------------------
+int route_dense(const ConvCall& c, char* name, size_t name_len) {
+    const int xs = c.x_store;
+    if (c.e.out_store != QNN_STORE_F32) return 1;
+    if (xs == QNN_STORE_F32) {
+        if (!c.w->d_wq || (long)c.g.N * c.g.cout >= 2000000000L) return 1;
+        hipLaunchKernelGGL(k_dense_f32in, dim3((unsigned)((long)c.g.N * c.g.cout)), dim3(64), 0, c.s, c.e, c.g.N, c.g.cin,
+                           c.g.cout, (const float*)c.x, c.w->d_wq, (float*)c.y);
+        snprintf(name, name_len, "dense_f32");
+        return 0;
     }
-    if (!leaky && dense && !e.res && x_store != QNN_STORE_F32 && e.out_store == QNN_STORE_F32 && (w->kwords % 4) == 0) {
-        int rc2 = x_store == QNN_STORE_BIN  ? launch_dense<QNN_STORE_BIN>(x, w, e, y, N, s)
-                  : x_store == QNN_STORE_T2 ? launch_dense<QNN_STORE_T2>(x, w, e, y, N, s)
-                  : x_store == QNN_STORE_I4 ? launch_dense<QNN_STORE_I4>(x, w, e, y, N, s)
-                                            : launch_dense<QNN_STORE_I8>(x, w, e, y, N, s);
-        if (rc2 == 0) {
-            launched = true;
-            snprintf(name, sizeof(name), "dense_%s", x_store == QNN_STORE_BIN ? "bin" : x_store == QNN_STORE_T2 ? "t2"
-                                                     : x_store == QNN_STORE_I4 ? "i4" : "i8");
-        }
-    }
-    if (!launched && !leaky && dense && !e.res && x_store == QNN_STORE_F32 && e.out_store == QNN_STORE_F32 && w->d_wq &&
-        (long)N * g.cout < 2000000000L) {
-        const unsigned blocks = (unsigned)((long)N * g.cout);
-        hipLaunchKernelGGL(k_dense_f32in, dim3(blocks), dim3(64), 0, s, e, N, g.cin, g.cout,
-                           (const float*)x, w->d_wq, (float*)y);
-        launched = true;
-        snprintf(name, sizeof(name), "dense_f32");
-    }
-    if (!launched && !leaky && !dense && !trick && x_store == QNN_STORE_I4 && try_launch_pw_f32(g, e, x, w, y, s) == 0) {
-        launched = true;
-        snprintf(name, sizeof(name), "pw_i4_f32");
-    }
-    if (x_store == QNN_STORE_U8) {
-        if (pref != 1 && qnn_try_launch_first_u8(g, e, x, w, y, s, false) == 0) {
-            qnn_set_kernel_name("mfma_i8_first_u8");
-        } else {
-            const size_t total = (size_t)g.N * g.Hp * g.Wp * e.ocw;
-            size_t blocks = (total + kBlock - 1) / kBlock;
-            if (blocks > 65535u * 16u) blocks = 65535u * 16u;
-            hipLaunchKernelGGL(k_conv_generic, dim3((unsigned)blocks), dim3(kBlock), 0, s, g, e, x_store,
-                               x, w->d_packed, w->d_wq, y);
-            qnn_set_kernel_name("generic_u8");
-        }
-        QNN_HIP(hipGetLastError());
-        return QNN_OK;
-    }
-    // opt-in: float32 images that are bytes / 255 on the byte kernels (qnn_first_u8.hip, F32IN; also the ResNet stem)
-    if (!launched && !leaky && pref != 1 && !dense && x_store == QNN_STORE_F32 && first_mode == 1 &&
-        qnn_try_launch_first_u8(g, e, x, w, y, s, true) == 0) {
-        launched = true;
-        snprintf(name, sizeof(name), "mfma_i8_first_img255");
-    }
-    if (!launched && !leaky && pref != 1 && !dense && x_store == QNN_STORE_F32 && qnn_try_launch_stem(g, e, x, w->d_wq, y, s) == 0) {
-        launched = true;                           // float-input layer with few filters (ResNet stem)
-        snprintf(name, sizeof(name), "mfma_f32_stem_cin%d", g.cin);
-    }
-    if (!launched && !leaky && pref != 1 && !dense)   // residual epilogues: only where the MFMA kernel has one
-        launched = qnn_try_launch_mfma(g, e, x_store, x, w, y, s, name, sizeof(name)) == 0;
-    if (!launched && !leaky && x_store == QNN_STORE_BIN && !dense && !e.res && !trick)
-        launched = try_launch_xnor_pk(g, e, x, w, y, s, name, sizeof(name)) == 0;
-    if (!launched && !leaky) launched = try_launch_ps(g, e, x_store, x, w, y, s, name, sizeof(name)) == 0;
-    // float32 activations with 16 / 32 / 64 channels (the LeakyReLU networks): the f32 matrix pipe, same FMA chain
-    if (!launched && pref != 1 && !dense && x_store == QNN_STORE_F32 && first_mode == 0)
-        launched = qnn_try_launch_f32act(g, e, x, w, y, s, name, sizeof(name)) == 0;
-    if (launched) {
-        qnn_set_kernel_name(name);
-    } else {
-        const size_t total = (size_t)g.N * g.Hp * g.Wp * e.ocw;
-        size_t blocks = (total + kBlock - 1) / kBlock;
-        if (blocks > 65535u * 16u) blocks = 65535u * 16u;
-        hipLaunchKernelGGL(k_conv_generic, dim3((unsigned)blocks), dim3(kBlock), 0, s, g, e, x_store,
-                           x, w->d_packed, w->d_wq, y);
-        qnn_set_kernel_name("generic");
-    }
+    if ((c.w->kwords % 4) != 0) return 1;
+    snprintf(name, name_len, "dense_%s", xs == QNN_STORE_BIN ? "bin" : xs == QNN_STORE_T2 ? "t2" : xs == QNN_STORE_I4 ? "i4" : "i8");
+    return xs == QNN_STORE_BIN  ? launch_dense<QNN_STORE_BIN>(c.x, c.w, c.e, c.y, c.g.N, c.s)
+           : xs == QNN_STORE_T2 ? launch_dense<QNN_STORE_T2>(c.x, c.w, c.e, c.y, c.g.N, c.s)
+           : xs == QNN_STORE_I4 ? launch_dense<QNN_STORE_I4>(c.x, c.w, c.e, c.y, c.g.N, c.s)
+                                : launch_dense<QNN_STORE_I8>(c.x, c.w, c.e, c.y, c.g.N, c.s);
+}
+
+int route_pw(const ConvCall& c, char* name, size_t name_len) {
+    if (c.x_store != QNN_STORE_I4 || try_launch_pw_f32(c.g, c.e, c.x, c.w, c.y, c.s) != 0) return 1;
+    snprintf(name, name_len, "pw_i4_f32");
+    return 0;
+}
+
+// image bytes (QNN_STORE_U8), and float32 images declared to be bytes / 255 (QNN_STORE_F32_IMAGE; also the ResNet stem)
+int route_first_u8(const ConvCall& c, char* name, size_t name_len) {
+    const bool f32in = c.x_store == QNN_STORE_F32;
+    if ((f32in ? c.e.first_mode != 1 : c.x_store != QNN_STORE_U8) || qnn_try_launch_first_u8(c.g, c.e, c.x, c.w, c.y, c.s, f32in))
+        return 1;
+    snprintf(name, name_len, f32in ? "mfma_i8_first_img255" : "mfma_i8_first_u8");
+    return 0;
+}
+
+// float-input layer with few filters (ResNet stem)
+int route_stem(const ConvCall& c, char* name, size_t name_len) {
+    if (c.x_store != QNN_STORE_F32 || qnn_try_launch_stem(c.g, c.e, c.x, c.w->d_wq, c.y, c.s) != 0) return 1;
+    snprintf(name, name_len, "mfma_f32_stem_cin%d", c.g.cin);
+    return 0;
+}
+
+int route_xnor_pk(const ConvCall& c, char* name, size_t name_len) {
+    return c.x_store == QNN_STORE_BIN ? try_launch_xnor_pk(c.g, c.e, c.x, c.w, c.y, c.s, name, name_len) : 1;
+}
+
+int route_ps(const ConvCall& c, char* name, size_t name_len) {
+    return try_launch_ps(c.g, c.e, c.x_store, c.x, c.w, c.y, c.s, name, name_len);
+}
+
+// float32 activations with 16 / 32 / 64 channels (the LeakyReLU networks): the f32 matrix pipe, same FMA chain
+int route_f32act(const ConvCall& c, char* name, size_t name_len) {
+    if (c.x_store != QNN_STORE_F32 || c.e.first_mode != 0) return 1;
+    return qnn_try_launch_f32act(c.g, c.e, c.x, c.w, c.y, c.s, name, name_len);
+}
+
+int route_generic(const ConvCall& c, char* name, size_t name_len) {
+    const size_t total = (size_t)c.g.N * c.g.Hp * c.g.Wp * c.e.ocw;
+    size_t blocks = (total + kBlock - 1) / kBlock;
+    if (blocks > 65535u * 16u) blocks = 65535u * 16u;
+    hipLaunchKernelGGL(k_conv_generic, dim3((unsigned)blocks), dim3(kBlock), 0, c.s, c.g, c.e, c.x_store, c.x,
+                       c.w->d_packed, c.w->d_wq, c.y);
+    snprintf(name, name_len, c.x_store == QNN_STORE_U8 ? "generic_u8" : "generic");
+    return 0;
+}
+
+// What a call uses and a route implements.  A route is skipped for a call that uses anything it lacks; the fold, the
+// QNN_EPI_* flags and the domain flag are hints a kernel may ignore without changing the bits, so they are not listed.
+enum : unsigned {
+    CAP_CONV = 1,       // convolutions (qnn_conv2d_forward)
+    CAP_DENSE = 2,      // dense layers (qnn_dense_forward)
+    CAP_RES = 4,        // residual merge (qnn_epilogue_t.res)
+    CAP_PROJ = 8,       // projection shortcut computed in the launch (qnn_epilogue_t.proj)
+    CAP_TRICK = 16,     // the faithful identity trick (qnn_epilogue_t.trick_s)
+    CAP_LEAKY = 32,     // QNN_FN_LEAKY_RELU
+};
+
+struct Route {
+    int (*launch)(const ConvCall& c, char* name, size_t name_len);
+    unsigned caps;
+    bool mfma;          // a matrix-pipe route: qnn_set_conv_impl(1) skips it
+};
+
+// in order of preference; k_conv_generic last takes every call without a projection
+const Route kRoutes[] = {
+    {route_dense, CAP_DENSE, false},
+    {route_pw, CAP_CONV, false},
+    {route_first_u8, CAP_CONV, true},
+    {route_stem, CAP_CONV, true},
+    {qnn_route_first_f32, CAP_CONV, true},
+    {qnn_route_strip, CAP_CONV | CAP_RES | CAP_PROJ, true},
+    {qnn_route_gemm, CAP_CONV | CAP_RES, true},
+    {route_xnor_pk, CAP_CONV, false},
+    {route_ps, CAP_CONV | CAP_DENSE | CAP_RES | CAP_TRICK, false},
+    {route_f32act, CAP_CONV | CAP_RES | CAP_LEAKY, true},
+    {route_generic, CAP_CONV | CAP_DENSE | CAP_RES | CAP_TRICK | CAP_LEAKY, false},
+};
+
+// the one feature check: may route (caps, mfma) take call c?
+bool route_takes(unsigned caps, bool mfma, const ConvCall& c) {
+    const EpiArgs& e = c.e;
+    const unsigned uses = (c.dense ? CAP_DENSE : CAP_CONV) | (e.res ? CAP_RES : 0u) | (e.proj_x ? CAP_PROJ : 0u) |
+                          (e.trick_s != 0.0f ? CAP_TRICK : 0u) | (e.fn == QNN_FN_LEAKY_RELU ? CAP_LEAKY : 0u);
+    // a projection call ignores the preference: no VALU kernel computes the shortcut
+    return (uses & ~caps) == 0 && !(mfma && !e.proj_x && qnn_conv_impl_pref() == 1);
+}
+
+int conv_launched(const char* name) {
+    qnn_set_kernel_name(name);
     QNN_HIP(hipGetLastError());
     return QNN_OK;
+}
+
+int conv_run(const ConvCall& c) {
+    if (c.g.N == 0) return QNN_OK;
+    QNN_REQUIRE(!(c.e.trick_s != 0.0f && c.dense), QNN_EINVAL, "dense_forward: the reference's Dense layers have no identity trick");
+    char name[64];
+    for (const Route& r : kRoutes)
+        if (route_takes(r.caps, r.mfma, c) && r.launch(c, name, sizeof(name)) == 0) return conv_launched(name);
+    // only a projection call gets here (k_conv_generic takes every other one); the caller keeps two launches
+    qnn_set_error("conv_forward: no kernel computes a projection shortcut for this layer (3x3 stride-1 int4, cin = cout in "
+                  "{32, 64}, proj cin = cin / 2, output ceil(H/2) x ceil(W/2) of the block input)");
+    return QNN_EUNSUPPORTED;
+}
+
+int conv_forward(const qnn_weights* w, const void* x, int x_store, int x_bits, int N, int H, int W,
+                 const qnn_epilogue_t* epi, void* y, void* stream, bool dense) {
+    ConvCall c;
+    const int rc = conv_describe(&c, w, x, x_store, x_bits, N, H, W, epi, y, stream, dense);
+    return rc != QNN_OK ? rc : conv_run(c);
 }
 
 }  // namespace
@@ -1567,33 +1613,21 @@ extern "C" int qnn_conv2d_forward_f32in(const qnn_weights_t* w, const float* x, 
     QNN_REQUIRE(in_fn == QNN_FN_BINARY_TANH || in_fn == QNN_FN_QUANTIZED_TANH || in_fn == QNN_FN_GRID,
                 QNN_EINVAL, "qnn_conv2d_forward_f32in: in_fn=%d", in_fn);
     const int x_bits = w->store == QNN_STORE_BIN ? 1 : in_bits;
-    // the fused binarize + XNOR kernel implements fn NONE / BINARY_TANH / QUANTIZED_TANH; leaky_relu goes the packed
-    // route, where conv_forward hands it to k_conv_generic
-    if (w->store == QNN_STORE_BIN && epi->out_store == QNN_STORE_F32 && epi->pool == 1 && N > 0 &&
-        !epi->res && epi->trick_s == 0.0f && epi->fn != QNN_FN_LEAKY_RELU && qnn_conv_impl_pref() != 2) {
-        ConvGeom g;
-        g.N = N; g.H = H; g.W = W;
-        g.cin = w->cin; g.cout = w->cout; g.kh = w->kh; g.kw = w->kw; g.stride = w->stride;
-        qnn_same_pad(H, w->kh, w->stride, w->same_pad, &g.Ho, &g.pt);
-        qnn_same_pad(W, w->kw, w->stride, w->same_pad, &g.Wo, &g.pl);
-        g.cw = w->cw; g.kwords = w->kwords; g.pool = 1; g.Hp = g.Ho; g.Wp = g.Wo;
-        g.fd_wp = qnn_fastdiv((uint32_t)g.Wp); g.fd_hp = qnn_fastdiv((uint32_t)g.Hp);
-        EpiArgs e;
-        int rc = check_epilogue(w, epi, 0, &e);
-        if (rc != QNN_OK) return rc;
-        char name[64];
-        if (try_launch_xnor_f32(g, e, in_fn, x, w, y, (hipStream_t)stream, name, sizeof(name)) == 0) {
-            qnn_set_kernel_name(name);
-            QNN_HIP(hipGetLastError());
-            return QNN_OK;
-        }
-    }
+    ConvCall c;
+    int rc = conv_describe(&c, w, x, w->store, x_bits, N, H, W, epi, y, stream, false);
+    if (rc != QNN_OK) return rc;
+    // the fused binarize + XNOR kernel (fn NONE / BINARY_TANH / QUANTIZED_TANH); qnn_set_conv_impl(2) keeps the packed route
+    char name[64];
+    if (w->store == QNN_STORE_BIN && N > 0 && qnn_conv_impl_pref() != 2 && route_takes(CAP_CONV, false, c) &&
+        try_launch_xnor_f32(c.g, c.e, in_fn, x, w, y, c.s, name, sizeof(name)) == 0)
+        return conv_launched(name);
     const size_t need = qnn_conv2d_workspace_bytes(w, N, H, W);
     QNN_REQUIRE(workspace && workspace_bytes >= need, QNN_EINVAL,
                 "qnn_conv2d_forward_f32in: workspace of %zu bytes needed, %zu given", need, workspace_bytes);
-    int rc = qnn_pack_f32(x, workspace, (size_t)N * H * W, w->cin, in_fn, x_bits, w->store, stream);
+    rc = qnn_pack_f32(x, workspace, (size_t)N * H * W, w->cin, in_fn, x_bits, w->store, stream);
     if (rc != QNN_OK) return rc;
-    return conv_forward(w, workspace, w->store, x_bits, N, H, W, epi, y, stream, false);
+    c.x = workspace;
+    return conv_run(c);
 }
 
 // The last conv group of a VGG and the classifier behind it in ONE launch (see the header).  Same result, bit for bit, as
@@ -1612,23 +1646,19 @@ extern "C" int qnn_conv2d_dense_forward(const qnn_weights_t* wc, const qnn_weigh
         return QNN_EUNSUPPORTED;
     }
     QNN_REQUIRE(x_bits >= 1 && x_bits <= 4, QNN_EINVAL, "qnn_conv2d_dense_forward: x_bits=%d", x_bits);
-    ConvGeom g;
-    g.N = N; g.H = H; g.W = W;
-    g.cin = wc->cin; g.cout = wc->cout; g.kh = wc->kh; g.kw = wc->kw; g.stride = wc->stride;
-    qnn_same_pad(H, wc->kh, wc->stride, wc->same_pad, &g.Ho, &g.pt);
-    qnn_same_pad(W, wc->kw, wc->stride, wc->same_pad, &g.Wo, &g.pl);
-    g.cw = wc->cw; g.kwords = wc->kwords; g.pool = 2;
-    g.Hp = g.Ho / 2; g.Wp = g.Wo / 2;
-    if (g.Hp <= 0 || g.Wp <= 0 || g.pt != 1 || g.pl != 1 || (g.cin % 64) != 0 || g.cin > 128 || g.cout != 64 ||
-        g.Hp * g.Wp * g.cout != wd->cin) {
+    int Ho, Wo, pt, pl;
+    qnn_same_pad(H, wc->kh, wc->stride, wc->same_pad, &Ho, &pt);
+    qnn_same_pad(W, wc->kw, wc->stride, wc->same_pad, &Wo, &pl);
+    if (Ho / 2 <= 0 || Wo / 2 <= 0 || pt != 1 || pl != 1 || (wc->cin % 64) != 0 || wc->cin > 128 || wc->cout != 64 ||
+        (Ho / 2) * (Wo / 2) * wc->cout != wd->cin) {
         qnn_set_error("qnn_conv2d_dense_forward: no fused kernel for this geometry");
         return QNN_EUNSUPPORTED;
     }
-    g.fd_wp = qnn_fastdiv((uint32_t)g.Wp);
-    g.fd_hp = qnn_fastdiv((uint32_t)g.Hp);
-    EpiArgs e, ed;
-    int rc = check_epilogue(wc, epi_conv, x_bits - 1, &e);
+    ConvCall c;
+    int rc = conv_describe(&c, wc, x, x_store, x_bits, N, H, W, epi_conv, y, stream, false);
     if (rc != QNN_OK) return rc;
+    const ConvGeom& g = c.g;
+    EpiArgs e = c.e, ed;
     const int abits = epi_conv->fn == QNN_FN_QUANTIZED_TANH ? epi_conv->act_bits : 1;     // codes the dense layer sees
     rc = check_epilogue(wd, epi_dense, abits - 1, &ed);
     if (rc != QNN_OK) return rc;
@@ -1642,15 +1672,13 @@ extern "C" int qnn_conv2d_dense_forward(const qnn_weights_t* wc, const qnn_weigh
         return QNN_EUNSUPPORTED;
     }
     mg.x_bytes = (uint32_t)xb; mg.w_bytes = (uint32_t)wb; mg.ablate = 0;
-    e.scale = e.scale * (1.0f / 256.0f);                    // both conv operands carry *16 (as qnn_try_launch_mfma)
+    e.scale = e.scale * (1.0f / 256.0f);                    // both conv operands carry *16 (as qnn_route_gemm)
     const char* kname = "";
     if (qnn_launch_areg_head(mg, e, x, wc->d_mfma, wd, ed, y, (hipStream_t)stream, &kname) != 0) {
         qnn_set_error("qnn_conv2d_dense_forward: no fused kernel for this geometry");
         return QNN_EUNSUPPORTED;
     }
-    qnn_set_kernel_name(kname);
-    QNN_HIP(hipGetLastError());
-    return QNN_OK;
+    return conv_launched(kname);
 }
 
 extern "C" int qnn_dense_forward(const qnn_weights_t* w, const void* x, int x_store, int x_bits,

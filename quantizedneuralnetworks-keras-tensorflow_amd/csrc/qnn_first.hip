@@ -1,5 +1,5 @@
 // Float-input first layer on the f32 matrix pipe (v_mfma_f32_32x32x2_f32): exact k-ordered FMA chain.
-// Dispatch: qnn_try_launch_mfma (qnn_mfma.hip).
+// Dispatch: qnn_route_first_f32 (qnn_mfma.hip).
 #include "qnn_mfma_common.h"
 
 namespace {

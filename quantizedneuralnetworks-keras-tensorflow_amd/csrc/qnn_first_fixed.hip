@@ -1,5 +1,5 @@
-// OPTIONAL fixed-point variant of the float-input first layer (qnn_set_option("first_fixed", 1); the exact FMA-chain kernel
-// of qnn_first.hip stays the default).  Dispatch: qnn_try_launch_mfma (qnn_mfma.hip).
+// OPTIONAL fixed-point variant of the float-input first layer (input declared QNN_STORE_F32_UNIT; the exact FMA-chain kernel
+// of qnn_first.hip stays the default).  Dispatch: qnn_route_first_f32 (qnn_mfma.hip).
 //
 // The exact layer cannot run faster than the f32 matrix peak allows (~96 us for 4096 x 32^2 x 3 -> 64).  For inputs in
 // [0, 1] (images / 255, utils/load_data.py:40) and weights of <= 4 bits the same convolution is an INTEGER problem:

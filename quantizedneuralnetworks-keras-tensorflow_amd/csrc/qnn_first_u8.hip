@@ -1,5 +1,5 @@
 // First layer on the dataset's own bytes: x_store = QNN_STORE_U8, value = code / 255 (utils/load_data.py:40 forms the
-// reference's float32 images exactly so).  Dispatch: conv_forward (qnn_conv.hip); any other shape with U8 input takes
+// reference's float32 images exactly so).  Dispatch: route_first_u8 (qnn_conv.hip); any other shape with U8 input takes
 // k_conv_generic, which implements the same arithmetic.
 //
 // With the integer weight codes k = w * 2^wshift the layer is an INTEGER problem with one offset:
@@ -28,7 +28,7 @@ constexpr int kRingU = 4 * kRowPitchU;         // ring of four input rows
 constexpr int kConstU = kRingU;                // four words 0x80808080: the A operand of K-block 3
 constexpr int kWaveLdsU = kRingU + 4;          // words per wave (a multiple of four: 16-byte aligned)
 
-// F32IN (opt-in, qnn_set_option("first_image", 1)): the same kernel for float32 inputs that ARE image bytes / 255
+// F32IN (opt-in, input declared QNN_STORE_F32_IMAGE; route_first_img255): the same kernel for float32 inputs that ARE image bytes / 255
 // (utils/load_data.py:40).  A staged value x is read as the byte k = rint(255 x) when |255 x - k| <= 2^-15 and
 // 0 <= k <= 255 -- true for every float32 quotient k/255 (the product is off by < 2^-16) -- and raises the layer's
 // domain flag otherwise (qnn_weights_check), exactly like the fixed-point variant.  An accepted x is within 1.5e-7 of

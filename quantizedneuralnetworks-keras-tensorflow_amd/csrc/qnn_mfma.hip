@@ -788,37 +788,36 @@ int qnn_mfma_prepare_weights(qnn_weights* w, hipStream_t s) {
     return QNN_OK;
 }
 
-// returns 0 if launched, 1 if this shape is not eligible
-int qnn_try_launch_mfma(const ConvGeom& g, const EpiArgs& e, int x_store, const void* x,
-                        const qnn_weights* w, void* y, hipStream_t s, char* name, size_t name_len) {
-    if (x_store == QNN_STORE_F32) {
-        // float-input first layer on the f32 matrix pipe
-        if (e.res) return 1;
-        if (g.kh != 3 || g.kw != 3 || (g.cin != 1 && g.cin != 3)) return 1;
-        if (g.cout != 64 && g.cout != 128 && g.cout != 256) return 1;
-        const int pw = e.out_store == QNN_STORE_F32 ? 1 : qnn_per_word(e.out_store);
-        if (g.cout % pw != 0) return 1;
-        // opt-in: float32 inputs that are image bytes / 255 on the uint8 entry's kernel (qnn_first_u8.hip, F32IN)
-        if (e.first_mode == 1 && qnn_try_launch_first_u8(g, e, x, w, y, s, true) == 0) {
-            snprintf(name, name_len, "mfma_i8_first_img255");
-            return 0;
-        }
-        // opt-in fixed-point variant (qnn_first_fixed.hip): NOT the oracle's float32 chain, see its header
-        if (e.first_mode == 2 && qnn_try_launch_first_fixed(g, e, x, w, y, s) == 0) {
-            snprintf(name, name_len, "mfma_i8x3_first_fixed");
-            return 0;
-        }
-        snprintf(name, name_len, "mfma_f32_first_cin%d", g.cin);
-        // the LDS-staged kernel works on 64-filter slices (blockIdx.y): prefer it whenever its tiling applies
-        const bool lds_shape = g.stride == 1 && g.pt == 1 && g.pl == 1 &&
-                               ((g.pool == 2 && (g.Wp % 8) == 0 && (g.H % 2) == 0 && (g.W % 2) == 0) ||
-                                (g.pool == 1 && (g.W % 32) == 0));
-        // (QNN_FIRST_GATHER, read once in qnn_first.hip, selects the gather variant for A/B timing)
-        if (lds_shape || g.cout == 64) return qnn_launch_first(g.cin, 2, g, e, x, w->d_wq, y, s);
-        return qnn_launch_first(g.cin, 4, g, e, x, w->d_wq, y, s);
+// float-input first layer on the f32 matrix pipe
+int qnn_route_first_f32(const ConvCall& c, char* name, size_t name_len) {
+    const ConvGeom& g = c.g;
+    const EpiArgs& e = c.e;
+    if (c.x_store != QNN_STORE_F32) return 1;
+    if (g.kh != 3 || g.kw != 3 || (g.cin != 1 && g.cin != 3)) return 1;
+    if (g.cout != 64 && g.cout != 128 && g.cout != 256) return 1;
+    const int pw = e.out_store == QNN_STORE_F32 ? 1 : qnn_per_word(e.out_store);
+    if (g.cout % pw != 0) return 1;
+    // opt-in fixed-point variant (qnn_first_fixed.hip): NOT the oracle's float32 chain, see its header
+    if (e.first_mode == 2 && qnn_try_launch_first_fixed(g, e, c.x, c.w, c.y, c.s) == 0) {
+        snprintf(name, name_len, "mfma_i8x3_first_fixed");
+        return 0;
     }
-    if (!w->d_mfma) return 1;
-    if (x_store != QNN_STORE_I8 && x_store != QNN_STORE_I4) return 1;
+    snprintf(name, name_len, "mfma_f32_first_cin%d", g.cin);
+    // the LDS-staged kernel works on 64-filter slices (blockIdx.y): prefer it whenever its tiling applies
+    const bool lds_shape = g.stride == 1 && g.pt == 1 && g.pl == 1 &&
+                           ((g.pool == 2 && (g.Wp % 8) == 0 && (g.H % 2) == 0 && (g.W % 2) == 0) ||
+                            (g.pool == 1 && (g.W % 32) == 0));
+    // (QNN_FIRST_GATHER, read once in qnn_first.hip, selects the gather variant for A/B timing)
+    if (lds_shape || g.cout == 64) return qnn_launch_first(g.cin, 2, g, e, c.x, c.w->d_wq, c.y, c.s);
+    return qnn_launch_first(g.cin, 4, g, e, c.x, c.w->d_wq, c.y, c.s);
+}
+
+// 3x3 int4 layers with 16 / 32 / 64 input channels: the row-walking strip kernels, then the small-channel tile kernel
+int qnn_route_strip(const ConvCall& c, char* name, size_t name_len) {
+    const ConvGeom& g = c.g;
+    const EpiArgs& e = c.e;
+    const qnn_weights* w = c.w;
+    if (!w->d_mfma || c.x_store != QNN_STORE_I4) return 1;
     static const bool small_off = QNN_ENV_STR("QNN_MFMA_SMALL_OFF") != nullptr;   // A/B switch (experiment builds only)
     // 3x3 stride-1 int4 layers with 16 / 32 / 64 input channels: row-walking strip kernel (qnn_mfma_strip.hip).
     // The residual's post-scale (models/resnet.py:128: 0.5) must be a power of two so that it folds exactly into the
@@ -833,7 +832,7 @@ int qnn_try_launch_mfma(const ConvGeom& g, const EpiArgs& e, int x_store, const 
         const bool s2 = g.stride == 2 && (g.cin == 16 || g.cin == 32) && (g.cout % 32) == 0 && !e.res;
         const bool proj_ok = !e.proj_x || (s1 && (g.cin == 32 || g.cin == 64) && g.cout == g.cin && e.proj_cin * 2 == g.cin &&
                                            !e.res && !e.fold_a && (e.proj_H + 1) / 2 == g.H && (e.proj_W + 1) / 2 == g.W);
-        const bool shape = x_store == QNN_STORE_I4 && w->store == QNN_STORE_I4 && proj_ok &&
+        const bool shape = w->store == QNN_STORE_I4 && proj_ok &&
                            (g.cin == 16 || g.cin == 32 || g.cin == 64) && g.kh == 3 && g.kw == 3 && (s1 || s2) &&
                            g.pool == 1 && e.out_store == QNN_STORE_I4 && pow2 &&
                            (!e.res || (e.res_store == QNN_STORE_I4 && e.res_cw == e.ocw) ||
@@ -855,18 +854,18 @@ int qnn_try_launch_mfma(const ConvGeom& g, const EpiArgs& e, int x_store, const 
                 // 16 -> 16 channels with a usable fold and an even width: the LDS-staged form (qnn_mfma_strip16.hip: a sixth
                 // of the load and a quarter of the store instructions)
                 static const bool lds16_off = QNN_ENV_STR("QNN_STRIP16_LDS_OFF") != nullptr;   // A/B switch (experiment builds only)
-                if (g.cin == 16 && !lds16_off && !(e.flags & QNN_EPI_NO_LDS16) && qnn_launch_strip16_lds(ms, es, x, w->d_mfma, y, s) == 0) {
+                if (g.cin == 16 && !lds16_off && !(e.flags & QNN_EPI_NO_LDS16) && qnn_launch_strip16_lds(ms, es, c.x, w->d_mfma, c.y, c.s) == 0) {
                     snprintf(name, name_len, "strip_i4_c16_lds");
                     return 0;
                 }
                 snprintf(name, name_len, g.stride == 2 ? "strip_i4_c%d_s2" : e.proj_x ? "strip_i4_c%d_proj" : "strip_i4_c%d", g.cin);
-                if (qnn_launch_strip(g.cin, ms, es, x, w->d_mfma, y, s) == 0) return 0;
+                if (qnn_launch_strip(g.cin, ms, es, c.x, w->d_mfma, c.y, c.s) == 0) return 0;
             }
         }
     }
     // small-channel 3x3 int4 layers on the tile kernel (both operands in registers)
     if (e.proj_x) return 1;      // the in-launch projection shortcut exists in the strip kernel only
-    if (x_store == QNN_STORE_I4 && w->store == QNN_STORE_I4 && (g.cin == 16 || g.cin == 32) && g.kh == 3 &&
+    if (w->store == QNN_STORE_I4 && (g.cin == 16 || g.cin == 32) && g.kh == 3 &&
         g.kw == 3 && g.stride == 1 && g.pt == 1 && g.pl == 1 && g.pool == 1 && (g.W % 16) == 0 &&
         e.out_store == QNN_STORE_I4 && (g.cout % (g.cin == 16 ? 16 : 32)) == 0 &&
         (!e.res || (e.res_store == QNN_STORE_I4 && e.res_cw == e.ocw) ||
@@ -880,10 +879,22 @@ int qnn_try_launch_mfma(const ConvGeom& g, const EpiArgs& e, int x_store, const 
             EpiArgs es = e;
             es.scale = e.scale * (1.0f / 256.0f);            // both operands carry *16
             snprintf(name, name_len, "mfma_i4_small_c%d", g.cin);
-            const int rc_ = qnn_launch_small(g.cin, ms, es, x, w->d_mfma, y, s);
-            if (rc_ == 0) return 0;
+            if (qnn_launch_small(g.cin, ms, es, c.x, w->d_mfma, c.y, c.s) == 0) return 0;
         }
     }
+    return 1;
+}
+
+// the tiled implicit-GEMM family (Cin and Cout multiples of 64): halo, operands in registers, weight-resident, tiles
+int qnn_route_gemm(const ConvCall& c, char* name, size_t name_len) {
+    const ConvGeom& g = c.g;
+    const EpiArgs& e = c.e;
+    const qnn_weights* w = c.w;
+    const void* x = c.x;
+    void* y = c.y;
+    hipStream_t s = c.s;
+    const int x_store = c.x_store;
+    if (!w->d_mfma || (x_store != QNN_STORE_I8 && x_store != QNN_STORE_I4)) return 1;
     if (g.cin % 64 != 0 || g.cout % 64 != 0) return 1;
     // the tiled kernels keep the in-image taps of a pixel in a 32-bit mask and shift it by up to kh*kw + 2 (the
     // past-the-end LDS-DMA steps): larger windows (not reachable today, qnn_prepack_weights stops at 3x3) fall back
@@ -925,7 +936,7 @@ int qnn_try_launch_mfma(const ConvGeom& g, const EpiArgs& e, int x_store, const 
     const bool areg = areg_env == 0 ? false : areg_env == 1 ? areg_fit : (areg_fit && g.cout == 64 && !tile_env && wres_env < 0);
     if (e.res && !(areg && g.pool == 1)) return 1;          // the other MFMA kernels have no residual epilogue
     // pooled int4 layers whose pooled map tiles into 8 x 2 / 4 x 4 rectangles: receptive field staged once through LDS
-    // (k_conv_mfma_halo, qnn_mfma_areg.hip; qnn_set_option("halo", 0) keeps them on the per-tap kernel below)
+    // (k_conv_mfma_halo, qnn_mfma_areg.hip; QNN_EPI_NO_HALO keeps them on the per-tap kernel below)
     if (areg && x_store == QNN_STORE_I4 && !(e.flags & QNN_EPI_NO_HALO) &&
         qnn_launch_halo(mg, e2, x, w->d_mfma, y, s) == 0) {
         snprintf(name, name_len, "mfma_i4_halo64x64");

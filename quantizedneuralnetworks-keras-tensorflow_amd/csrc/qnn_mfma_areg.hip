@@ -1,5 +1,5 @@
 // Persistent short-K int8 MFMA kernels: filter slice resident in LDS (k_conv_mfma_wres) and activations
-// loaded straight into operand registers (k_conv_mfma_areg).  Dispatch: qnn_try_launch_mfma (qnn_mfma.hip).
+// loaded straight into operand registers (k_conv_mfma_areg).  Dispatch: qnn_route_gemm (qnn_mfma.hip).
 #include "qnn_mfma_common.h"
 #include "qnn_fold.h"
 

@@ -1,5 +1,5 @@
 // 3x3 int4 layers with 16 / 32 input channels on v_mfma_i32_16x16x64_i8, both operands in registers.
-// Dispatch: qnn_try_launch_mfma (qnn_mfma.hip).
+// Dispatch: qnn_route_strip (qnn_mfma.hip).
 #include "qnn_mfma_common.h"
 
 namespace {

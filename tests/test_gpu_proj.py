@@ -8,6 +8,8 @@ tests run that block end as ONE launch (k_conv_strip<.., RES = 3>) against
   * the oracle's float32 restatement of the reference's operations;
 and whole CIFAR ResNets through engine.ResidualFusedModel with and without the fused form.
 """
+import ctypes
+
 import numpy as np
 import pytest
 import torch
@@ -19,6 +21,7 @@ from test_gpu_fold import _layer, _packed_codes
 
 pytestmark = pytest.mark.gpu
 F32 = np.float32
+QNN_EINVAL = -1          # include/qnn_abi.h
 
 
 def _proj_layer(rng, cin0, cout, bias):
@@ -95,6 +98,39 @@ def test_projection_is_refused_where_no_kernel_computes_it():
     y, _, _ = _abi.conv2d(w, xp, _abi.STORE_I4, 4, 1, 8, 16, inv, shift, _abi.FN_QUANTIZED_TANH, 4, 1, _abi.STORE_I4,
                           post_scale=0.5, proj=(pw, x0p, 16, 32, 4))
     assert _abi.last_kernel() == "strip_i4_c32_proj"
+    # a 64-filter projection beside a layer whose kernel has no projection: the float-input first layer, the fused
+    # binarize + XNOR kernel of the float32 entry, the fused conv + classifier launch (pooled: invalid with a projection)
+    x0, x0p = _packed_codes(rng, 2, 16, 32, 32)
+    proj = (engine._prepack(_proj_layer(rng, 32, 64, False), _abi.STORE_I4, torch.device("cuda"), stride=2, same_pad=True),
+            x0p, 16, 32, 4)
+    first = {"op": "conv", "kind": "quantized", "nb": 4, "kernel": rng.uniform(-1, 1, (3, 3, 3, 64)).astype(F32),
+             "bias": None, "strides": (1, 1), "padding": "same"}
+    wf = engine._prepack(first, _abi.STORE_F32, torch.device("cuda"))
+    img = dev((rng.integers(0, 256, (2, 8, 16, 3)).astype(F32) / F32(255)).astype(F32))
+    with pytest.raises(_abi.QnnUnsupported):
+        _abi.conv2d(wf, img, _abi.STORE_F32, 0, 2, 8, 16, proj=proj)
+    lib = _abi.load()
+    binop = {"op": "conv", "kind": "binary", "kernel": rng.uniform(-1, 1, (3, 3, 64, 64)).astype(F32), "bias": None,
+             "strides": (1, 1), "padding": "same"}
+    wb = engine._prepack(binop, _abi.STORE_BIN, torch.device("cuda"))
+    xf = dev(rng.standard_normal((2, 8, 16, 64)).astype(F32))
+    y = torch.empty((2, 8, 16, 64), dtype=torch.float32, device="cuda")
+    ws = torch.empty(lib.qnn_conv2d_workspace_bytes(wb.handle, 2, 8, 16) // 4, dtype=torch.int32, device="cuda")
+    epi = _abi.make_epilogue(None, None, _abi.FN_NONE, 0, 1, _abi.STORE_F32, proj=proj)
+    assert lib.qnn_conv2d_forward_f32in(wb.handle, _abi.ptr(xf), _abi.FN_BINARY_TANH, 1, 2, 8, 16, ctypes.byref(epi),
+                                        _abi.ptr(y), _abi.ptr(ws), ws.numel() * 4, _abi.stream_ptr()) == _abi.QNN_EUNSUPPORTED
+    op, bn = _layer(rng, 64, 64, 3, False)
+    wc = engine._prepack(op, _abi.STORE_I4, torch.device("cuda"), stride=1, same_pad=True)
+    i, s = engine.bn_constants(bn)
+    inv, shift = dev(i), dev(s)
+    dense = {"op": "dense", "kind": "quantized", "nb": 4, "kernel": rng.uniform(-1, 1, (1024, 10)).astype(F32), "bias": None}
+    wd = engine._prepack(dense, _abi.STORE_I4, torch.device("cuda"))
+    _, xp = _packed_codes(rng, 2, 8, 8, 64)
+    logits = torch.empty((2, 10), dtype=torch.float32, device="cuda")
+    ec = _abi.make_epilogue(inv, shift, _abi.FN_QUANTIZED_TANH, 4, 2, _abi.STORE_I4, proj=proj)
+    ed = _abi.make_epilogue(None, None, _abi.FN_NONE, 0, 1, _abi.STORE_F32)
+    assert lib.qnn_conv2d_dense_forward(wc.handle, wd.handle, _abi.ptr(xp), _abi.STORE_I4, 4, 2, 8, 8, ctypes.byref(ec),
+                                        ctypes.byref(ed), _abi.ptr(logits), _abi.stream_ptr()) == QNN_EINVAL
 
 
 @pytest.mark.parametrize("nres", [1, 2])
