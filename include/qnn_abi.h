@@ -189,6 +189,8 @@ typedef struct qnn_epilogue {
  *   QNN_EPI_NO_HALO      pooled int4 layers with 64 input channels: per-tap operand fetch (k_conv_mfma_areg) instead of
  *                        the receptive field staged once through LDS (k_conv_mfma_halo)
  *   QNN_EPI_NO_LDS16     16 -> 16 channel layers with a fold: k_conv_strip instead of the LDS-staged k_conv_strip16_lds
+ *   QNN_EPI_NO_FP6       folded pooled int4 layers: k_conv_mfma_halo on the int8 matrix pipe instead of its FP6 (e2m3)
+ *                        form
  * The restricted-domain first-layer kernels are selected by the TYPED input stores QNN_STORE_F32_IMAGE /
  * QNN_STORE_F32_UNIT of the call (above), never by a switch.
  */
@@ -196,6 +198,7 @@ typedef struct qnn_epilogue {
 #define QNN_EPI_NO_STRIP64  2u
 #define QNN_EPI_NO_HALO     4u
 #define QNN_EPI_NO_LDS16    8u
+#define QNN_EPI_NO_FP6      16u
 
 /* ---- library ------------------------------------------------------------ */
 int         qnn_version(void);

@@ -66,6 +66,8 @@ struct qnn_weights {
     uint32_t* h_flag;     // domain flag (pinned, device-visible host word; qnn_weights_check) or nullptr
     uint32_t* d_flag;     // the same word through the device's address space
     float* d_f32act;      // float32-activation kernel (qnn_f32act.hip): filters k-step major [cout/16][K/4][64 lanes], or nullptr
+    uint8_t* d_fp6;       // I4 3x3, cin 64: the FP6 (e2m3) filter image of k_conv_mfma_halo [cout][9][48 B], or nullptr
+    int32_t* d_fp6_wsum;  // [cout] sum of the channel's 576 weight codes (inside the d_fp6 allocation)
 };
 
 struct ConvGeom;

@@ -1558,6 +1558,7 @@ extern "C" int qnn_free_weights(qnn_weights_t* w) {
     if (w->d_bias) (void)hipFree(w->d_bias);
     if (w->d_corr) (void)hipFree(w->d_corr);
     if (w->d_mfma_own) (void)hipFree(w->d_mfma_own);
+    if (w->d_fp6) (void)hipFree(w->d_fp6);
     if (w->d_aux) (void)hipFree(w->d_aux);
     if (w->h_flag) (void)hipHostFree(w->h_flag);
     if (w->d_head) (void)hipFree(w->d_head);
@@ -1674,7 +1675,7 @@ extern "C" int qnn_conv2d_dense_forward(const qnn_weights_t* wc, const qnn_weigh
     mg.x_bytes = (uint32_t)xb; mg.w_bytes = (uint32_t)wb; mg.ablate = 0;
     e.scale = e.scale * (1.0f / 256.0f);                    // both conv operands carry *16 (as qnn_route_gemm)
     const char* kname = "";
-    if (qnn_launch_areg_head(mg, e, x, wc->d_mfma, wd, ed, y, (hipStream_t)stream, &kname) != 0) {
+    if (qnn_launch_areg_head(mg, e, x, wc->d_mfma, qnn_halo_fp6(wc, e), wd, ed, y, (hipStream_t)stream, &kname) != 0) {
         qnn_set_error("qnn_conv2d_dense_forward: no fused kernel for this geometry");
         return QNN_EUNSUPPORTED;
     }

@@ -759,11 +759,42 @@ __global__ __launch_bounds__(256) void k_expand_i4_weights(const uint32_t* __res
     }
 }
 
+// FP6 (e2m3) filter image of k_conv_mfma_halo's FP6 form: one thread per (filter, tap, channel half) builds the six
+// dwords a B-operand lane supplies -- field e = 6-bit code of the channel qnn_fp6_channel(e) of that half, w / 8 in
+// sign-magnitude (|w| <= 8 is exact) -- stored as the kernel's LDS image wants them: [filter][tap][dwords 0-3 of half 0,
+// dwords 0-3 of half 1, dwords 4-5 of half 0, dwords 4-5 of half 1]; then the per-filter sum of the 576 codes
+__global__ __launch_bounds__(256) void k_fp6_weights(const uint32_t* __restrict__ packed, uint32_t* __restrict__ img,
+                                                     int32_t* __restrict__ wsum, int cout) {
+    const int i = blockIdx.x * 256 + threadIdx.x;          // (c * 9 + tap) * 2 + h
+    if (i >= cout * 18) return;
+    const int h = i & 1, ct = i >> 1;
+    const uint32_t* p = packed + ct * 8;                   // 64 codes of (filter, tap): 8 words
+    uint32_t d[6] = {0, 0, 0, 0, 0, 0};
+    for (int e = 0; e < 32; ++e) {
+        const int ch = 32 * h + qnn_fp6_channel(e);
+        const int w = ((int)(p[ch >> 3] << (28 - 4 * (ch & 7)))) >> 28;
+        const uint32_t f = w < 0 ? 0x20u | (uint32_t)(-w) : (uint32_t)w;
+        d[(6 * e) >> 5] |= f << ((6 * e) & 31);
+        if (((6 * e) & 31) > 26) d[((6 * e) >> 5) + 1] |= f >> (32 - ((6 * e) & 31));
+    }
+    uint32_t* o = img + ct * 12;
+    for (int j = 0; j < 4; ++j) o[4 * h + j] = d[j];
+    o[8 + 2 * h] = d[4];
+    o[9 + 2 * h] = d[5];
+    if (h == 0 && ct % 9 == 0) {
+        int sum = 0;
+        for (int k = 0; k < 9 * 64; ++k) sum += ((int)(p[k >> 3] << (28 - 4 * (k & 7)))) >> 28;
+        wsum[ct / 9] = sum;
+    }
+}
+
 }  // namespace
 
 // Build the int8 weight image the MFMA kernel reads (called from qnn_prepack_weights).
 int qnn_mfma_prepare_weights(qnn_weights* w, hipStream_t s) {
     w->d_mfma = nullptr;
+    w->d_fp6 = nullptr;
+    w->d_fp6_wsum = nullptr;
     const bool small = w->store == QNN_STORE_I4 && (w->cin == 16 || w->cin == 32) && (w->cout % 16) == 0 &&
                        w->kh == 3 && w->kw == 3;
     // the 1x1 strides-2 projection of a ResNet stage (models/resnet.py:117-124): read by the strip kernel of the block's
@@ -785,6 +816,13 @@ int qnn_mfma_prepare_weights(qnn_weights* w, hipStream_t s) {
                        (uint32_t*)w->d_mfma_own, words);
     w->d_mfma = (uint8_t*)w->d_mfma_own;
     QNN_HIP(hipGetLastError());
+    if (w->kh == 3 && w->kw == 3 && w->cin == 64 && w->cout % 64 == 0) {
+        QNN_HIP(hipMalloc((void**)&w->d_fp6, (size_t)w->cout * (9 * 48 + 4)));
+        w->d_fp6_wsum = (int32_t*)(w->d_fp6 + (size_t)w->cout * 9 * 48);
+        hipLaunchKernelGGL(k_fp6_weights, dim3((w->cout * 18 + 255) / 256), dim3(256), 0, s, w->d_packed,
+                           (uint32_t*)w->d_fp6, w->d_fp6_wsum, w->cout);
+        QNN_HIP(hipGetLastError());
+    }
     return QNN_OK;
 }
 
@@ -938,7 +976,7 @@ int qnn_route_gemm(const ConvCall& c, char* name, size_t name_len) {
     // pooled int4 layers whose pooled map tiles into 8 x 2 / 4 x 4 rectangles: receptive field staged once through LDS
     // (k_conv_mfma_halo, qnn_mfma_areg.hip; QNN_EPI_NO_HALO keeps them on the per-tap kernel below)
     if (areg && x_store == QNN_STORE_I4 && !(e.flags & QNN_EPI_NO_HALO) &&
-        qnn_launch_halo(mg, e2, x, w->d_mfma, y, s) == 0) {
+        qnn_launch_halo(mg, e2, x, w->d_mfma, qnn_halo_fp6(w, e), y, s) == 0) {
         snprintf(name, name_len, "mfma_i4_halo64x64");
         return 0;
     }

@@ -780,17 +780,36 @@ __global__ __launch_bounds__(256, (OUT == QNN_STORE_F32 ? 2 : 3)) void k_conv_mf
 // FOLD (round 4): the epilogue as qnn_fold.h's "bits" form -- the accumulators start from the channel's offset (which carries
 // the float's bit pattern), the 2x2 window is pooled on the raw integers as before, and a pooled value costs one v_fma_f32 +
 // half a v_cvt_pknorm_i16_f32 + half a packing instruction instead of cvt, add, mul, add, add, v_med3 and a shift-add.
-template <int TWP, int NW, bool HEAD, bool FOLD = false>
+// FP6: the same tiling on v_mfma_scale_f32_32x32x64_f8f6f4 with e2m3 operands (both E8M0 scales 2^3), which takes the
+// 64 channels of a tap in ONE instruction at the cycles of the int8 one (9 x 4 MFMAs per tile instead of 18 x 4).  An
+// activation code c is staged as u = c + 8 in [0, 15] (the nibble XOR 8; a padding zero becomes u = 8), whose zero-extended
+// 6-bit pattern is the e2m3 code of u / 8; a weight w in [-8, 7] is the sign-magnitude code of w / 8.  Every product is
+// the integer u w, every partial sum stays below 2^17 in magnitude, so the float32 accumulators hold the exact integer
+// S + 8 sum(w) (S = the int8 kernel's sum of codes); the pooled value becomes 256 S (+ the fold's offset) -- the int8
+// kernel's accumulator -- in one conversion and one shift-add, after which the epilogue is the int8 one, bit for bit.
+// Region: plane A = dwords 0-3 of a pixel's two 32-channel halves (the int8 plane's geometry and swizzle), plane B =
+// their dwords 4-5 ([row][pixel][2 eight-byte slots], slot = lane half XOR (row & 1): a ds_read_b64 group of 32 lanes
+// covers 16 pixels on two rows of different parity (TWP 8) or 4 x 8 pixels on rows whose 16-byte columns pair up with
+// the opposite parity (TWP 4, pitch 192 B), conflict-free).  Filters: plane A [tap][filter][2 x 16 B, half XOR bit 3 of
+// the filter], plane B [tap][filter][2 x 8 B, half XOR bit 4], again one bank per lane of a read group.
+// Only the folded layers without the classifier take it (B0 of the CIFAR VGG: 30.0 -> 25.6 us at batch 4096).  The
+// float-chain epilogue (binary networks) needs more registers than the two waves per SIMD leave and spilled (the bnn
+// step went from 66.6 to 83.8 us); with the classifier (C0) the form measured 11.5 against 11.0 us.
+template <int TWP, int NW, bool HEAD, bool FOLD = false, bool FP6 = false>
 __global__ __launch_bounds__(NW * 64, 1) void k_conv_mfma_halo(MfmaGeom mg, EpiArgs e, const uint8_t* __restrict__ x,
                                                                const uint8_t* __restrict__ wq8, void* __restrict__ y,
                                                                int ntiles, FastDiv fd_tpi, int txn, FastDiv fd_txn,
-                                                               uint32_t img_bytes, HeadArgs hd) {
+                                                               uint32_t img_bytes, HeadArgs hd,
+                                                               const int32_t* __restrict__ wsum) {
     constexpr int THP = 16 / TWP;
     constexpr int RW = 2 * TWP + 2, RH = 2 * THP + 2;     // region, pixels
     constexpr int NCH = 2 * RW * RH;                       // 16-byte chunks of packed input (32 B per pixel)
     constexpr int RWP = (RW + 3) & ~3;
-    constexpr int PITCH = RWP * 32, PLANE = RH * PITCH, REGION = 2 * PLANE;
-    constexpr int B_STEP = 64 * 64, FILT = 9 * B_STEP;
+    constexpr int PITCH = RWP * 32, PLANE = RH * PITCH;
+    constexpr int PITCHB = RWP * 16, REGION = FP6 ? PLANE + RH * PITCHB : 2 * PLANE;
+    constexpr int B_STEP = 64 * 64, FILT = FP6 ? 9 * 3072 : 9 * B_STEP;
+    constexpr int WB6 = 9 * 2048;                          // FP6: filter plane B
+    static_assert(!FP6 || (FOLD && !HEAD), "the FP6 form serves the folded layers without the classifier");
     constexpr int HTAB = FILT + NW * REGION;
     static_assert(NCH <= 256, "four load rounds per lane");
     const ConvGeom& g = mg.g;
@@ -801,10 +820,21 @@ __global__ __launch_bounds__(NW * 64, 1) void k_conv_mfma_halo(MfmaGeom mg, EpiA
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int nbase = blockIdx.y * 64;
     const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<uint8_t*>(wq8), 0, (int)mg.w_bytes, 0x00020000);
+        const_cast<uint8_t*>(wq8), 0, FP6 ? g.cout * 9 * 48 : (int)mg.w_bytes, 0x00020000);
 
     // ---- the slice's filters -> LDS (first four waves; the areg kernel's image and swizzle) ----
-    if (tid < 256) {
+    if constexpr (FP6) {                               // [filter][tap][3 x 16 B] (k_fp6_weights) -> the two planes
+        for (int i = tid; i < 64 * 27; i += NW * 64) {
+            const int col = i / 27, r = i - col * 27, tap = r / 3, part = r - tap * 3;
+            uint4 v = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, ((nbase + col) * 9 + tap) * 48 + part * 16, 0, 0));
+            if (part < 2) {
+                *reinterpret_cast<uint4*>(smem + tap * 2048 + col * 32 + ((part ^ ((col >> 3) & 1)) << 4)) = v;
+            } else {
+                if ((col >> 4) & 1) v = make_uint4(v.z, v.w, v.x, v.y);
+                *reinterpret_cast<uint4*>(smem + WB6 + tap * 1024 + col * 16) = v;
+            }
+        }
+    } else if (tid < 256) {
         const int srow = tid >> 2, sch = tid & 3;
         const int wv = (nbase + srow) * (9 * 64) + sch * 16;
         uint4 wreg[9];
@@ -838,6 +868,11 @@ __global__ __launch_bounds__(NW * 64, 1) void k_conv_mfma_halo(MfmaGeom mg, EpiA
             fda[b] = e.fold_a[c]; fdc[b] = e.fold_c[c]; fdb[b] = e.fold_b[c];
         }
     }
+    // FP6: the accumulators hold S + 8 sum(w); 256 S + offset = 256 * acc + (offset - 2048 sum(w))
+    if constexpr (FP6) {
+#pragma unroll
+        for (int b = 0; b < 2; ++b) fdb[b] = (int)((uint32_t)fdb[b] - 2048u * (uint32_t)wsum[nbase + b * 32 + li]);
+    }
     int hu = 0;
     float hbias = 0.0f, hinv = 1.0f, hshift = 0.0f;
     if constexpr (HEAD) {
@@ -856,7 +891,7 @@ __global__ __launch_bounds__(NW * 64, 1) void k_conv_mfma_halo(MfmaGeom mg, EpiA
 
     // ---- staging lanes: chunk j = lane + 64 i is half (j & 1) of region pixel j >> 1 ----
     const int regbase = FILT + wave * REGION;
-    int rel[4], wr_addr[4];
+    int rel[4], wr_addr[4], wrb_addr[4];
     unsigned long long edgeL[4], edgeR[4];
     bool wr_ok[4];
 #pragma unroll
@@ -867,21 +902,25 @@ __global__ __launch_bounds__(NW * 64, 1) void k_conv_mfma_halo(MfmaGeom mg, EpiA
         wr_ok[i] = j < NCH;
         rel[i] = wr_ok[i] ? (ry * g.W + rx) * 32 + half * 16 : (int)0x80000000;
         wr_addr[i] = regbase + ry * PITCH + rx * 32 + ((half ^ (ry & 1)) << 4);
+        wrb_addr[i] = regbase + PLANE + ry * PITCHB + rx * 16 + ((half ^ (ry & 1)) << 3);
         edgeL[i] = __ballot(rx == 0);
         edgeR[i] = __ballot(rx == RW - 1);
     }
     // ---- A fragments: rows mt * 32 + li = 4 * (pooled pixel) + (position in its 2x2 window) ----
-    int a_even[2], a_odd[2];
+    int a_even[2], a_odd[2], ab_even[2], ab_odd[2];
 #pragma unroll
     for (int mt = 0; mt < 2; ++mt) {
         const int q = 8 * mt + (li >> 2), sub = li & 3;
         const int ry0 = 2 * (q / TWP) + (sub >> 1), rx0 = 2 * (q % TWP) + (sub & 1);
         a_even[mt] = regbase + ry0 * PITCH + rx0 * 32 + ((lh ^ (ry0 & 1)) << 4);
         a_odd[mt] = a_even[mt] ^ 16;
+        ab_even[mt] = regbase + PLANE + ry0 * PITCHB + rx0 * 16 + ((lh ^ (ry0 & 1)) << 3);
+        ab_odd[mt] = ab_even[mt] ^ 8;
     }
     int fb_addr[2];
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk) fb_addr[kk] = li * 64 + (((lh * 2 + kk) ^ ((li >> 2) & 3)) << 4);
+    const int fb6a = li * 32 + ((lh ^ ((li >> 3) & 1)) << 4), fb6b = WB6 + li * 16 + ((lh ^ ((li >> 4) & 1)) << 3);
 
     const int t_stride = gridDim.x * NW;
     int t = blockIdx.x * NW + wave;
@@ -910,6 +949,28 @@ __global__ __launch_bounds__(NW * 64, 1) void k_conv_mfma_halo(MfmaGeom mg, EpiA
         }
     };
     auto stage = [&]() {
+        if constexpr (FP6) {
+            // 32 codes -> 32 six-bit fields (qnn_fp6_channel): XOR 8, then per pair of words one rotate each and
+            // two AND(-OR)s per output word; 24 bytes per chunk
+            auto grp = [](uint32_t x0, uint32_t y0, uint32_t& d0, uint32_t& d1, uint32_t& d2) {
+                const uint32_t xr = __builtin_amdgcn_alignbit(x0, x0, 30), yr = __builtin_amdgcn_alignbit(y0, y0, 30);
+                d0 = (x0 & 0x0F00F00Fu) | (xr & 0xC03C03C0u);
+                d1 = (xr & 0x03C03C03u) | (y0 & 0xF00F00F0u);
+                d2 = (y0 & 0x00F00F00u) | (yr & 0x3C03C03Cu);
+            };
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const uint4 q = L[i];
+                uint32_t d[6];
+                grp(q.x ^ 0x88888888u, q.y ^ 0x88888888u, d[0], d[1], d[2]);
+                grp(q.z ^ 0x88888888u, q.w ^ 0x88888888u, d[3], d[4], d[5]);
+                if (i < 3 || wr_ok[i]) {
+                    *reinterpret_cast<uint4*>(smem + wr_addr[i]) = make_uint4(d[0], d[1], d[2], d[3]);
+                    *reinterpret_cast<uint2*>(smem + wrb_addr[i]) = make_uint2(d[4], d[5]);
+                }
+            }
+            return;
+        }
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const uint4 q = L[i];
@@ -923,6 +984,7 @@ __global__ __launch_bounds__(NW * 64, 1) void k_conv_mfma_halo(MfmaGeom mg, EpiA
     };
 
     v16i acc[2][2];
+    v16f acc6[2][2];
     auto bn = [&](int v, const FoldEpi& f) {
         return __fadd_rn(__fmul_rn(__fadd_rn((float)v, f.nb), f.ninv), f.nshift);
     };
@@ -941,6 +1003,18 @@ __global__ __launch_bounds__(NW * 64, 1) void k_conv_mfma_halo(MfmaGeom mg, EpiA
             for (int a = 0; a < 2; ++a)
 #pragma unroll
                 for (int g4 = 0; g4 < 4; ++g4) {
+                    if constexpr (FP6) {                 // exact integers: the float order is the integer order
+                        const float f0 = acc6[a][b][4 * g4], f1 = acc6[a][b][4 * g4 + 1];
+                        const float f2 = acc6[a][b][4 * g4 + 2], f3 = acc6[a][b][4 * g4 + 3];
+                        float pf = fmaxf(fmaxf(f0, f1), fmaxf(f2, f3));
+                        if (!all_pos) {
+                            const float mn = fminf(fminf(f0, f1), fminf(f2, f3));
+                            pf = ke[b].neg ? mn : pf;
+                        }
+                        // 256 S + the fold's offset: the int8 kernel's pooled accumulator
+                        pv[a * 4 + g4] = (int)(((uint32_t)(int)pf << 8) + (uint32_t)fdb[b]);
+                        continue;
+                    }
                     const int i0 = acc[a][b][4 * g4], i1 = acc[a][b][4 * g4 + 1];
                     const int i2 = acc[a][b][4 * g4 + 2], i3 = acc[a][b][4 * g4 + 3];
                     const int mx = max(max(i0, i1), max(i2, i3));
@@ -990,6 +1064,45 @@ __global__ __launch_bounds__(NW * 64, 1) void k_conv_mfma_halo(MfmaGeom mg, EpiA
         const int image = n_next;
         stage();                                       // this tile's region (waits for its loads)
         fetch(t + t_stride);                           // the next tile's loads fly under this tile's MFMAs
+        if constexpr (FP6) {
+            // 9 K-steps (one per tap, all 64 channels); fragments of step s + 1 requested before the MFMAs of step s
+            v8i fa[2][2], fb[2][2];
+            auto frags = [&](int tap, v8i (&A)[2], v8i (&B)[2]) {
+                const int dy = tap / 3, dx = tap % 3;
+#pragma unroll
+                for (int mt = 0; mt < 2; ++mt) {
+                    const v4i lo = *reinterpret_cast<const v4i*>(smem + (dy == 1 ? a_odd[mt] : a_even[mt]) + dy * PITCH + dx * 32);
+                    const v2i hi = *reinterpret_cast<const v2i*>(smem + (dy == 1 ? ab_odd[mt] : ab_even[mt]) + dy * PITCHB + dx * 16);
+                    A[mt] = v8i{lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, 0, 0};
+                }
+#pragma unroll
+                for (int b = 0; b < 2; ++b) {
+                    const v4i lo = *reinterpret_cast<const v4i*>(smem + fb6a + tap * 2048 + b * 1024);
+                    const v2i hi = *reinterpret_cast<const v2i*>(smem + fb6b + tap * 1024 + b * 512);
+                    B[b] = v8i{lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, 0, 0};
+                }
+            };
+            frags(0, fa[0], fb[0]);
+#pragma unroll
+            for (int st = 0; st < 9; ++st) {
+                if (st + 1 < 9) frags(st + 1, fa[(st + 1) & 1], fb[(st + 1) & 1]);
+                __builtin_amdgcn_sched_barrier(0);
+                __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+                for (int a = 0; a < 2; ++a)
+#pragma unroll
+                    for (int b = 0; b < 2; ++b) {
+                        const v16f c0 = {};
+                        // formats 2 / 2 = e2m3 x e2m3, E8M0 scales 130 = 2^3 on both operands
+                        acc6[a][b] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(fa[st & 1][a], fb[st & 1][b],
+                                                                                     st == 0 ? c0 : acc6[a][b], 2, 2, 0, 130, 0, 130);
+                    }
+                __builtin_amdgcn_s_setprio(0);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            epilogue(pq0, image);
+            continue;
+        }
         // 18 K-steps (tap, kk); the fragments of step s + 1 are requested before the MFMAs of step s are issued (two register
         // sets), so a step's LDS latency lies under the previous step's 128 matrix-pipe cycles
         v4i fa[2][2], fb[2][2];
@@ -1029,37 +1142,43 @@ __global__ __launch_bounds__(NW * 64, 1) void k_conv_mfma_halo(MfmaGeom mg, EpiA
     }
 }
 
-template <int TWP, int NW, bool HEAD, bool FOLD = false>
-void launch_halo_one_f(const MfmaGeom& mg, const EpiArgs& e, const void* x, const uint8_t* w, void* y, const HeadArgs& hd,
-                       hipStream_t s) {
+template <int TWP, int NW, bool HEAD, bool FOLD, bool FP6>
+void launch_halo_one_f(const MfmaGeom& mg, const EpiArgs& e, const void* x, const uint8_t* w, const int32_t* wsum, void* y,
+                       const HeadArgs& hd, hipStream_t s) {
     const ConvGeom& g = mg.g;
     constexpr int THP = 16 / TWP;
     const int txn = g.Wp / TWP, tyn = g.Hp / THP;
     const int tpi = txn * tyn;
     const int ntiles = g.N * tpi;
     constexpr int RW = 2 * TWP + 2, RH = 2 * THP + 2, RWP = (RW + 3) & ~3;
-    const size_t lds = (size_t)9 * 4096 + (size_t)NW * (2 * RH * RWP * 32) + (HEAD ? 16 * 64 * 2 * 4 : 0);
+    const size_t lds = FP6 ? (size_t)9 * 3072 + (size_t)NW * (RH * RWP * 48) + (HEAD ? 16 * 64 * 2 * 4 : 0)
+                           : (size_t)9 * 4096 + (size_t)NW * (2 * RH * RWP * 32) + (HEAD ? 16 * 64 * 2 * 4 : 0);
     const int ny = g.cout / 64;
     int gx = (ntiles + NW - 1) / NW;
     const int cap = 256 / ny > 0 ? 256 / ny : 1;             // one resident workgroup per CU
     if (gx > cap) gx = cap;
     static const bool lds_ok = [] {
-        (void)hipFuncSetAttribute((const void*)k_conv_mfma_halo<TWP, NW, HEAD, FOLD>,
+        (void)hipFuncSetAttribute((const void*)k_conv_mfma_halo<TWP, NW, HEAD, FOLD, FP6>,
                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         return true;
     }();
     (void)lds_ok;
-    hipLaunchKernelGGL((k_conv_mfma_halo<TWP, NW, HEAD, FOLD>), dim3((unsigned)gx, (unsigned)ny), dim3(NW * 64), lds, s, mg, e,
-                       (const uint8_t*)x, w, y, ntiles, qnn_fastdiv((uint32_t)tpi), txn, qnn_fastdiv((uint32_t)txn),
-                       (uint32_t)(g.H * g.W * 32), hd);
+    hipLaunchKernelGGL((k_conv_mfma_halo<TWP, NW, HEAD, FOLD, FP6>), dim3((unsigned)gx, (unsigned)ny), dim3(NW * 64), lds, s, mg,
+                       e, (const uint8_t*)x, w, y, ntiles, qnn_fastdiv((uint32_t)tpi), txn, qnn_fastdiv((uint32_t)txn),
+                       (uint32_t)(g.H * g.W * 32), hd, wsum);
 }
 
-// a usable fold in the "bits" form (qnn_fold.h mode 2: e.fold_c set) takes the folded epilogue
+// a usable fold in the "bits" form (qnn_fold.h mode 2: e.fold_c set) takes the folded epilogue; with an FP6 filter image
+// and no classifier, on the FP6 form
 template <int TWP, int NW, bool HEAD>
-void launch_halo_one(const MfmaGeom& mg, const EpiArgs& e, const void* x, const uint8_t* w, void* y, const HeadArgs& hd,
-                     hipStream_t s) {
-    if (e.fold_a && e.fold_c && e.fn == QNN_FN_QUANTIZED_TANH) launch_halo_one_f<TWP, NW, HEAD, true>(mg, e, x, w, y, hd, s);
-    else launch_halo_one_f<TWP, NW, HEAD, false>(mg, e, x, w, y, hd, s);
+void launch_halo_one(const MfmaGeom& mg, const EpiArgs& e, const void* x, const uint8_t* w, HaloFp6 w6, void* y,
+                     const HeadArgs& hd, hipStream_t s) {
+    const bool fold = e.fold_a && e.fold_c && e.fn == QNN_FN_QUANTIZED_TANH;
+    if constexpr (!HEAD) {
+        if (fold && w6.w) return launch_halo_one_f<TWP, NW, HEAD, true, true>(mg, e, x, w6.w, w6.wsum, y, hd, s);
+    }
+    if (fold) launch_halo_one_f<TWP, NW, HEAD, true, false>(mg, e, x, w, nullptr, y, hd, s);
+    else launch_halo_one_f<TWP, NW, HEAD, false, false>(mg, e, x, w, nullptr, y, hd, s);
 }
 
 // 0 = launched.  The pooled map must tile into 8 x 2 or 4 x 4 rectangles; everything else stays on k_conv_mfma_areg.
@@ -1199,17 +1318,17 @@ static int halo_waves(const MfmaGeom& mg, int tw) {
     return ntiles >= 256 * 8 ? 8 : 4;
 }
 
-int qnn_launch_halo(const MfmaGeom& mg, const EpiArgs& e, const void* x, const uint8_t* w, void* y, hipStream_t s) {
+int qnn_launch_halo(const MfmaGeom& mg, const EpiArgs& e, const void* x, const uint8_t* w, HaloFp6 w6, void* y, hipStream_t s) {
     const int tw = halo_width(mg, e);
     if (tw == 0) return 1;
     const int nw = halo_waves(mg, tw);
     const HeadArgs none{};
     if (tw == 8) {
-        if (nw == 8) launch_halo_one<8, 8, false>(mg, e, x, w, y, none, s);
-        else launch_halo_one<8, 4, false>(mg, e, x, w, y, none, s);
+        if (nw == 8) launch_halo_one<8, 8, false>(mg, e, x, w, w6, y, none, s);
+        else launch_halo_one<8, 4, false>(mg, e, x, w, w6, y, none, s);
     } else {
-        if (nw == 8) launch_halo_one<4, 8, false>(mg, e, x, w, y, none, s);
-        else launch_halo_one<4, 4, false>(mg, e, x, w, y, none, s);
+        if (nw == 8) launch_halo_one<4, 8, false>(mg, e, x, w, w6, y, none, s);
+        else launch_halo_one<4, 4, false>(mg, e, x, w, w6, y, none, s);
     }
     return 0;
 }
@@ -1233,8 +1352,8 @@ int qnn_head_prepare(qnn_weights* w, hipStream_t s) {
 
 // 0 = launched.  Conv: int4 in, 3x3 stride 1 SAME, Cin 64 / 128, 64 filters, 2x2 pool, int4 codes out, 4 x 4 pooled map;
 // dense: the matching 1024 -> <= 16 head prepacked for int4.  `ed` is the dense layer's epilogue (float32 out, no fn).
-int qnn_launch_areg_head(const MfmaGeom& mg, const EpiArgs& e, const void* x, const uint8_t* w, const qnn_weights* wd,
-                         const EpiArgs& ed, float* y, hipStream_t s, const char** kname) {
+int qnn_launch_areg_head(const MfmaGeom& mg, const EpiArgs& e, const void* x, const uint8_t* w, HaloFp6 w6,
+                         const qnn_weights* wd, const EpiArgs& ed, float* y, hipStream_t s, const char** kname) {
     const ConvGeom& g = mg.g;
     if (g.kh != 3 || g.kw != 3 || g.stride != 1 || g.cout != 64 || g.pool != 2 || (mg.kc != 1 && mg.kc != 2)) return 1;
     if (g.Hp * g.Wp != 16 || e.out_store != QNN_STORE_I4 || e.res || !wd->d_head || wd->cin != 1024) return 1;
@@ -1242,8 +1361,8 @@ int qnn_launch_areg_head(const MfmaGeom& mg, const EpiArgs& e, const void* x, co
     hd.tab = wd->d_head; hd.bias = ed.bias; hd.bn_inv = ed.bn_inv; hd.bn_shift = ed.bn_shift;
     hd.scale = ed.scale; hd.units = wd->cout; hd.y = y;
     if (!(e.flags & QNN_EPI_NO_HALO) && halo_width(mg, e) == 4 && g.Wp == 4) {   // tile == image
-        if (halo_waves(mg, 4) == 8) launch_halo_one<4, 8, true>(mg, e, x, w, nullptr, hd, s);
-        else launch_halo_one<4, 4, true>(mg, e, x, w, nullptr, hd, s);
+        if (halo_waves(mg, 4) == 8) launch_halo_one<4, 8, true>(mg, e, x, w, w6, nullptr, hd, s);
+        else launch_halo_one<4, 4, true>(mg, e, x, w, w6, nullptr, hd, s);
         *kname = "mfma_i4_halo64x64+dense";
         return 0;
     }

@@ -26,6 +26,9 @@
 typedef int v4i __attribute__((ext_vector_type(4)));
 typedef float v2f __attribute__((ext_vector_type(2)));   // operand pair of the packed float32 VALU operations
 typedef int v16i __attribute__((ext_vector_type(16)));
+typedef int v2i __attribute__((ext_vector_type(2)));
+typedef int v8i __attribute__((ext_vector_type(8)));
+typedef float v16f __attribute__((ext_vector_type(16)));
 
 // (outside the anonymous namespace: it appears in the signatures of the cross-TU launchers below)
 struct MfmaGeom {
@@ -248,9 +251,32 @@ int qnn_launch_areg(int x_store, int kc, const MfmaGeom& mg, const EpiArgs& e, c
                     void* y, hipStream_t s);
 int qnn_launch_wres(int x_store, const MfmaGeom& mg, const EpiArgs& e, const void* x, const uint8_t* w,
                     void* y, hipStream_t s);
-int qnn_launch_halo(const MfmaGeom& mg, const EpiArgs& e, const void* x, const uint8_t* w, void* y, hipStream_t s);
-int qnn_launch_areg_head(const MfmaGeom& mg, const EpiArgs& e, const void* x, const uint8_t* w, const qnn_weights* wd,
-                         const EpiArgs& ed, float* y, hipStream_t s, const char** kname);
+// FP6 form of k_conv_mfma_halo: which channel of a 32-channel half a lane's operand field e (bits 6e .. 6e + 5 of its six
+// registers) carries.  The staging builds each 3-dword group of fields from two code words x, y (channels 16 p + 0..7,
+// 16 p + 8..15) as  (x & 0x0F00F00F) | (rotl(x, 2) & 0xC03C03C0),  (rotl(x, 2) & 0x03C03C03) | (y & 0xF00F00F0),
+// (y & 0x00F00F00) | (rotl(y, 2) & 0x3C03C03C): nibbles only move by 0 or 2 bits, and the nibble rotated across bit 31
+// becomes the field that straddles the first two registers.  The filter image follows the same order.
+__host__ __device__ constexpr int qnn_fp6_channel(int e) {
+    return 16 * (e >> 4) + (int)((0xEDBA8F5C29764310ull >> (4 * (e & 15))) & 15u);
+}
+
+// the FP6 filter image k_conv_mfma_halo runs on (null: the int8 form)
+struct HaloFp6 {
+    const uint8_t* w;
+    const int32_t* wsum;
+};
+inline HaloFp6 qnn_halo_fp6(const qnn_weights* w, const EpiArgs& e) {
+#ifdef QNN_HALO_NO_FP6
+    (void)w; (void)e;
+    return HaloFp6{nullptr, nullptr};
+#else
+    if (!w->d_fp6 || (e.flags & QNN_EPI_NO_FP6)) return HaloFp6{nullptr, nullptr};
+    return HaloFp6{w->d_fp6, w->d_fp6_wsum};
+#endif
+}
+int qnn_launch_halo(const MfmaGeom& mg, const EpiArgs& e, const void* x, const uint8_t* w, HaloFp6 w6, void* y, hipStream_t s);
+int qnn_launch_areg_head(const MfmaGeom& mg, const EpiArgs& e, const void* x, const uint8_t* w, HaloFp6 w6,
+                         const qnn_weights* wd, const EpiArgs& ed, float* y, hipStream_t s, const char** kname);
 int qnn_launch_small(int cin, const MfmaGeom& mg, const EpiArgs& e, const void* x, const uint8_t* w,
                      void* y, hipStream_t s);
 int qnn_launch_strip(int cin, const MfmaGeom& mg, const EpiArgs& e, const void* x, const uint8_t* w,
