@@ -469,6 +469,12 @@ __global__ __launch_bounds__(256, (NBLK == 1 ? 6 : 3)) void k_conv_first_u8_full
                     }
                     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4i, make_uint4(Pq[0], Pq[1], Pq[2], Pq[3])), yr,
                                                            ypos + (8 * t) * pixb, srow, 0);
+                    // A 16-byte store reads its data VGPRs a state after issue, and hipcc inserts no wait state here:
+                    // in the F32IN forms the very next instruction rewrote the first data register, and that dword of
+                    // some stores came out wrong, nondeterministically.  The fences keep the nop right behind the store.
+                    __builtin_amdgcn_sched_barrier(0);
+                    asm volatile("s_nop 1");
+                    __builtin_amdgcn_sched_barrier(0);
                 }
             } else if constexpr (OUT == QNN_STORE_I8) {
 #pragma unroll

@@ -334,24 +334,34 @@ class FusedModel:
         u8 = example.dtype == torch.uint8
         cur, bound = example, []
         nsteps = len(self.steps)
-        for si, st in enumerate(self.steps):
-            if si == nsteps - 2 and si >= 1:
-                y = self.run_head(cur, N, H, W)
-                if y is not None:            # conv group + classifier in one launch: the plan ends here
-                    c, d = self.steps[-2], self.steps[-1]
-                    bound.append(_abi.BoundHead(c["w"], d["w"], c["x_store"], c["x_bits"], N, H, W, c["inv"], c["shift"],
-                                                c["fn"], c["act_bits"], d["inv"], d["shift"], cur,
-                                                fold=self._first_fold(len(self.steps) - 2, c["x_store"])))
-                    cur = y
-                    break
-            out, H1, W1 = self.run_step(si, cur, N, H, W)
-            x_store = _abi.STORE_U8 if (u8 and si == 0) else self._x_store(si)
-            bound.append(_abi.BoundStep(st["kind"], st["w"], x_store, st["x_bits"], N, H, W, st["inv"], st["shift"],
-                                        st["fn"], st["act_bits"], st["pool"], st["out_store"],
-                                        None if si == 0 else cur, None if si == len(self.steps) - 1 else out,
-                                        trick=None if (u8 and si == 0) else st["trick"],
-                                        fold=self._first_fold(si, x_store) if st["kind"] == "conv" else None))
-            cur, H, W = out, H1, W1
+        # The binding pass runs the forward once on `example` only to create and bind the intermediates; its first
+        # layer writes a scratch domain-flag word ("auto").  `example` need not be image bytes / 255 (engine.Pipelined
+        # binds on the first batch of a new shape) and nothing reads this pass's flag: a raise left in the model's own
+        # word would send the next eager forward of an image batch to the exact kernel and make check_domain() raise.
+        # A scratch word rather than clearing the model's word afterwards: that would also erase a raise an earlier
+        # replay left there unread.
+        own_flag, self._flag = self._flag, torch.zeros(1, dtype=torch.int32, device=self.device)
+        try:
+            for si, st in enumerate(self.steps):
+                if si == nsteps - 2 and si >= 1:
+                    y = self.run_head(cur, N, H, W)
+                    if y is not None:            # conv group + classifier in one launch: the plan ends here
+                        c, d = self.steps[-2], self.steps[-1]
+                        bound.append(_abi.BoundHead(c["w"], d["w"], c["x_store"], c["x_bits"], N, H, W, c["inv"], c["shift"],
+                                                    c["fn"], c["act_bits"], d["inv"], d["shift"], cur,
+                                                    fold=self._first_fold(len(self.steps) - 2, c["x_store"])))
+                        cur = y
+                        break
+                out, H1, W1 = self.run_step(si, cur, N, H, W)
+                x_store = _abi.STORE_U8 if (u8 and si == 0) else self._x_store(si)
+                bound.append(_abi.BoundStep(st["kind"], st["w"], x_store, st["x_bits"], N, H, W, st["inv"], st["shift"],
+                                            st["fn"], st["act_bits"], st["pool"], st["out_store"],
+                                            None if si == 0 else cur, None if si == len(self.steps) - 1 else out,
+                                            trick=None if (u8 and si == 0) else st["trick"],
+                                            fold=self._first_fold(si, x_store) if st["kind"] == "conv" else None))
+                cur, H, W = out, H1, W1
+        finally:
+            self._flag = own_flag
         last = len(bound) - 1
         own = self._own_flag().data_ptr() if (self._auto_now() and not u8) else None
 

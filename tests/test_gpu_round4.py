@@ -86,6 +86,35 @@ def test_residual_engine_auto_first_layer():
     pipe.check_domain()
 
 
+@pytest.mark.parametrize("tail", [0, 5], ids=["no_tail", "tail"])
+@pytest.mark.parametrize("kind", ["fused", "residual"])
+def test_pipelined_first_batch_not_images_leaves_no_stale_flag(kind, tail):
+    """engine.Pipelined binds (FusedModel.bind) or captures (ResidualFusedModel) its lanes on the FIRST batch of a new
+    shape.  When that batch is not image bytes / 255, the binding pass must not leave the model's own "auto" flag word
+    raised: every row equals its own oracle, check_domain() passes, and the ragged image tail (eager) stays on the byte
+    kernel -- no recomputation on the exact kernel."""
+    if kind == "fused":
+        cf, spec = _cfg(2)
+        m, B = engine.FusedModel(spec), 16
+    else:
+        cf = nets.Config(network_type="full-qnn", wbits=4, abits=4, architecture="RESNET", nres=1, dim=32)
+        spec = nets.build_spec(cf, 3)[:-1]
+        m, B = engine.ResidualFusedModel(spec), 4
+    assert m.first_layer == "auto"
+    xf = np.random.default_rng(21).uniform(0, 1, (B, cf.dim, cf.dim, cf.channels)).astype(F32)
+    xu8 = nets.synthetic_images_u8(cf, 3 * B + tail, 22)
+    x = np.concatenate([xf, (xu8.astype(F32) / F32(255)).astype(F32)])
+    want = np.concatenate([O.run_spec(spec, xf, float_conv="device"), O.run_spec_u8(spec, xu8)])
+    pipe = engine.Pipelined(m, lanes=2, batch_size=B)
+    m.kernel_log = []
+    np.testing.assert_array_equal(host(pipe(dev(x))), want)
+    pipe.check_domain()
+    if tail:
+        log = m.kernel_log
+        last = len(log) - 1 - log[::-1].index("mfma_i8_first_img255")      # the tail's first layer
+        assert not any(k.startswith(("mfma_f32_first", "mfma_f32_stem")) for k in log[last:]), log[last:]
+
+
 @pytest.mark.parametrize("kind", ["fused", "residual"])
 def test_pipelined_ring_slots_hold_the_eager_logits(kind):
     """engine.Pipelined.lanes_for(x, slots=4, inputs=2): the rings bench.py hands to its collectives.  FusedModel: one
