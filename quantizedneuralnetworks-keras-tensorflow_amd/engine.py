@@ -1,20 +1,28 @@
-"""Whole-network runners over a net spec (nets.py).
+"""Whole-network runners over a net spec (nets.py): the only way from a spec to the HIP library.
 
-  FusedModel   the production pipeline ("M1" traffic model): every
-               conv -> BN -> activation clip -> max-pool group is ONE kernel launch
-               whose epilogue writes the next layer's input already packed at the
-               activation width; inter-layer tensors never exist in float32.
-               Chains only (VGG); everything else goes through GraphModel.
-  GraphModel   general interpreter (ResNet: adds, 0.5 scaling, avg-pool, softmax).
-               Low-bit contractions run on the HIP kernels with the activation clip
-               fused into their pack-on-load and BN fused into their epilogue; the
-               stock Keras layers around them are elementwise torch ops on the GPU.
-  LayerModel   the Keras-compatible layer objects called one by one (float32 NHWC
-               in, float32 NHWC out per layer: "M0" traffic model).
+  FusedModel          chains (VGG): every conv -> BN -> activation clip -> max-pool group is ONE kernel launch whose
+                      epilogue writes the next layer's input already packed at the activation width ("M1" traffic
+                      model); inter-layer tensors never exist in float32.  What nets.Model runs for a
+                      chain, and what bench.py times step by step (steps / run_step / bind).
+  ResidualFusedModel  every other topology (ResNet): the same fusion plus the residual merge
+                      conv -> BN -> add(shortcut) -> [x0.5] -> act in one launch, evaluated on demand from the output;
+                      what is not on the low-bit path (avg-pool, softmax, ...) runs as float32 torch ops.  What
+                      nets.Model runs for everything FusedModel refuses (NotFusable).
+  Pipelined           a fused engine's forward with several batches in flight: bound launch plans (FusedModel.bind) or
+                      hipGraphs of model(x) per lane.  What nets.Model.predict and bench.py's timed region run.
+  GraphModel          general interpreter, one launch per contraction with the activation clip fused into its
+                      pack-on-load and BN into its epilogue; the stock Keras layers around it are float32 torch ops.
+                      The plain counterpart the tests hold the fused engines against.
+  LayerModel          the Keras-compatible layer objects called one by one (float32 NHWC in, float32 NHWC out per
+                      layer: "M0" traffic model); nets.Model.conv_output reads intermediate tensors through it.
 
-All three produce logits identical to each other; tests compare them with the CPU
-oracle.  None of them has a CPU path.
+The three spec interpreters share one reading of the spec (_SpecGraph) and one set of float32 glue ops (_GLUE); the two
+fused engines share the "auto" first-layer protocol (_DomainFlag).  All engines produce identical logits; tests compare
+them with the CPU oracle.  None of them has a CPU path.
 """
+import contextlib
+import math
+
 import numpy as np
 import torch
 
@@ -103,8 +111,163 @@ def _prepack(op, store, device, stride=1, same_pad=True):
                         stride, same_pad, store)
 
 
+def _images(x, what):
+    """The images of a forward as the C ABI takes them: uint8 (the typed QNN_STORE_U8 entry) or float32, NHWC on the GPU."""
+    if isinstance(x, torch.Tensor) and x.dtype == torch.uint8:
+        return _abi.require_cuda_u8(x, what)
+    return _abi.require_cuda(x, what)
+
+
+class _SpecGraph:
+    """One reading of a net spec for the interpreters below: the name of every op's output, which op produces and which
+    ops consume each tensor, the BN constants on the device, and the weights, prepacked when first asked for."""
+
+    def __init__(self, spec, device):
+        self.spec, self.device = spec, torch.device(device)
+        self.names = [op.get("dst", "t%d" % i) for i, op in enumerate(spec)]
+        self.prod = {n: i for i, n in enumerate(self.names)}
+        # the tensors op i reads: add -> a, b; a named `src`; else the previous op's output; else the images
+        self.srcs = [[op["a"], op["b"]] if op["op"] == "add" else
+                     [op["src"] if "src" in op else self.names[i - 1] if i > 0 else "input"] for i, op in enumerate(spec)]
+        self.cons = {}
+        for i, ss in enumerate(self.srcs):
+            for s in ss:
+                self.cons.setdefault(s, []).append(i)
+        self.bn = {i: tuple(torch.as_tensor(c).to(self.device) for c in bn_constants(op))
+                   for i, op in enumerate(spec) if op["op"] == "bn"}
+        self.packed = {}                     # (op index, store) -> _abi.Weights
+
+    def weights(self, i, store):
+        if (i, store) not in self.packed:
+            op = self.spec[i]
+            self.packed[i, store] = _prepack(op, store, self.device, stride=tuple(op.get("strides", (1, 1)))[0],
+                                             same_pad=op.get("padding", "same") == "same")
+        return self.packed[i, store]
+
+
+# ---- the stock Keras layers around the contractions, on float32 tensors.  Every interpreter below calls these, so their
+# results cannot drift apart; oracle/qnn_oracle.py restates them independently.
+def _maxpool(t, op):
+    s = op.get("size", 2)
+    N, H, W, C = t.shape
+    return t[:, :H // s * s, :W // s * s, :].reshape(N, H // s, s, W // s, s, C).amax(dim=(2, 4))
+
+
+def _avgpool(t, op):
+    s = op.get("size", 8)
+    N, H, W, C = t.shape
+    win = t[:, :H // s * s, :W // s * s, :].reshape(N, H // s, s, W // s, s, C)
+    # window sums of grid values are exact in float64; one division in float32
+    return win.double().sum(dim=(2, 4)).float() / F32(s * s)
+
+
+def _zeropad(t, op):
+    p = op["pad"]
+    return torch.nn.functional.pad(t, (0, 0, p, p, p, p))
+
+
+def _flatten(t, op):
+    return t.reshape(t.shape[0], -1)
+
+
+def _scale(t, op):
+    return t * F32(op["value"])
+
+
+def _add(a, b):
+    return a + b
+
+
+def _bn_apply(t, inv, shift):
+    return t * inv + shift                   # two roundings, as tf.nn.batch_normalization
+
+
+def _act(t, op):
+    """An activation op: the clips of layers/*_ops.py (ternary_tanh thresholds at the mean of the whole batch tensor,
+    ternary_ops.py:23) and LeakyReLU."""
+    fn = op["fn"]
+    if fn == "binary_tanh":
+        return binary_ops.binary_tanh(t)
+    if fn == "quantized_tanh":
+        return quantized_ops.quantized_tanh(t, op["nb"])
+    if fn == "ternary_tanh":
+        return ternary_ops.ternary_tanh(t)
+    if fn == "leaky_relu":
+        return torch.where(t >= 0, t, t * F32(op.get("alpha", 0.3)))
+    raise ValueError(fn)
+
+
+_GLUE = {"maxpool": _maxpool, "avgpool": _avgpool, "zeropad": _zeropad, "flatten": _flatten, "scale": _scale, "act": _act,
+         "softmax": lambda t, op: _abi.softmax(t)}
+
+
+class _DomainFlag:
+    """The "auto" first layer of the two fused engines: float32 images run on the byte kernel, which raises a domain-flag
+    word (qnn_epilogue_t.domain_flag) when a value is not an image byte / 255; a flagged batch is recomputed on the exact
+    kernel.  An engine passes _own_flag() to its first layer where _auto_now(images) holds, gives `_forward(x)` (one
+    forward as `first_layer` and `_exact_now` say), `_check_restricted()` and the text `_UNRECOMPUTED`."""
+
+    _flag = None                             # the word the first layer writes: the model's own unless flag_word() says otherwise
+    _exact_now = False                       # the batch being recomputed takes the exact kernel
+
+    def _auto_now(self, x):
+        return self.first_layer == "auto" and not self._exact_now and x.dtype == torch.float32
+
+    def _own_flag(self):
+        if self._flag is None:
+            self._flag = torch.zeros(1, dtype=torch.int32, device=self.device)
+        return self._flag
+
+    @contextlib.contextmanager
+    def flag_word(self, word):
+        """Inside the block the first layer writes `word` (an int32 device tensor) instead of the model's own word, which
+        keeps what it holds: a raise an earlier replay left there unread, or none where the block's batch raises one."""
+        own, self._flag = self._flag, word
+        try:
+            yield word
+        finally:
+            self._flag = own
+
+    def take_flag(self):
+        """Synchronise, return True and clear if this model's own flag word is raised (an eager forward, a captured graph
+        or a bench replay met a batch that is not image bytes / 255)."""
+        if self._flag is None:
+            return False
+        raised = int(self._flag.item()) != 0
+        if raised:
+            self._flag.zero_()
+        return raised
+
+    def forward(self, x):
+        """x: float32 or uint8 NHWC CUDA tensor -> the network's output, float32."""
+        y = self._forward(x)
+        if self._auto_now(x) and not torch.cuda.is_current_stream_capturing() and self.take_flag():
+            y = self.forward_exact(x)        # the batch was not image bytes / 255
+        return y
+
+    def forward_exact(self, x, **kw):
+        """The forward with the exact float32 first layer, whatever `first_layer` says (what "auto" falls back to)."""
+        self._exact_now = True
+        try:
+            return self._forward(x, **kw)
+        finally:
+            self._exact_now = False
+
+    def check_domain(self):
+        """Synchronise the current stream and raise QnnError if a restricted-domain first layer ("fixed", "image") met
+        an input outside its domain since the last check (qnn_weights_check).  "auto": raises only for replays nobody
+        recomputed (hipGraph replays outside engine.Pipelined.forward).  A no-op for the exact and uint8 entries."""
+        if self.first_layer != "auto":
+            self._check_restricted()
+        elif self.take_flag():
+            raise _abi.QnnError(self._UNRECOMPUTED)
+
+    __call__ = forward
+    predict = forward
+
+
 # ---------------------------------------------------------------------------
-class FusedModel:
+class FusedModel(_DomainFlag):
     """Packed, fully fused pipeline for sequential specs (models/vgg.py topology).
 
     forward(x) takes the images either as uint8 NHWC, the dataset's own bytes (value = code / 255,
@@ -123,6 +286,8 @@ class FusedModel:
     # how float32 images are declared to the C ABI: a typed entry per call, no process-wide switch is touched
     FIRST_LAYER_STORE = {"exact": _abi.STORE_F32, "image": _abi.STORE_F32_IMAGE, "fixed": _abi.STORE_F32_UNIT,
                          "auto": _abi.STORE_F32_IMAGE}
+    _UNRECOMPUTED = ("FusedModel: a replayed batch was not image bytes / 255 and has not been recomputed on "
+                     "the exact first layer (run it through forward() / engine.Pipelined.forward())")
 
     def __init__(self, spec, device="cuda", first_layer="auto", trick=None):
         """trick: None = the reference's lr-multiplier identity trick is the identity ("exact" mode, the default), or
@@ -137,8 +302,6 @@ class FusedModel:
             first_layer = "exact"            # the faithful output-side trick lives in the VALU kernel family only
         self.first_layer = first_layer
         self.fold = True                     # folded epilogues where the library proves one (today: the image entry's first layer)
-        self._flag = None                    # "auto": this model's own domain-flag word (eager forwards, captured graphs)
-        self._exact_now = False              # "auto": the batch being recomputed takes the exact kernel
         self.device = torch.device(device)
         self.fuse_head = True                # conv group + Flatten + Dense in one launch where the library has the kernel
         self._head_no = {}                   # (H, W) of inputs the library has no fused head kernel for
@@ -281,7 +444,7 @@ class FusedModel:
             raise _abi.QnnError("FusedModel: trick=%r cannot be combined with uint8 images (the QNN_STORE_U8 entry has no "
                                 "output-side trick); pass float32 images" % (st["trick"],))
         x_store = _abi.STORE_U8 if u8 else self._x_store(si)
-        flag = self._own_flag() if (si == 0 and not u8 and self._auto_now()) else None
+        flag = self._own_flag() if (si == 0 and self._auto_now(cur)) else None
         return _abi.conv2d(st["w"], cur, x_store, st["x_bits"], N, H, W, st["inv"],
                            st["shift"], st["fn"], st["act_bits"], st["pool"], st["out_store"], out=out,
                            trick=st["trick"], domain_flag=flag, fold=self._first_fold(si, x_store))
@@ -308,14 +471,6 @@ class FusedModel:
             st[key] = _abi.Fold.try_prepare(st["w"], args[0], args[1], st["inv"], st["shift"], st["fn"], 4, st["out_store"])
         return st[key]
 
-    def _auto_now(self):
-        return self.first_layer == "auto" and not self._exact_now and self.steps[0]["x_store"] == _abi.STORE_F32
-
-    def _own_flag(self):
-        if self._flag is None:
-            self._flag = torch.zeros(1, dtype=torch.int32, device=self.device)
-        return self._flag
-
     def _x_store(self, si):
         """Input store of step si for float32 / packed inputs (the first step carries the declared image domain)."""
         st = self.steps[si]
@@ -340,8 +495,7 @@ class FusedModel:
         # word would send the next eager forward of an image batch to the exact kernel and make check_domain() raise.
         # A scratch word rather than clearing the model's word afterwards: that would also erase a raise an earlier
         # replay left there unread.
-        own_flag, self._flag = self._flag, torch.zeros(1, dtype=torch.int32, device=self.device)
-        try:
+        with self.flag_word(torch.zeros(1, dtype=torch.int32, device=self.device)):
             for si, st in enumerate(self.steps):
                 if si == nsteps - 2 and si >= 1:
                     y = self.run_head(cur, N, H, W)
@@ -360,10 +514,8 @@ class FusedModel:
                                             trick=None if (u8 and si == 0) else st["trick"],
                                             fold=self._first_fold(si, x_store) if st["kind"] == "conv" else None))
                 cur, H, W = out, H1, W1
-        finally:
-            self._flag = own_flag
         last = len(bound) - 1
-        own = self._own_flag().data_ptr() if (self._auto_now() and not u8) else None
+        own = self._own_flag().data_ptr() if self._auto_now(example) else None
 
         def plan(stream, x_ptr, y_ptr, flag_ptr=None):
             """flag_ptr ("auto" first layer): device address of THIS batch's domain-flag word (default: the model's)."""
@@ -395,72 +547,29 @@ class FusedModel:
                 cur = _abi.softmax(cur)
         return cur
 
-    def forward(self, x):
-        """x: float32 or uint8 NHWC CUDA tensor -> float32 (N, classes)."""
-        u8 = isinstance(x, torch.Tensor) and x.dtype == torch.uint8
-        x = _abi.require_cuda_u8(x, "FusedModel.forward") if u8 else _abi.require_cuda(x, "FusedModel.forward")
-        if u8 and (self.steps[0]["kind"] != "conv" or self.steps[0]["w"].wkind == _abi.W_FLOAT):
+    def _forward(self, x, out=None):
+        what = "FusedModel.forward_exact" if self._exact_now else "FusedModel.forward"
+        x = _abi.require_cuda(x, what) if self._exact_now else _images(x, what)
+        if x.dtype == torch.uint8 and (self.steps[0]["kind"] != "conv" or self.steps[0]["w"].wkind == _abi.W_FLOAT):
             raise _abi.QnnError("FusedModel.forward: uint8 images need a low-bit convolution as the first layer")
         N, H, W, _ = x.shape
-        y = self.forward_from(0, x, N, H, W)
-        if not u8 and self._auto_now() and not torch.cuda.is_current_stream_capturing():
-            # "auto": the batch ran on the byte kernel with this model's flag word; not image bytes / 255 -> the exact kernel
-            if int(self._own_flag().item()) != 0:
-                self._flag.zero_()
-                y = self.forward_exact(x)
-        return y
+        return self.forward_from(0, x, N, H, W, out=out)
 
-    def forward_exact(self, x, out=None):
-        """The forward with the exact float32 first layer, whatever `first_layer` says (what "auto" falls back to)."""
-        x = _abi.require_cuda(x, "FusedModel.forward_exact")
-        N, H, W, _ = x.shape
-        self._exact_now = True
-        try:
-            return self.forward_from(0, x, N, H, W, out=out)
-        finally:
-            self._exact_now = False
-
-    def take_flag(self):
-        """"auto": synchronise, return True and clear if this model's own flag word is raised (a captured graph or a bench
-        replay met a batch that is not image bytes / 255)."""
-        if self._flag is None:
-            return False
-        raised = int(self._flag.item()) != 0
-        if raised:
-            self._flag.zero_()
-        return raised
-
-    def check_domain(self):
-        """Synchronise the current stream and raise QnnError if a restricted-domain first layer ("fixed", "image") met
-        an input outside its domain since the last check (qnn_weights_check).  "auto": raises only for replays nobody
-        recomputed (hipGraph replays outside engine.Pipelined.forward).  A no-op for the exact and uint8 entries."""
-        if self.first_layer == "auto":
-            if self.take_flag():
-                raise _abi.QnnError("FusedModel: a replayed batch was not image bytes / 255 and has not been recomputed on "
-                                    "the exact first layer (run it through forward() / engine.Pipelined.forward())")
-            return
+    def _check_restricted(self):
         self.steps[0]["w"].check()
-
-    __call__ = forward
-    predict = forward
 
 
 # ---------------------------------------------------------------------------
 class _Virtual:
-    """An activation clip that has not been materialised: (pre-activation, fn, nb)."""
+    """An activation clip that has not been materialised: (pre-activation, fn, nb) of activation `op`."""
 
-    def __init__(self, pre, fn, nb):
-        self.pre, self.fn, self.nb = pre, fn, nb
+    def __init__(self, pre, fn, nb, op):
+        self.pre, self.fn, self.nb, self.op = pre, fn, nb, op
         self._mat = None
 
     def materialize(self):
-        if self._mat is None:
-            if self.fn == _abi.FN_GRID:             # already clipped (ternary_tanh): values ARE the grid
-                self._mat = self.pre
-            elif self.fn == _abi.FN_BINARY_TANH:
-                self._mat = binary_ops.binary_tanh(self.pre)
-            else:
-                self._mat = quantized_ops.quantized_tanh(self.pre, self.nb)
+        if self._mat is None:                       # FN_GRID: already clipped (ternary_tanh), the values ARE the grid
+            self._mat = self.pre if self.fn == _abi.FN_GRID else _act(self.pre, self.op)
         return self._mat
 
 
@@ -470,150 +579,77 @@ class GraphModel:
     def __init__(self, spec, device="cuda"):
         self.device = torch.device(device)
         self.spec = spec
-        self._weights = {}
-        self._bn = {}
-        # which ops consume each named tensor (to decide BN fusion)
-        self._names = []
-        for i, op in enumerate(spec):
-            self._names.append(op.get("dst", "t%d" % i))
-        self._consumers = {}
-        for i, op in enumerate(spec):
-            srcs = []
-            if op["op"] == "add":
-                srcs = [op["a"], op["b"]]
-            elif "src" in op:
-                srcs = [op["src"]]
-            elif i > 0:
-                srcs = [self._names[i - 1]]
-            else:
-                srcs = ["input"]
-            for s in srcs:
-                self._consumers.setdefault(s, []).append(i)
-        for i, op in enumerate(spec):
-            if op["op"] == "bn":
-                inv, shift = bn_constants(op)
-                self._bn[i] = (torch.as_tensor(inv).to(self.device), torch.as_tensor(shift).to(self.device))
-
-    def _get_weights(self, i, op, store):
-        key = (i, store)
-        if key not in self._weights:
-            st = tuple(op.get("strides", (1, 1)))
-            self._weights[key] = _prepack(op, store, self.device, stride=st[0],
-                                          same_pad=op.get("padding", "same") == "same")
-        return self._weights[key]
-
-    def _src(self, env, i, op):
-        if "src" in op:
-            return env[op["src"]]
-        return env[self._names[i - 1]] if i > 0 else env["input"]
+        self.graph = _SpecGraph(spec, device)
 
     @staticmethod
     def _plain(t):
         return t.materialize() if isinstance(t, _Virtual) else t
 
+    def _contract(self, i, op, src, inv, shift):
+        """Conv / dense op `i` on `src` with BN (inv, shift) in its epilogue."""
+        kind, wstore, g = op["op"], _wstore(op), self.graph
+        if isinstance(src, _Virtual) and wstore is not None:
+            bits = 1 if src.fn == _abi.FN_BINARY_TANH else src.nb
+            if src.fn == _abi.FN_GRID and op["kind"] == "ternary" and TERNARY_T2:
+                store = _abi.STORE_T2        # ternary x ternary: sign / mask planes, two popcounts
+            elif src.fn == _abi.FN_GRID:     # ternary codes {-1,0,1}: value = code, needs >= 4 bits
+                store = max(_abi.STORE_I4, wstore if wstore != _abi.STORE_BIN else _abi.STORE_I4)
+            else:
+                store = _join_store(bits, wstore)
+            pre = src.pre
+            C = pre.shape[-1]
+            w = g.weights(i, store)
+            nb_in = src.nb if src.fn == _abi.FN_QUANTIZED_TANH else 1
+            if kind == "conv" and src.fn == _abi.FN_GRID:
+                N, H, W, _ = pre.shape
+                xp = _abi.pack(pre, C, _abi.FN_GRID, 1, store)
+                return _abi.conv2d(w, xp, store, 1, N, H, W, inv, shift)[0]
+            if kind == "conv":
+                # activation clip fused on load, BN fused in the epilogue
+                return _abi.conv2d_f32in(w, pre, src.fn, nb_in, inv, shift)[0]
+            xp = _abi.pack(pre, C, src.fn, nb_in, store)
+            return _abi.dense(w, xp, store, bits, pre.shape[0], inv, shift)
+        xin = self._plain(src)
+        w = g.weights(i, _abi.STORE_F32)
+        if kind == "conv":
+            N, H, W, _ = xin.shape
+            xs = _abi.STORE_U8 if xin.dtype == torch.uint8 else _abi.STORE_F32    # typed image entry
+            return _abi.conv2d(w, xin, xs, 0, N, H, W, inv, shift)[0]
+        return _abi.dense(w, xin, _abi.STORE_F32, 0, xin.shape[0], inv, shift)
+
     def forward(self, x):
-        x = (_abi.require_cuda_u8(x, "GraphModel.forward") if isinstance(x, torch.Tensor) and x.dtype == torch.uint8
-             else _abi.require_cuda(x, "GraphModel.forward"))
-        env = {"input": x}
+        g, spec = self.graph, self.spec
+        env = {"input": _images(x, "GraphModel.forward")}
         skip = set()
-        spec = self.spec
         for i, op in enumerate(spec):
             if i in skip:
                 continue
-            kind = op["op"]
-            name = self._names[i]
+            kind, name = op["op"], g.names[i]
+            src = env[g.srcs[i][0]]
             if kind in ("conv", "dense"):
-                src = self._src(env, i, op)
                 # fuse an immediately following BN that is this tensor's only consumer
                 inv = shift = None
-                cons = self._consumers.get(name, [])
-                if len(cons) == 1 and spec[cons[0]]["op"] == "bn" and cons[0] == i + 1:
-                    inv, shift = self._bn[i + 1]
+                if g.cons.get(name, []) == [i + 1] and spec[i + 1]["op"] == "bn":
+                    inv, shift = g.bn[i + 1]
                     skip.add(i + 1)
-                    name = self._names[i + 1]
-                wstore = _wstore(op)
-                if isinstance(src, _Virtual) and wstore is not None:
-                    bits = 1 if src.fn == _abi.FN_BINARY_TANH else src.nb
-                    if src.fn == _abi.FN_GRID and op["kind"] == "ternary" and TERNARY_T2:
-                        store = _abi.STORE_T2        # ternary x ternary: sign / mask planes, two popcounts
-                    elif src.fn == _abi.FN_GRID:     # ternary codes {-1,0,1}: value = code, needs >= 4 bits
-                        store = max(_abi.STORE_I4, wstore if wstore != _abi.STORE_BIN else _abi.STORE_I4)
-                    else:
-                        store = _join_store(bits, wstore)
-                    pre = src.pre
-                    C = pre.shape[-1]
-                    w = self._get_weights(i, op, store)
-                    nb_in = src.nb if src.fn == _abi.FN_QUANTIZED_TANH else 1
-                    if kind == "conv" and src.fn == _abi.FN_GRID:
-                        N, H, W, _ = pre.shape
-                        xp = _abi.pack(pre, C, _abi.FN_GRID, 1, store)
-                        y, _, _ = _abi.conv2d(w, xp, store, 1, N, H, W, inv, shift)
-                    elif kind == "conv":
-                        # activation clip fused on load, BN fused in the epilogue
-                        y, _, _ = _abi.conv2d_f32in(w, pre, src.fn, nb_in, inv, shift)
-                    else:
-                        xp = _abi.pack(pre, C, src.fn, nb_in, store)
-                        y = _abi.dense(w, xp, store, bits, pre.shape[0], inv, shift)
-                else:
-                    xin = self._plain(src)
-                    w = self._get_weights(i, op, _abi.STORE_F32)
-                    if kind == "conv":
-                        N, H, W, _ = xin.shape
-                        xs = _abi.STORE_U8 if xin.dtype == torch.uint8 else _abi.STORE_F32    # typed image entry
-                        y, _, _ = _abi.conv2d(w, xin, xs, 0, N, H, W, inv, shift)
-                    else:
-                        y = _abi.dense(w, xin, _abi.STORE_F32, 0, xin.shape[0], inv, shift)
-                env[name] = y
-                continue
-            src = None if kind == "add" else self._src(env, i, op)
-            if kind == "bn":
-                inv, shift = self._bn[i]
-                y = self._plain(src) * inv + shift      # two roundings, as tf.nn.batch_normalization
-            elif kind == "act":
-                fn = op["fn"]
-                pre = self._plain(src)
-                if fn == "binary_tanh":
-                    y = _Virtual(pre, _abi.FN_BINARY_TANH, 1)
-                elif fn == "quantized_tanh" and op["nb"] <= 8:
-                    y = _Virtual(pre, _abi.FN_QUANTIZED_TANH, int(op["nb"]))
-                elif fn == "quantized_tanh":
-                    y = quantized_ops.quantized_tanh(pre, op["nb"])
-                elif fn == "ternary_tanh":
-                    # global mean over the batch tensor (ternary_ops.py:23): not fusable; the
-                    # result is on the grid {-1,0,1} and is packed as such by its consumers
-                    y = _Virtual(ternary_ops.ternary_tanh(pre), _abi.FN_GRID, 1)
-                elif fn == "leaky_relu":
-                    y = torch.where(pre >= 0, pre, pre * F32(op.get("alpha", 0.3)))
-                else:
-                    raise ValueError(fn)
-            elif kind == "maxpool":
-                t = self._plain(src)
-                s = op.get("size", 2)
-                N, H, W, C = t.shape
-                y = t[:, :H // s * s, :W // s * s, :].reshape(N, H // s, s, W // s, s, C).amax(dim=(2, 4))
-            elif kind == "avgpool":
-                t = self._plain(src)
-                s = op.get("size", 8)
-                N, H, W, C = t.shape
-                win = t[:, :H // s * s, :W // s * s, :].reshape(N, H // s, s, W // s, s, C)
-                # window sums of grid values are exact in float64; one division in float32
-                y = (win.double().sum(dim=(2, 4)).float() / F32(s * s))
-            elif kind == "zeropad":
-                p = op["pad"]
-                y = torch.nn.functional.pad(self._plain(src), (0, 0, p, p, p, p))
-            elif kind == "flatten":
-                t = self._plain(src)
-                y = t.reshape(t.shape[0], -1)
+                    name = g.names[i + 1]
+                y = self._contract(i, op, src, inv, shift)
+            elif kind == "bn":
+                y = _bn_apply(self._plain(src), *g.bn[i])
             elif kind == "add":
-                y = self._plain(env[op["a"]]) + self._plain(env[op["b"]])
-            elif kind == "scale":
-                y = self._plain(src) * F32(op["value"])
-            elif kind == "softmax":
-                y = _abi.softmax(self._plain(src))
+                y = _add(self._plain(src), self._plain(env[op["b"]]))
+            elif kind == "act" and _act_code(op) is not None:
+                y = _Virtual(self._plain(src), *_act_code(op), op)      # its consumers fuse the clip into their pack-on-load
+            elif kind == "act" and op["fn"] == "ternary_tanh":
+                # global mean over the batch tensor: not fusable; the result is on the grid {-1,0,1} and is packed as
+                # such by its consumers
+                y = _Virtual(_act(self._plain(src), op), _abi.FN_GRID, 1, op)
+            elif kind in _GLUE:
+                y = _GLUE[kind](self._plain(src), op)
             else:
                 raise ValueError(kind)
             env[name] = y
-        return self._plain(env[self._names[-1]])
+        return self._plain(env[g.names[-1]])
 
     __call__ = forward
     predict = forward
@@ -627,13 +663,43 @@ class _Packed:
         self.t, self.store, self.bits, self.shape = t, store, bits, tuple(shape)   # shape: NHWC or (N, K)
 
     def to_f32(self):
-        n = 1
-        for d in self.shape[:-1]:
-            n *= d
-        return _abi.unpack(self.t, n, self.shape[-1], self.store, self.bits).reshape(self.shape)
+        return _abi.unpack(self.t, math.prod(self.shape[:-1]), self.shape[-1], self.store, self.bits).reshape(self.shape)
 
 
-class ResidualFusedModel:
+def _ok_lowbit(op):
+    """Convs the fused epilogue path takes: low-bit weights (packed input) or the float-input
+    first layer; stock float convs stay on the float32 route."""
+    return op["op"] == "conv" and op["kind"] in ("binary", "quantized", "ternary") and op.get("nb", 1) <= 8
+
+
+def _stored_bytes(store, pixels, ch):
+    """Bytes of a tensor as stored (SURVEY.md 8d model M1)."""
+    if store == _abi.STORE_U8:
+        return pixels * ch
+    if store in (_abi.STORE_F32, _abi.STORE_F32_IMAGE, _abi.STORE_F32_UNIT):
+        return pixels * ch * 4
+    return pixels * _abi.words(store, ch) * 4
+
+
+def _capture_entry(kernel, launch, op, xshape, Ho, Wo, xs, out_store, res, res_store, proj):
+    """One launch of a forward as bench.py re-issues it for per-kernel timing (the closure keeps the operands alive);
+    bytes = tensors as stored: input + output + shortcut."""
+    N, H, W, C = xshape
+    kh, kw, _, cout = op["kernel"].shape
+    b = _stored_bytes(xs, N * H * W, C) + _stored_bytes(out_store, N * Ho * Wo, cout)
+    if res is not None:
+        b += _stored_bytes(res_store, N * Ho * Wo, cout)
+    if proj is not None:                     # the even rows of the block input (every other pixel of a row shares its
+        ps = proj[1].shape                   # 32-byte sectors with the pixels that are read)
+        b += _stored_bytes(proj[1].store, ps[0] * ((ps[1] + 1) // 2) * ps[2], ps[3])
+    return dict(kernel=kernel, launch=lambda: launch()[0],
+                shape=(N, H, W, C, cout, kh, tuple(op.get("strides", (1, 1)))[0],
+                       "res_" + ("proj" if proj is not None else "none" if res is None
+                                 else "packed" if isinstance(res, _Packed) else "f32")),
+                bytes=b, macs=N * Ho * Wo * kh * kw * C * cout, pipe="f32" if kernel.startswith("mfma_f32") else "i8")
+
+
+class ResidualFusedModel(_DomainFlag):
     """Packed, fused execution of arbitrary (residual) specs -- SURVEY.md 8f.1.
 
     Every `conv -> BN -> act` chain and every residual merge
@@ -644,6 +710,9 @@ class ResidualFusedModel:
     that merges it.  Anything that is not on the low-bit path (avg-pool, softmax, ...) runs as
     float32 torch ops on unpacked tensors.
     """
+
+    _UNRECOMPUTED = ("ResidualFusedModel: a replayed batch was not image bytes / 255 and has not been "
+                     "recomputed on the exact first layer")
 
     def __init__(self, spec, device="cuda", first_layer="auto", fold=True, fuse_projection=True):
         """first_layer: kernel for float32 images in front of the first (3-channel) conv, as engine.FusedModel:
@@ -656,47 +725,18 @@ class ResidualFusedModel:
         if first_layer not in ("auto", "exact", "image"):
             raise ValueError("first_layer must be 'auto', 'exact' or 'image', got %r" % (first_layer,))
         self.first_layer = first_layer
-        self._flag = None
-        self._exact_now = False
         self.fold = bool(fold)
         self._folds = {}                     # (conv, bn, shortcut kind, ...) -> _abi.Fold or None
         self.fuse_projection = bool(fuse_projection)   # projection shortcuts inside the second conv's launch (qnn_projection_t)
-        self._proj_ok = {}                   # conv index -> the pair is eligible (False after a QNN_EUNSUPPORTED)
+        self._proj_ok = {}                   # conv index -> False once the library had no kernel for the pair
+        self._plans = {}                     # tensor name -> what _plan() matched in front of it
         self.device = torch.device(device)
-        self.spec = spec
-        self.names = [op.get("dst", "t%d" % i) for i, op in enumerate(spec)]
-        self.prod = {n: i for i, n in enumerate(self.names)}
-        self.srcs = []
-        for i, op in enumerate(spec):
-            if op["op"] == "add":
-                self.srcs.append([op["a"], op["b"]])
-            elif "src" in op:
-                self.srcs.append([op["src"]])
-            else:
-                self.srcs.append([self.names[i - 1] if i > 0 else "input"])
-        self.cons = {}
-        for i, ss in enumerate(self.srcs):
-            for s_ in ss:
-                self.cons.setdefault(s_, []).append(i)
-        self._w = {}
-        self._bn = {}
-        for i, op in enumerate(spec):
-            if op["op"] == "bn":
-                inv, shift = bn_constants(op)
-                self._bn[i] = (torch.as_tensor(inv).to(self.device), torch.as_tensor(shift).to(self.device))
+        g = self.graph = _SpecGraph(spec, device)
+        self.spec, self.names, self.prod, self.srcs, self.cons = spec, g.names, g.prod, g.srcs, g.cons
         self.kernel_log = None
         self.capture = None
 
-    # ---- helpers -----------------------------------------------------------------
-    def _weights(self, i, store):
-        key = (i, store)
-        if key not in self._w:
-            op = self.spec[i]
-            st = tuple(op.get("strides", (1, 1)))
-            self._w[key] = _prepack(op, store, self.device, stride=st[0],
-                                    same_pad=op.get("padding", "same") == "same")
-        return self._w[key]
-
+    # ---- what the spec alone decides: matched once per model ----------------------
     def _single(self, name, kind):
         """Index of the op producing `name` if it is of `kind` and `name` has one consumer."""
         i = self.prod.get(name)
@@ -704,13 +744,34 @@ class ResidualFusedModel:
             return None
         return i
 
+    def _conv_bn_of(self, name):
+        """(conv index, bn index or None) if `name` is conv or conv->bn with single consumers."""
+        b = self._single(name, "bn")
+        c = self._single(self.srcs[b][0] if b is not None else name, "conv")
+        return None if c is None else (c, b)
+
+    def _fusable_before(self, pre):
+        """The launches activation input `pre` can be the epilogue of: conv -> bn, or the residual merge
+        conv -> bn -> add(shortcut) -> [scale] read with either operand of the add as the main path.
+        List of (conv index, bn index or None, shortcut name or None, post_scale); the caller takes the first one whose
+        conv it has a kernel for."""
+        cb = self._conv_bn_of(pre)
+        if cb is not None:
+            return [(cb[0], cb[1], None, 1.0)]
+        sc_i = self._single(pre, "scale")
+        post = float(self.spec[sc_i]["value"]) if sc_i is not None else 1.0
+        ad_i = self._single(self.srcs[sc_i][0] if sc_i is not None else pre, "add")
+        if ad_i is None:
+            return []
+        a_n, b_n = self.srcs[ad_i]
+        return [cb + (short, post) for main, short in ((b_n, a_n), (a_n, b_n))
+                if (cb := self._conv_bn_of(main)) is not None]
+
     def _projection_of(self, short, ci, fn, bits, out_store):
         """Index of the conv op behind shortcut `short` if it is a projection the second conv `ci` of the block can compute
         inside its own launch (qnn_projection_t, include/qnn_abi.h): a 1x1 strides-2 4-bit QuantizedConv2D with one consumer
         (models/resnet.py:117-124), `ci` a 3x3 stride-1 4-bit layer with cin = cout in {32, 64} = twice the projection's
         input channels, packed 4-bit quantized_tanh output.  None = keep the float32 shortcut tensor."""
-        if not self.fuse_projection or self._proj_ok.get(ci) is False:
-            return None
         pi = self._single(short, "conv")
         if pi is None:
             return None
@@ -721,7 +782,6 @@ class ResidualFusedModel:
               and tuple(mk[:2]) == (3, 3) and tuple(mo.get("strides", (1, 1))) == (1, 1) and mo.get("padding", "same") == "same"
               and mk[2] == mk[3] and mk[3] in (32, 64) and pk[3] == mk[3] and 2 * pk[2] == mk[2]
               and fn == _abi.FN_QUANTIZED_TANH and bits == 4 and out_store == _abi.STORE_I4)
-        self._proj_ok[ci] = bool(ok)
         return pi if ok else None
 
     def _act_out_store(self, name, bits):
@@ -753,323 +813,193 @@ class ResidualFusedModel:
                     out.append(self.spec[ci])
         return out
 
-    def _own_flag(self):
-        if self._flag is None:
-            self._flag = torch.zeros(1, dtype=torch.int32, device=self.device)
-        return self._flag
+    def _plan(self, name):
+        """What is fused in front of the bn or activation `name`, as far as the spec decides it:
+          bn                  (conv, bn) of the launch it is the epilogue of, or None;
+          low-bit clip        (packed store or None, output store, the launch out of _fusable_before() or None, the
+                              projection conv that launch can compute itself or None);
+          LeakyReLU(0.3)      the _fusable_before() list: which one has a kernel depends on the evaluated source;
+          ternary_tanh        (packed store or None, every contraction behind it has ternary weights: T2 planes)."""
+        if name in self._plans:
+            return self._plans[name]
+        i = self.prod[name]
+        op, pre, p = self.spec[i], self.srcs[i][0], None
+        ac = _act_code(op) if op["op"] == "act" else None
+        if op["op"] == "bn":
+            p = self._conv_bn_of(name)
+        elif ac is not None:
+            store = self._act_out_store(name, ac[1])
+            out_store = store if store is not None else _abi.STORE_F32
+            m = next((m for m in self._fusable_before(pre) if _ok_lowbit(self.spec[m[0]])), None)
+            pj = self._projection_of(m[2], m[0], ac[0], ac[1], out_store) if m is not None and m[2] is not None else None
+            p = store, out_store, m, pj
+        elif op["fn"] == "leaky_relu":
+            p = self._fusable_before(pre) if F32(op.get("alpha", 0.3)) == F32(0.3) else []
+        elif op["fn"] == "ternary_tanh":
+            users = self._users_through_pools(name)
+            p = (self._act_out_store(name, 4),      # codes {-1,0,1}: at least 4-bit storage
+                 any(u["op"] in ("conv", "dense") for u in users) and
+                 all(u["op"] in ("add", "avgpool") or (u["op"] in ("conv", "dense") and u["kind"] == "ternary")
+                     for u in users))
+        self._plans[name] = p
+        return p
 
-    def take_flag(self):
-        if self._flag is None:
-            return False
-        raised = int(self._flag.item()) != 0
-        if raised:
-            self._flag.zero_()
-        return raised
-
-    def check_domain(self):
-        """Synchronise and raise QnnError if the "image" first layer met a float32 input that is not a byte / 255
-        ("auto": only for replays nobody recomputed, as FusedModel.check_domain)."""
-        if self.first_layer == "auto":
-            if self.take_flag():
-                raise _abi.QnnError("ResidualFusedModel: a replayed batch was not image bytes / 255 and has not been "
-                                    "recomputed on the exact first layer")
-            return
-        for w in self._w.values():
+    def _check_restricted(self):
+        for w in self.graph.packed.values():
             if w.shape[2] <= 4 and w.store == _abi.STORE_F32:
                 w.check()
 
-    def forward_exact(self, x):
-        self._exact_now = True
-        try:
-            return self._forward(x)
-        finally:
-            self._exact_now = False
-
-    # ---- evaluation --------------------------------------------------------------
-    def forward(self, x):
-        y = self._forward(x)
-        if self.first_layer == "auto" and not self._exact_now and isinstance(x, torch.Tensor) and x.dtype == torch.float32 \
-                and self._flag is not None and not torch.cuda.is_current_stream_capturing():
-            if int(self._flag.item()) != 0:          # not image bytes / 255: recompute on the exact first layer
-                self._flag.zero_()
-                y = self.forward_exact(x)
-        return y
-
+    # ---- evaluation: demand-driven from the output, memoised per forward in `memo` (tensor name -> value) ---------
     def _forward(self, x):
-        x = (_abi.require_cuda_u8(x, "ResidualFusedModel.forward")
-             if isinstance(x, torch.Tensor) and x.dtype == torch.uint8
-             else _abi.require_cuda(x, "ResidualFusedModel.forward"))
-        memo = {"input": x}
-
-        def f32(name):
-            v = ev(name)
-            return v.to_f32() if isinstance(v, _Packed) else v
-
-        def conv_call(ci, bn_i, res, post_scale, fn, bits, out_store, proj=None):
-            """Launch conv `ci` with everything fused behind it.  proj = (conv index of a 1x1 strides-2 projection, its packed
-            input): the shortcut is computed inside this launch (qnn_projection_t) instead of being read from `res`."""
-            op = self.spec[ci]
-            src = ev(self.srcs[ci][0])
-            inv, shift = self._bn[bn_i] if bn_i is not None else (None, None)
-            rkw = {}
-            if proj is not None:
-                psrc = proj[1]
-                rkw = dict(post_scale=post_scale,
-                           proj=(self._weights(proj[0], psrc.store), psrc.t, psrc.shape[1], psrc.shape[2], psrc.bits))
-            if res is not None:
-                if isinstance(res, _Packed) and res.store == _abi.STORE_T2:
-                    res = res.to_f32()           # the shortcut operand of the epilogue reads codes or float32, not bit planes
-                if isinstance(res, _Packed):
-                    rkw = dict(res=res.t, res_store=res.store, res_bits=res.bits, post_scale=post_scale)
-                else:
-                    rkw = dict(res=res.contiguous(), res_store=_abi.STORE_F32, res_bits=0, post_scale=post_scale)
-            ab = bits if fn == _abi.FN_QUANTIZED_TANH else 0
-            if isinstance(src, _Packed) and _wstore(op) is None:
-                src = src.to_f32()               # stock float conv: float32 route
-            if isinstance(src, _Packed):
-                N, H, W, C = src.shape
-                w = self._weights(ci, src.store)
-                xin, xs, xb = src.t, src.store, src.bits
-            else:
-                N, H, W, C = src.shape
-                w = self._weights(ci, _abi.STORE_F32)
-                xin, xs, xb = src.contiguous(), _abi.STORE_F32, 0
-                if src.dtype == torch.uint8:     # the images as bytes: typed QNN_STORE_U8 entry
-                    xs = _abi.STORE_U8
-
-            dflag = None
-            if xs == _abi.STORE_F32 and src is memo["input"] and not self._exact_now:
-                if self.first_layer == "image":
-                    xs = _abi.STORE_F32_IMAGE    # the images: declared as bytes / 255 for this call (typed entry)
-                elif self.first_layer == "auto":
-                    xs = _abi.STORE_F32_IMAGE    # ... with this model's own flag word: forward() recomputes a flagged batch
-                    dflag = self._own_flag()
-
-            fold = None
-            if self.fold and proj is None and xs == _abi.STORE_I4 and out_store == _abi.STORE_I4 \
-                    and fn == _abi.FN_QUANTIZED_TANH and ab == 4 \
-                    and (res is None or (isinstance(res, _Packed) and res.store == _abi.STORE_I4 and res.bits == 4)):
-                fkey = (ci, bn_i, xb, None if res is None else float(post_scale))
-                if fkey not in self._folds and not torch.cuda.is_current_stream_capturing():
-                    self._folds[fkey] = _abi.Fold.try_prepare(          # (synchronises: never inside a capture)
-                        w, xs, xb, inv, shift, fn, ab, out_store, **{k: v for k, v in rkw.items()})
-                fold = self._folds.get(fkey)
-
-            def launch():
-                return _abi.conv2d(w, xin, xs, xb, N, H, W, inv, shift, fn, ab, 1, out_store, fold=fold, domain_flag=dflag,
-                                   **rkw)
-
-            y, Ho, Wo = launch()
-            if self.kernel_log is not None:
-                self.kernel_log.append(_abi.last_kernel())
-            cout = op["kernel"].shape[3]
-            if self.capture is not None:
-                # bench.py re-issues every launch of one forward for per-kernel timing: the closure keeps the
-                # operands alive; bytes = tensors as stored (input + output + shortcut), SURVEY.md 8d model M1
-                def nbytes(store, pixels, ch):
-                    if store == _abi.STORE_U8:
-                        return pixels * ch
-                    if store in (_abi.STORE_F32, _abi.STORE_F32_IMAGE, _abi.STORE_F32_UNIT):
-                        return pixels * ch * 4
-                    return pixels * _abi.words(store, ch) * 4
-                kh, kw = op["kernel"].shape[:2]
-                b = nbytes(xs, N * H * W, C) + nbytes(out_store, N * Ho * Wo, cout)
-                if res is not None:
-                    b += nbytes(rkw["res_store"], N * Ho * Wo, cout)
-                if proj is not None:                 # the even rows of the block input (every other pixel of a row shares its
-                    ps = proj[1].shape               # 32-byte sectors with the pixels that are read)
-                    b += nbytes(proj[1].store, ps[0] * ((ps[1] + 1) // 2) * ps[2], ps[3])
-                self.capture.append(dict(kernel=_abi.last_kernel(), launch=lambda: launch()[0],
-                                         shape=(N, H, W, C, cout, kh, tuple(op.get("strides", (1, 1)))[0],
-                                                "res_" + ("proj" if proj is not None else "none" if res is None
-                                                          else "packed" if isinstance(res, _Packed) else "f32")),
-                                         bytes=b, macs=N * Ho * Wo * kh * kw * C * cout,
-                                         pipe="f32" if _abi.last_kernel().startswith("mfma_f32") else "i8"))
-            if out_store == _abi.STORE_F32:
-                return y
-            return _Packed(y, out_store, bits, (N, Ho, Wo, cout))
-
-        def conv_bn_of(name):
-            """(conv index, bn index or None) if `name` is conv or conv->bn with single consumers."""
-            b = self._single(name, "bn")
-            if b is not None:
-                c = self._single(self.srcs[b][0], "conv")
-                if c is not None:
-                    return c, b
-                return None
-            c = self._single(name, "conv")
-            if c is not None:
-                return c, None
-            return None
-
-        def leaky_on_f32_kernel(ci):
-            """True if conv `ci` reads float32 activations that only the float32-activation kernel or k_conv_generic take
-            (not the images, not 1 or 3 channels): those two implement FN_LEAKY_RELU, so fusing it costs nothing."""
-            src = ev(self.srcs[ci][0])
-            return not isinstance(src, _Packed) and src is not memo["input"] and src.shape[-1] not in (1, 3)
-
-        def leaky_plan(pre_name):
-            """LeakyReLU(alpha = 0.3) inside the launch of the conv behind it: conv -> bn -> leaky, or
-            conv -> bn -> add(shortcut) -> [scale] -> leaky with the float32 shortcut in the epilogue.
-            (conv index, bn index, shortcut name or None, post_scale), or None = not fusable."""
-            cb = conv_bn_of(pre_name)
-            if cb is not None:
-                return (cb[0], cb[1], None, 1.0) if leaky_on_f32_kernel(cb[0]) else None
-            sc_i = self._single(pre_name, "scale")
-            add_name = self.srcs[sc_i][0] if sc_i is not None else pre_name
-            post = float(self.spec[sc_i]["value"]) if sc_i is not None else 1.0
-            ad_i = self._single(add_name, "add")
-            if ad_i is None:
-                return None
-            a_n, b_n = self.srcs[ad_i]
-            for main, short in ((b_n, a_n), (a_n, b_n)):
-                cb = conv_bn_of(main)
-                if cb is not None and leaky_on_f32_kernel(cb[0]):
-                    return cb[0], cb[1], short, post
-            return None
-
-        def ev(name):
-            if name in memo:
-                return memo[name]
-            i = self.prod[name]
-            op = self.spec[i]
-            kind = op["op"]
-            out = None
-            if kind == "act":
-                ac = _act_code(op)
-                pre_name = self.srcs[i][0]
-                if ac is not None:
-                    fn, bits = ac
-                    store = self._act_out_store(name, bits)
-                    out_store = store if store is not None else _abi.STORE_F32
-                    # pattern 1: conv -> bn -> act
-                    cb = conv_bn_of(pre_name)
-                    if cb is not None and _ok_lowbit(self.spec[cb[0]]):
-                        out = conv_call(cb[0], cb[1], None, 1.0, fn, bits, out_store)
-                    else:
-                        # pattern 2: conv -> bn -> add(shortcut) -> [scale] -> act
-                        sc_i = self._single(pre_name, "scale")
-                        add_name = self.srcs[sc_i][0] if sc_i is not None else pre_name
-                        post = float(self.spec[sc_i]["value"]) if sc_i is not None else 1.0
-                        ad_i = self._single(add_name, "add")
-                        if ad_i is not None:
-                            a_n, b_n = self.srcs[ad_i]
-                            for main, short in ((b_n, a_n), (a_n, b_n)):
-                                cb = conv_bn_of(main)
-                                if cb is not None and _ok_lowbit(self.spec[cb[0]]):
-                                    pj = self._projection_of(short, cb[0], fn, bits, out_store)
-                                    if pj is not None:
-                                        psrc = ev(self.srcs[pj][0])
-                                        if isinstance(psrc, _Packed) and psrc.store == _abi.STORE_I4:
-                                            try:
-                                                out = conv_call(cb[0], cb[1], None, post, fn, bits, out_store, proj=(pj, psrc))
-                                                break
-                                            except _abi.QnnUnsupported:      # no kernel for this pair: two launches, as before
-                                                self._proj_ok[cb[0]] = False
-                                    res = ev(short)
-                                    out = conv_call(cb[0], cb[1], res, post, fn, bits, out_store)
-                                    break
-                    if out is None:      # no fusable producer: clip (+pack) the float32 tensor
-                        pre = f32(pre_name)
-                        if store is not None:
-                            C = pre.shape[-1]
-                            nb_in = bits if fn == _abi.FN_QUANTIZED_TANH else 1
-                            out = _Packed(_abi.pack(pre, C, fn, nb_in, store), store, bits, pre.shape)
-                        else:
-                            out = (binary_ops.binary_tanh(pre) if fn == _abi.FN_BINARY_TANH
-                                   else quantized_ops.quantized_tanh(pre, bits))
-                elif op["fn"] == "leaky_relu" and F32(op.get("alpha", 0.3)) == F32(0.3) and \
-                        (plan := leaky_plan(pre_name)) is not None:
-                    ci, bn_i, short, post = plan
-                    res = ev(short) if short is not None else None
-                    out = conv_call(ci, bn_i, res, post, _abi.FN_LEAKY_RELU, 0, _abi.STORE_F32)
-                else:
-                    pre = f32(pre_name)
-                    fnn = op["fn"]
-                    if fnn == "quantized_tanh":
-                        out = quantized_ops.quantized_tanh(pre, op["nb"])
-                    elif fnn == "ternary_tanh":
-                        out = ternary_ops.ternary_tanh(pre)
-                        tstore = self._act_out_store(name, 4)      # codes {-1,0,1}: at least 4-bit storage
-                        users = self._users_through_pools(name)
-                        if TERNARY_T2 and any(u["op"] in ("conv", "dense") for u in users) and \
-                                all(u["op"] in ("add", "avgpool") or
-                                    (u["op"] in ("conv", "dense") and u["kind"] == "ternary") for u in users):
-                            tstore = _abi.STORE_T2                 # every contraction behind it has ternary weights
-                        if tstore is not None:
-                            out = _Packed(_abi.pack(out, out.shape[-1], _abi.FN_GRID, 1, tstore), tstore, 1, out.shape)
-                    elif fnn == "leaky_relu":
-                        out = torch.where(pre >= 0, pre, pre * F32(op.get("alpha", 0.3)))
-                    else:
-                        raise ValueError(fnn)
-            elif kind == "bn":
-                cb = conv_bn_of(name)
-                if cb is not None:
-                    out = conv_call(cb[0], cb[1], None, 1.0, _abi.FN_NONE, 0, _abi.STORE_F32)
-                else:
-                    inv, shift = self._bn[i]
-                    out = f32(self.srcs[i][0]) * inv + shift
-            elif kind == "conv":
-                out = conv_call(i, None, None, 1.0, _abi.FN_NONE, 0, _abi.STORE_F32)
-            elif kind == "dense":
-                src = ev(self.srcs[i][0])
-                if isinstance(src, _Packed) and _wstore(op) is not None:
-                    w = self._weights(i, src.store)
-                    out = _abi.dense(w, src.t, src.store, src.bits, src.shape[0])
-                else:
-                    xin = src.to_f32() if isinstance(src, _Packed) else src
-                    out = _abi.dense(self._weights(i, _abi.STORE_F32), xin.contiguous(), _abi.STORE_F32, 0, xin.shape[0])
-            elif kind == "flatten":
-                src = ev(self.srcs[i][0])
-                if isinstance(src, _Packed) and src.shape[-1] % _abi.per_word(src.store) == 0:
-                    N = src.shape[0]
-                    k = 1
-                    for d in src.shape[1:]:
-                        k *= d
-                    out = _Packed(src.t, src.store, src.bits, (N, k))
-                else:
-                    t = src.to_f32() if isinstance(src, _Packed) else src
-                    out = t.reshape(t.shape[0], -1)
-            elif kind == "add":
-                out = f32(self.srcs[i][0]) + f32(self.srcs[i][1])
-            elif kind == "scale":
-                out = f32(self.srcs[i][0]) * F32(op["value"])
-            elif kind == "maxpool":
-                src = ev(self.srcs[i][0])
-                t = src.to_f32() if isinstance(src, _Packed) else src
-                s_ = op.get("size", 2)
-                N, H, W, C = t.shape
-                out = t[:, :H // s_ * s_, :W // s_ * s_, :].reshape(N, H // s_, s_, W // s_, s_, C).amax(dim=(2, 4))
-                if isinstance(src, _Packed) and src.store == _abi.STORE_T2:
-                    # the maximum of ternary codes is a ternary code: stay on the bit planes for the next ternary layer
-                    out = _Packed(_abi.pack(out.contiguous(), C, _abi.FN_GRID, 1, src.store), src.store, src.bits, out.shape)
-            elif kind == "avgpool":
-                src = ev(self.srcs[i][0]); s_ = op.get("size", 8)
-                if isinstance(src, _Packed) and src.store == _abi.STORE_T2:
-                    src = src.to_f32()
-                if isinstance(src, _Packed):     # window sums on the codes: no float32 copy of the activation
-                    N, H, W, C = src.shape
-                    out = _abi.avgpool_packed(src.t, src.store, src.bits, N, H, W, C, s_)
-                else:
-                    t = src
-                    N, H, W, C = t.shape
-                    win = t[:, :H // s_ * s_, :W // s_ * s_, :].reshape(N, H // s_, s_, W // s_, s_, C)
-                    out = win.double().sum(dim=(2, 4)).float() / F32(s_ * s_)
-            elif kind == "zeropad":
-                p_ = op["pad"]
-                out = torch.nn.functional.pad(f32(self.srcs[i][0]), (0, 0, p_, p_, p_, p_))
-            elif kind == "softmax":
-                out = _abi.softmax(f32(self.srcs[i][0]))
-            else:
-                raise ValueError(kind)
-            memo[name] = out
-            return out
-
-        res = ev(self.names[-1])
+        memo = {"input": _images(x, "ResidualFusedModel.forward")}
+        res = self._ev(memo, self.names[-1])
         return res.to_f32() if isinstance(res, _Packed) else res
 
-    __call__ = forward
-    predict = forward
+    def _ev(self, memo, name):
+        if name not in memo:
+            memo[name] = self._compute(memo, self.prod[name], name)
+        return memo[name]
+
+    def _f32(self, memo, name):
+        v = self._ev(memo, name)
+        return v.to_f32() if isinstance(v, _Packed) else v
+
+    def _conv_call(self, memo, ci, bn_i, res, post_scale, fn, bits, out_store, proj=None):
+        """Launch conv `ci` with everything fused behind it.  proj = (conv index of a 1x1 strides-2 projection, its packed
+        input): the shortcut is computed inside this launch (qnn_projection_t) instead of being read from `res`."""
+        op = self.spec[ci]
+        src = self._ev(memo, self.srcs[ci][0])
+        inv, shift = self.graph.bn[bn_i] if bn_i is not None else (None, None)
+        rkw = {}
+        if proj is not None:
+            psrc = proj[1]
+            rkw = dict(post_scale=post_scale,
+                       proj=(self.graph.weights(proj[0], psrc.store), psrc.t, psrc.shape[1], psrc.shape[2], psrc.bits))
+        if res is not None:
+            if isinstance(res, _Packed) and res.store == _abi.STORE_T2:
+                res = res.to_f32()           # the shortcut operand of the epilogue reads codes or float32, not bit planes
+            if isinstance(res, _Packed):
+                rkw = dict(res=res.t, res_store=res.store, res_bits=res.bits, post_scale=post_scale)
+            else:
+                rkw = dict(res=res.contiguous(), res_store=_abi.STORE_F32, res_bits=0, post_scale=post_scale)
+        ab = bits if fn == _abi.FN_QUANTIZED_TANH else 0
+        if isinstance(src, _Packed) and _wstore(op) is None:
+            src = src.to_f32()               # stock float conv: float32 route
+        N, H, W, C = src.shape
+        if isinstance(src, _Packed):
+            xin, xs, xb = src.t, src.store, src.bits
+        else:                                # the images as bytes: typed QNN_STORE_U8 entry
+            xin, xs, xb = src.contiguous(), _abi.STORE_U8 if src.dtype == torch.uint8 else _abi.STORE_F32, 0
+        w = self.graph.weights(ci, xs if isinstance(src, _Packed) else _abi.STORE_F32)
+
+        dflag = None
+        if xs == _abi.STORE_F32 and src is memo["input"] and not self._exact_now and self.first_layer in ("image", "auto"):
+            xs = _abi.STORE_F32_IMAGE        # the images: declared as bytes / 255 for this call (typed entry)
+            if self.first_layer == "auto":   # ... with the domain-flag word forward() reads to recompute a flagged batch
+                dflag = self._own_flag()
+
+        fold = None
+        if self.fold and proj is None and xs == _abi.STORE_I4 and out_store == _abi.STORE_I4 \
+                and fn == _abi.FN_QUANTIZED_TANH and ab == 4 \
+                and (res is None or (isinstance(res, _Packed) and res.store == _abi.STORE_I4 and res.bits == 4)):
+            fkey = (ci, bn_i, xb, None if res is None else float(post_scale))
+            if fkey not in self._folds and not torch.cuda.is_current_stream_capturing():
+                self._folds[fkey] = _abi.Fold.try_prepare(          # (synchronises: never inside a capture)
+                    w, xs, xb, inv, shift, fn, ab, out_store, **rkw)
+            fold = self._folds.get(fkey)
+
+        def launch():
+            return _abi.conv2d(w, xin, xs, xb, N, H, W, inv, shift, fn, ab, 1, out_store, fold=fold, domain_flag=dflag,
+                               **rkw)
+
+        y, Ho, Wo = launch()
+        kernel = _abi.last_kernel()
+        if self.kernel_log is not None:
+            self.kernel_log.append(kernel)
+        if self.capture is not None:
+            self.capture.append(_capture_entry(kernel, launch, op, (N, H, W, C), Ho, Wo, xs, out_store, res,
+                                               rkw.get("res_store"), proj))
+        return y if out_store == _abi.STORE_F32 else _Packed(y, out_store, bits, (N, Ho, Wo, op["kernel"].shape[3]))
+
+    def _leaky_on_f32_kernel(self, memo, ci):
+        """True if conv `ci` reads float32 activations that only the float32-activation kernel or k_conv_generic take
+        (not the images, not 1 or 3 channels): those two implement FN_LEAKY_RELU, so fusing it costs nothing."""
+        src = self._ev(memo, self.srcs[ci][0])
+        return not isinstance(src, _Packed) and src is not memo["input"] and src.shape[-1] not in (1, 3)
+
+    def _merge(self, memo, m, fn, bits, out_store):
+        """Launch `m` out of _fusable_before() with activation `fn` in its epilogue and the shortcut read from its tensor."""
+        ci, bn_i, short, post = m
+        res = self._ev(memo, short) if short is not None else None
+        return self._conv_call(memo, ci, bn_i, res, post, fn, bits, out_store)
+
+    def _activation(self, memo, i, name):
+        op, pre_name = self.spec[i], self.srcs[i][0]
+        ac = _act_code(op)
+        if ac is not None:
+            fn, bits = ac
+            store, out_store, m, pj = self._plan(name)
+            if m is not None and pj is not None and self.fuse_projection and self._proj_ok.get(m[0], True):
+                psrc = self._ev(memo, self.srcs[pj][0])
+                if isinstance(psrc, _Packed) and psrc.store == _abi.STORE_I4:
+                    try:
+                        return self._conv_call(memo, m[0], m[1], None, m[3], fn, bits, out_store, proj=(pj, psrc))
+                    except _abi.QnnUnsupported:      # no kernel for this pair: two launches, as before
+                        self._proj_ok[m[0]] = False
+            if m is not None:
+                return self._merge(memo, m, fn, bits, out_store)
+            pre = self._f32(memo, pre_name)          # no fusable producer: clip (+pack) the float32 tensor
+            if store is None:
+                return _act(pre, op)
+            nb_in = bits if fn == _abi.FN_QUANTIZED_TANH else 1
+            return _Packed(_abi.pack(pre, pre.shape[-1], fn, nb_in, store), store, bits, pre.shape)
+        if op["fn"] == "leaky_relu":
+            # LeakyReLU(alpha = 0.3) inside the launch of the conv behind it, with the float32 shortcut in the epilogue
+            m = next((m for m in self._plan(name) if self._leaky_on_f32_kernel(memo, m[0])), None)
+            if m is not None:
+                return self._merge(memo, m, _abi.FN_LEAKY_RELU, 0, _abi.STORE_F32)
+        out = _act(self._f32(memo, pre_name), op)
+        if op["fn"] == "ternary_tanh":
+            tstore, ternary_users = self._plan(name)
+            if TERNARY_T2 and ternary_users:
+                tstore = _abi.STORE_T2
+            if tstore is not None:
+                out = _Packed(_abi.pack(out, out.shape[-1], _abi.FN_GRID, 1, tstore), tstore, 1, out.shape)
+        return out
+
+    def _compute(self, memo, i, name):
+        op, s0 = self.spec[i], self.srcs[i][0]
+        kind = op["op"]
+        if kind == "act":
+            return self._activation(memo, i, name)
+        if kind == "bn":
+            cb = self._plan(name)
+            if cb is not None:
+                return self._conv_call(memo, cb[0], cb[1], None, 1.0, _abi.FN_NONE, 0, _abi.STORE_F32)
+            return _bn_apply(self._f32(memo, s0), *self.graph.bn[i])
+        if kind == "conv":
+            return self._conv_call(memo, i, None, None, 1.0, _abi.FN_NONE, 0, _abi.STORE_F32)
+        if kind == "add":
+            return _add(self._f32(memo, s0), self._f32(memo, self.srcs[i][1]))
+        if kind != "dense" and kind not in _GLUE:
+            raise ValueError(kind)
+        src = self._ev(memo, s0)
+        if isinstance(src, _Packed):         # the ops that read packed words as they are
+            if kind == "dense" and _wstore(op) is not None:
+                return _abi.dense(self.graph.weights(i, src.store), src.t, src.store, src.bits, src.shape[0])
+            if kind == "flatten" and src.shape[-1] % _abi.per_word(src.store) == 0:
+                return _Packed(src.t, src.store, src.bits, (src.shape[0], math.prod(src.shape[1:])))
+            if kind == "avgpool" and src.store != _abi.STORE_T2:     # window sums on the codes: no float32 copy
+                return _abi.avgpool_packed(src.t, src.store, src.bits, *src.shape, op.get("size", 8))
+        t = src.to_f32() if isinstance(src, _Packed) else src
+        if kind == "dense":
+            return _abi.dense(self.graph.weights(i, _abi.STORE_F32), t.contiguous(), _abi.STORE_F32, 0, t.shape[0])
+        out = _GLUE[kind](t, op)
+        if kind == "maxpool" and isinstance(src, _Packed) and src.store == _abi.STORE_T2:
+            # the maximum of ternary codes is a ternary code: stay on the bit planes for the next ternary layer
+            out = _Packed(_abi.pack(out.contiguous(), out.shape[-1], _abi.FN_GRID, 1, src.store), src.store, src.bits,
+                          out.shape)
+        return out
 
 
 class Pipelined:
@@ -1111,7 +1041,6 @@ class Pipelined:
         cur = torch.cuda.current_stream()
         direct = slots > 1 and isinstance(self.model, FusedModel) and not self.model.steps[-1]["softmax"]
         auto = self._auto(example)
-        model_flag = getattr(self.model, "_flag", None)
         for _ in range(self.nlanes):
             xs = torch.empty_like(example)
             xs.copy_(example)
@@ -1123,52 +1052,54 @@ class Pipelined:
             cur.wait_stream(side)
             lane = dict(stream=torch.cuda.Stream(), x=xs)
             if auto:
-                # "auto" first layer: every lane owns the domain-flag word its graphs write (the model's own word while
-                # the lane is captured); forward() copies it out per batch, bench.py reads it after its timed region
+                # "auto" first layer: every lane owns the domain-flag word its graphs write (the model's word while the
+                # lane is captured); forward() copies it out per batch, bench.py reads it after its timed region
                 lane["flag"] = torch.zeros(1, dtype=torch.int32, device=example.device)
-                self.model._flag = lane["flag"]
-            if slots == 1 and inputs > 1:
-                # `inputs` static input buffers per lane, one graph each: a replay loop that rotates them streams its
-                # images from HBM instead of re-reading one batch out of the 256 MB Infinity Cache (bench.py)
-                lane.update(xs=[xs] + [xs.clone() for _ in range(inputs - 1)], graphs=[], ys=[])
-                for xi in lane["xs"]:
-                    g = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(g):
-                        yi = self.model(xi)
-                    lane["graphs"].append(g)
-                    lane["ys"].append(yi)
-                lane.update(graph=lane["graphs"][0], y=lane["ys"][0])
-            elif slots == 1:
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
-                    ys = self.model(xs)
-                lane.update(graph=g, y=ys)
-            else:
-                # `slots` result slots per lane (a ring the caller hands to one collective per `slots` batches): one
-                # graph per slot whose last kernel writes straight into the slot -- or, for engines that cannot be told
-                # where to write, ONE graph plus a copy into the slot after every replay
-                B = y0.shape[0]
-                ring = torch.zeros((slots * B,) + tuple(y0.shape[1:]), dtype=y0.dtype, device=y0.device)
-                lane.update(ring=ring, direct=direct, graphs=[])
-                N, H, W, _ = example.shape
-                # `inputs` static input buffers: slot j's graph reads buffer j % inputs (HBM-streaming replays, as above)
-                lane["xs"] = [xs] + [xs.clone() for _ in range(min(inputs, slots if direct else 1) - 1)]
-                for j in range(slots if direct else 1):
-                    xi = lane["xs"][j % len(lane["xs"])]
-                    g = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(g):
-                        if direct:
-                            ys = self.model.forward_from(0, xi, N, H, W, out=ring[j * B:(j + 1) * B])
-                        else:
-                            ys = self.model(xi)
-                    lane["graphs"].append(g)
-                lane.update(graph=lane["graphs"][0], y=ys)
+            with self.model.flag_word(lane["flag"]) if auto else contextlib.nullcontext():
+                self._capture_lane(lane, xs, y0, example, slots, inputs, direct)
             lanes.append(lane)
-        if auto:
-            self.model._flag = model_flag
         torch.cuda.synchronize()
         self._lanes[key] = lanes
         return lanes
+
+    def _capture_lane(self, lane, xs, y0, example, slots, inputs, direct):
+        """Capture the graphs of one lane on its static input `xs` (y0: what the warm-up forward returned)."""
+        if slots == 1 and inputs > 1:
+            # `inputs` static input buffers per lane, one graph each: a replay loop that rotates them streams its
+            # images from HBM instead of re-reading one batch out of the 256 MB Infinity Cache (bench.py)
+            lane.update(xs=[xs] + [xs.clone() for _ in range(inputs - 1)], graphs=[], ys=[])
+            for xi in lane["xs"]:
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g):
+                    yi = self.model(xi)
+                lane["graphs"].append(g)
+                lane["ys"].append(yi)
+            lane.update(graph=lane["graphs"][0], y=lane["ys"][0])
+        elif slots == 1:
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                ys = self.model(xs)
+            lane.update(graph=g, y=ys)
+        else:
+            # `slots` result slots per lane (a ring the caller hands to one collective per `slots` batches): one
+            # graph per slot whose last kernel writes straight into the slot -- or, for engines that cannot be told
+            # where to write, ONE graph plus a copy into the slot after every replay
+            B = y0.shape[0]
+            ring = torch.zeros((slots * B,) + tuple(y0.shape[1:]), dtype=y0.dtype, device=y0.device)
+            lane.update(ring=ring, direct=direct, graphs=[])
+            N, H, W, _ = example.shape
+            # `inputs` static input buffers: slot j's graph reads buffer j % inputs (HBM-streaming replays, as above)
+            lane["xs"] = [xs] + [xs.clone() for _ in range(min(inputs, slots if direct else 1) - 1)]
+            for j in range(slots if direct else 1):
+                xi = lane["xs"][j % len(lane["xs"])]
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g):
+                    if direct:
+                        ys = self.model.forward_from(0, xi, N, H, W, out=ring[j * B:(j + 1) * B])
+                    else:
+                        ys = self.model(xi)
+                lane["graphs"].append(g)
+            lane.update(graph=lane["graphs"][0], y=ys)
 
     def lanes_for(self, example, slots=1, inputs=1):
         """The captured lanes for batches shaped like `example` (bench.py replays them directly).  slots > 1: every
@@ -1240,8 +1171,7 @@ class Pipelined:
             outs[i * B:(i + 1) * B] = self.model.forward_exact(x[i * B:(i + 1) * B])
 
     def forward(self, x):
-        u8 = isinstance(x, torch.Tensor) and x.dtype == torch.uint8
-        x = _abi.require_cuda_u8(x, "Pipelined.forward") if u8 else _abi.require_cuda(x, "Pipelined.forward")
+        x = _images(x, "Pipelined.forward")
         N = x.shape[0]
         B = min(self.batch_size, N)
         nfull = N // B if B else 0
@@ -1296,12 +1226,6 @@ class Pipelined:
         self._lanes.clear()
 
 
-def _ok_lowbit(op):
-    """Convs the fused epilogue path takes: low-bit weights (packed input) or the float-input
-    first layer; stock float convs stay on the float32 route."""
-    return op["op"] == "conv" and op["kind"] in ("binary", "quantized", "ternary") and op.get("nb", 1) <= 8
-
-
 # ---------------------------------------------------------------------------
 class LayerModel:
     """The spec instantiated as Keras-compatible layer objects, called one by one
@@ -1311,7 +1235,7 @@ class LayerModel:
         self.device = torch.device(device)
         self.spec = spec
         self.layers = {}
-        self._graph = GraphModel(spec, device)   # reuse name/consumer bookkeeping only
+        self.graph = _SpecGraph(spec, device)
         prev_act = {}
         for i, op in enumerate(spec):
             if op["op"] not in ("conv", "dense"):
@@ -1346,68 +1270,45 @@ class LayerModel:
             self.layers[i] = layer
         self.fuse_input_activation = fuse_input_activation
 
+
+    @staticmethod
+    def _grid(op):
+        """What a layer may assume about the values activation `op` hands it (layers/_base.py, input_domain)."""
+        if op["fn"] == "quantized_tanh":
+            return ("quantized", op["nb"]) if op["nb"] <= 8 else None
+        return {"binary_tanh": "binary", "ternary_tanh": ("quantized", 1)}.get(op["fn"])      # grid {-1,0,1}: value = code
+
     def forward(self, x, upto=None):
         """upto: index of a spec op whose output is returned instead of the network's (the intermediate model of
         test_resnet.py:70-72, `Model(inputs=model.input, outputs=model.get_layer(name).output)`)."""
         x = _abi.require_cuda(x, "LayerModel.forward")
-        g = self._graph
+        g = self.graph
         env = {"input": x}
         dom = {"input": None}     # what is known about each tensor's values
         for i, op in enumerate(self.spec):
-            name = g._names[i]
-            kind = op["op"]
+            kind, sname = op["op"], g.srcs[i][0]
+            src, d = env[sname], None
             if kind == "add":
-                y = env[op["a"]] + env[op["b"]]
-                d = None
-            else:
-                sname = op["src"] if "src" in op else (g._names[i - 1] if i > 0 else "input")
-                src = env[sname]
-                d = None
-                if kind in ("conv", "dense"):
-                    layer = self.layers[i]
-                    layer.input_domain = dom.get(sname) if self.fuse_input_activation else None
-                    y = layer(src)
-                elif kind == "bn":
-                    inv, shift = g._bn[i]
-                    y = src * inv + shift
-                elif kind == "act":
-                    if op["fn"] == "binary_tanh":
-                        y = binary_ops.binary_tanh(src); d = "binary"
-                    elif op["fn"] == "quantized_tanh":
-                        y = quantized_ops.quantized_tanh(src, op["nb"])
-                        d = ("quantized", op["nb"]) if op["nb"] <= 8 else None
-                    elif op["fn"] == "ternary_tanh":
-                        y = ternary_ops.ternary_tanh(src)
-                        d = ("quantized", 1)          # grid {-1,0,1}: value = code
-                    else:
-                        y = torch.where(src >= 0, src, src * F32(op.get("alpha", 0.3)))
-                elif kind == "maxpool":
-                    s = op.get("size", 2)
-                    N, H, W, C = src.shape
-                    y = src[:, :H // s * s, :W // s * s, :].reshape(N, H // s, s, W // s, s, C).amax(dim=(2, 4))
+                y = _add(src, env[op["b"]])
+            elif kind in ("conv", "dense"):
+                layer = self.layers[i]
+                layer.input_domain = dom.get(sname) if self.fuse_input_activation else None
+                y = layer(src)
+            elif kind == "bn":
+                y = _bn_apply(src, *g.bn[i])
+            elif kind in _GLUE:
+                y = _GLUE[kind](src, op)
+                if kind == "act":
+                    d = self._grid(op)
+                elif kind in ("maxpool", "flatten"):
                     d = dom.get(sname)      # max of grid values stays on the grid
-                elif kind == "avgpool":
-                    s = op.get("size", 8)
-                    N, H, W, C = src.shape
-                    win = src[:, :H // s * s, :W // s * s, :].reshape(N, H // s, s, W // s, s, C)
-                    y = win.double().sum(dim=(2, 4)).float() / F32(s * s)
-                elif kind == "zeropad":
-                    p = op["pad"]
-                    y = torch.nn.functional.pad(src, (0, 0, p, p, p, p))
-                elif kind == "flatten":
-                    y = src.reshape(src.shape[0], -1)
-                    d = dom.get(sname)
-                elif kind == "scale":
-                    y = src * F32(op["value"])
-                elif kind == "softmax":
-                    y = _abi.softmax(src)
-                else:
-                    raise ValueError(kind)
-            env[name] = y
-            dom[name] = d
+            else:
+                raise ValueError(kind)
+            env[g.names[i]] = y
+            dom[g.names[i]] = d
             if upto is not None and i == upto:
                 return y
-        return env[g._names[-1]]
+        return env[g.names[-1]]
 
     __call__ = forward
     predict = forward
