@@ -184,7 +184,8 @@ typedef struct qnn_epilogue {
  * under every combination; there is no process-wide switch (the library keeps no global state besides
  * qnn_set_conv_impl's family preference).
  *   QNN_EPI_NO_STRIP     3x3 stride-1 / -2 int4 layers with 16 / 32 / 64 channels: not the row-walking strip kernels
- *                        (the tile kernels take them)
+ *                        (the tile kernels take them); the same layers with int8-stored operands and an un-pooled int8
+ *                        output: not the int8 strip kernels (k_conv_ps / the tiled int8 kernels take them, as before)
  *   QNN_EPI_NO_STRIP64   only the 64-channel layers leave the strip kernel (the LDS-weight kernel takes them)
  *   QNN_EPI_NO_HALO      pooled int4 layers with 64 input channels: per-tap operand fetch (k_conv_mfma_areg) instead of
  *                        the receptive field staged once through LDS (k_conv_mfma_halo)

@@ -802,7 +802,11 @@ int qnn_mfma_prepare_weights(qnn_weights* w, hipStream_t s) {
     // runs such a layer on its own
     const bool proj = w->store == QNN_STORE_I4 && (w->cin == 16 || w->cin == 32) && w->cout == 2 * w->cin &&
                       w->kh == 1 && w->kw == 1 && w->stride == 2;
-    if (!small && !proj && (w->cin % 64 != 0 || w->cout % 64 != 0)) return QNN_OK;
+    // int8-stored 3x3 layers with 16 / 32 input channels: the int8 strip kernels (qnn_mfma_strip_i8.hip) read the codes
+    // as they are packed
+    const bool small8 = w->store == QNN_STORE_I8 && (w->cin == 16 || w->cin == 32) && (w->cout % 16) == 0 &&
+                        w->kh == 3 && w->kw == 3;
+    if (!small && !small8 && !proj && (w->cin % 64 != 0 || w->cout % 64 != 0)) return QNN_OK;
     if (w->store == QNN_STORE_I8) {
         w->d_mfma = (uint8_t*)w->d_packed;      // int8 codes, natural channel order
         return QNN_OK;
@@ -850,12 +854,49 @@ int qnn_route_first_f32(const ConvCall& c, char* name, size_t name_len) {
     return qnn_launch_first(g.cin, 4, g, e, c.x, c.w->d_wq, c.y, c.s);
 }
 
-// 3x3 int4 layers with 16 / 32 / 64 input channels: the row-walking strip kernels, then the small-channel tile kernel
+// int8-stored activations and weights, 3x3, 16 / 32 (/ 64) input channels, un-pooled int8 output: the int8 row-walking
+// strip kernels (qnn_mfma_strip_i8.hip).  Everything else with int8 operands stays where it was: pooled layers and
+// Cin = 64 on the tiled family (qnn_route_gemm), float32 or int4 outputs and 16 / 32 channels on k_conv_ps.
+static int route_strip_i8(const ConvCall& c, char* name, size_t name_len) {
+    const ConvGeom& g = c.g;
+    const EpiArgs& e = c.e;
+    const qnn_weights* w = c.w;
+    if (w->store != QNN_STORE_I8 || (e.flags & QNN_EPI_NO_STRIP) || e.fold_a || e.proj_x) return 1;
+    int pexp = 0;
+    // the residual's post-scale (models/resnet.py:128: 0.5) folds into the activation's code scale: a power of two
+    const bool pow2 = !e.res || (e.post_scale > 0.0f && frexpf(e.post_scale, &pexp) == 0.5f);
+    const int cmul = g.cin == 16 ? 16 : 32;
+    const bool s1 = g.stride == 1 && g.pt == 1 && g.pl == 1 && (g.cin == 16 || g.cin == 32 || g.cin == 64) &&
+                    (g.cout % cmul) == 0;
+    const bool s2 = g.stride == 2 && (g.cin == 16 || g.cin == 32) && (g.cout % 32) == 0 && !e.res;
+    // Accumulator bound: K = 9 * Cin <= 576 products of two codes in [-128, 127]: |acc| <= 576 * 128 * 128 = 9 437 184
+    // < 2^24, so the kernels' int -> float32 conversion is exact (as the reference's float32 sum of the same products).
+    static_assert(576L * 128 * 128 < (1L << 24), "int8 strip kernels: accumulators must convert to float32 exactly");
+    const bool shape = g.kh == 3 && g.kw == 3 && (s1 || s2) && g.pool == 1 && e.out_store == QNN_STORE_I8 && pow2 &&
+                       (!e.res || (e.res_store == QNN_STORE_I8 && e.res_cw == e.ocw) ||
+                        (e.res_store == QNN_STORE_F32 && e.res_cw == g.cout));
+    // Cin 64 has a matrix-pipe kernel already (mfma_i8_areg64x64 for Cout = 64): QNN_EPI_NO_STRIP64 keeps it (the A/B
+    // switch, as on the int4 path); the two times are in DESIGN 3.2
+    const bool want = g.cin != 64 || !(e.flags & QNN_EPI_NO_STRIP64);
+    if (!shape || !want) return 1;
+    MfmaGeom ms;
+    ms.g = g; ms.kc = 1; ms.steps = 0; ms.x_pix_bytes = g.cin;
+    ms.total_q = (long)g.N * g.Ho * g.Wo;
+    const double wb_ = (double)g.cout * 9 * g.cin;
+    if (wb_ >= 2.0e9) return 1;
+    ms.x_bytes = 0; ms.w_bytes = (uint32_t)wb_; ms.ablate = 0;
+    snprintf(name, name_len, g.stride == 2 ? "strip_i8_c%d_s2" : "strip_i8_c%d", g.cin);
+    return qnn_launch_strip_i8(g.cin, ms, e, c.x, w->d_mfma, c.y, c.s);
+}
+
+// 3x3 layers with 16 / 32 / 64 input channels: the row-walking strip kernels (int4, int8), then the small-channel tile kernel
 int qnn_route_strip(const ConvCall& c, char* name, size_t name_len) {
     const ConvGeom& g = c.g;
     const EpiArgs& e = c.e;
     const qnn_weights* w = c.w;
-    if (!w->d_mfma || c.x_store != QNN_STORE_I4) return 1;
+    if (!w->d_mfma) return 1;
+    if (c.x_store == QNN_STORE_I8) return route_strip_i8(c, name, name_len);
+    if (c.x_store != QNN_STORE_I4) return 1;
     static const bool small_off = QNN_ENV_STR("QNN_MFMA_SMALL_OFF") != nullptr;   // A/B switch (experiment builds only)
     // 3x3 stride-1 int4 layers with 16 / 32 / 64 input channels: row-walking strip kernel (qnn_mfma_strip.hip).
     // The residual's post-scale (models/resnet.py:128: 0.5) must be a power of two so that it folds exactly into the

@@ -281,4 +281,7 @@ int qnn_launch_small(int cin, const MfmaGeom& mg, const EpiArgs& e, const void* 
                      void* y, hipStream_t s);
 int qnn_launch_strip(int cin, const MfmaGeom& mg, const EpiArgs& e, const void* x, const uint8_t* w,
                      void* y, hipStream_t s);
+// the int8-stored form (qnn_mfma_strip_i8.hip): w = the int8 codes [cout][9][cin]
+int qnn_launch_strip_i8(int cin, const MfmaGeom& mg, const EpiArgs& e, const void* x, const uint8_t* w,
+                        void* y, hipStream_t s);
 int qnn_launch_strip16_lds(const MfmaGeom& mg, const EpiArgs& e, const void* x, const uint8_t* w, void* y, hipStream_t s);

@@ -1,6 +1,7 @@
 // 3x3 stride-1 int4 layers with 16 or 32 channels (the 224x224 and 112x112 stages of the ImageNet ResNet,
 // models/resnet.py:104-129) as a ROW-WALKING kernel on v_mfma_i32_16x16x64_i8.
-// Dispatch: qnn_route_strip (qnn_mfma.hip).
+// Dispatch: qnn_route_strip (qnn_mfma.hip).  The same layers with int8-STORED activations and weights (the 8-bit
+// ResNets) run on the int8 form of this walk, qnn_mfma_strip_i8.hip: no widening, 16-byte operand loads, byte epilogue.
 //
 // These layers are bound by instruction issue, not by the matrix pipe (16 x 16 outputs need 3 or 12 MFMAs of 16
 // cycles) and not by HBM: QuantizedConv2D.call (quantized_layers.py:164-194) + BN + residual merge + quantized_tanh
