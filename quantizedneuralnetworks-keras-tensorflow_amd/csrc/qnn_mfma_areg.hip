@@ -784,9 +784,10 @@ __global__ __launch_bounds__(256, (OUT == QNN_STORE_F32 ? 2 : 3)) void k_conv_mf
 // 64 channels of a tap in ONE instruction at the cycles of the int8 one (9 x 4 MFMAs per tile instead of 18 x 4).  An
 // activation code c is staged as u = c + 8 in [0, 15] (the nibble XOR 8; a padding zero becomes u = 8), whose zero-extended
 // 6-bit pattern is the e2m3 code of u / 8; a weight w in [-8, 7] is the sign-magnitude code of w / 8.  Every product is
-// the integer u w, every partial sum stays below 2^17 in magnitude, so the float32 accumulators hold the exact integer
-// S + 8 sum(w) (S = the int8 kernel's sum of codes); the pooled value becomes 256 S (+ the fold's offset) -- the int8
-// kernel's accumulator -- in one conversion and one shift-add, after which the epilogue is the int8 one, bit for bit.
+// the integer u w, every partial sum stays below 2^17 in magnitude, so the float32 accumulators, started from 1.5 * 2^23,
+// hold the exact integer S + 8 sum(w) on top of it (S = the int8 kernel's sum of codes) and their bit patterns are integers
+// that order like the sums: the window is pooled with integer maxima and the pooled pattern becomes 256 S (+ the fold's
+// offset) -- the int8 kernel's accumulator -- in one shift-add, after which the epilogue is the int8 one, bit for bit.
 // Region: plane A = dwords 0-3 of a pixel's two 32-channel halves (the int8 plane's geometry and swizzle), plane B =
 // their dwords 4-5 ([row][pixel][2 eight-byte slots], slot = lane half XOR (row & 1): a ds_read_b64 group of 32 lanes
 // covers 16 pixels on two rows of different parity (TWP 8) or 4 x 8 pixels on rows whose 16-byte columns pair up with
@@ -868,10 +869,19 @@ __global__ __launch_bounds__(NW * 64, 1) void k_conv_mfma_halo(MfmaGeom mg, EpiA
             fda[b] = e.fold_a[c]; fdc[b] = e.fold_c[c]; fdb[b] = e.fold_b[c];
         }
     }
-    // FP6: the accumulators hold S + 8 sum(w); 256 S + offset = 256 * acc + (offset - 2048 sum(w))
+    // FP6: the accumulators start from 1.5 * 2^23 and hold the exact integer S + 8 sum(w) on top of it (every partial sum is
+    // below 2^17 in magnitude, so the float stays in [2^23, 2^24) where its ulp is 1): the BIT PATTERN is the integer
+    // SEED_BITS + S + 8 sum(w), which orders like the value.  256 S + offset = (bits << 8) + (offset - 2048 sum(w) -
+    // (SEED_BITS << 8)), all modulo 2^32
+    constexpr uint32_t SEED_BITS = 0x4B400000u;        // 1.5 * 2^23
+    v16f seed6 = {};
     if constexpr (FP6) {
 #pragma unroll
-        for (int b = 0; b < 2; ++b) fdb[b] = (int)((uint32_t)fdb[b] - 2048u * (uint32_t)wsum[nbase + b * 32 + li]);
+        for (int b = 0; b < 2; ++b)
+            fdb[b] = (int)((uint32_t)fdb[b] - 2048u * (uint32_t)wsum[nbase + b * 32 + li] - (SEED_BITS << 8));
+        const float sv = __builtin_bit_cast(float, SEED_BITS);
+        seed6 = v16f{sv, sv, sv, sv, sv, sv, sv, sv, sv, sv, sv, sv, sv, sv, sv, sv};
+        asm volatile("" : "+v"(seed6));                // sixteen registers kept for the whole kernel, not sixteen moves per tile
     }
     int hu = 0;
     float hbias = 0.0f, hinv = 1.0f, hshift = 0.0f;
@@ -920,7 +930,12 @@ __global__ __launch_bounds__(NW * 64, 1) void k_conv_mfma_halo(MfmaGeom mg, EpiA
     int fb_addr[2];
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk) fb_addr[kk] = li * 64 + (((lh * 2 + kk) ^ ((li >> 2) & 3)) << 4);
-    const int fb6a = li * 32 + ((lh ^ ((li >> 3) & 1)) << 4), fb6b = WB6 + li * 16 + ((lh ^ ((li >> 4) & 1)) << 3);
+    const int fb6a = li * 32 + ((lh ^ ((li >> 3) & 1)) << 4);
+    // plane B of the two filter halves off two base registers the compiler cannot relate: reads off one base are merged into
+    // ds_read2st64_b64, whose four result registers then have to be copied into the two six-register operand tuples
+    int fb6b[2] = {WB6 + li * 16 + ((lh ^ ((li >> 4) & 1)) << 3), 0};
+    fb6b[1] = fb6b[0] + 512;
+    if constexpr (FP6) asm volatile("" : "+v"(fb6b[1]));
 
     const int t_stride = gridDim.x * NW;
     int t = blockIdx.x * NW + wave;
@@ -950,20 +965,26 @@ __global__ __launch_bounds__(NW * 64, 1) void k_conv_mfma_halo(MfmaGeom mg, EpiA
     };
     auto stage = [&]() {
         if constexpr (FP6) {
-            // 32 codes -> 32 six-bit fields (qnn_fp6_channel): XOR 8, then per pair of words one rotate each and
-            // two AND(-OR)s per output word; 24 bytes per chunk
+            // 32 codes -> 32 six-bit fields (qnn_fp6_channel) of code XOR 8: per pair of words one rotate each and two
+            // v_bitop3_b32 per output word, (x & M1) ^ K then ^ (x' & M2).  The XOR commutes with the rotate and the two
+            // masks are disjoint, so K = (8s & M1) | (rot(8s) & M2) carries the XOR bits of both parts; 24 bytes per chunk
             auto grp = [](uint32_t x0, uint32_t y0, uint32_t& d0, uint32_t& d1, uint32_t& d2) {
+                constexpr uint32_t E = 0x88888888u, ER = 0x22222222u;      // the XOR 8 of eight codes, and rotated left by two
+                constexpr uint32_t AND_XOR = 0x6A;                         // v_bitop3_b32 truth table of (a & b) ^ c
                 const uint32_t xr = __builtin_amdgcn_alignbit(x0, x0, 30), yr = __builtin_amdgcn_alignbit(y0, y0, 30);
-                d0 = (x0 & 0x0F00F00Fu) | (xr & 0xC03C03C0u);
-                d1 = (xr & 0x03C03C03u) | (y0 & 0xF00F00F0u);
-                d2 = (y0 & 0x00F00F00u) | (yr & 0x3C03C03Cu);
+                d0 = __builtin_amdgcn_bitop3_b32(x0, 0x0F00F00Fu, (E & 0x0F00F00Fu) | (ER & 0xC03C03C0u), AND_XOR);
+                d0 = __builtin_amdgcn_bitop3_b32(xr, 0xC03C03C0u, d0, AND_XOR);
+                d1 = __builtin_amdgcn_bitop3_b32(xr, 0x03C03C03u, (ER & 0x03C03C03u) | (E & 0xF00F00F0u), AND_XOR);
+                d1 = __builtin_amdgcn_bitop3_b32(y0, 0xF00F00F0u, d1, AND_XOR);
+                d2 = __builtin_amdgcn_bitop3_b32(y0, 0x00F00F00u, (E & 0x00F00F00u) | (ER & 0x3C03C03Cu), AND_XOR);
+                d2 = __builtin_amdgcn_bitop3_b32(yr, 0x3C03C03Cu, d2, AND_XOR);
             };
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const uint4 q = L[i];
                 uint32_t d[6];
-                grp(q.x ^ 0x88888888u, q.y ^ 0x88888888u, d[0], d[1], d[2]);
-                grp(q.z ^ 0x88888888u, q.w ^ 0x88888888u, d[3], d[4], d[5]);
+                grp(q.x, q.y, d[0], d[1], d[2]);
+                grp(q.z, q.w, d[3], d[4], d[5]);
                 if (i < 3 || wr_ok[i]) {
                     *reinterpret_cast<uint4*>(smem + wr_addr[i]) = make_uint4(d[0], d[1], d[2], d[3]);
                     *reinterpret_cast<uint2*>(smem + wrb_addr[i]) = make_uint2(d[4], d[5]);
@@ -988,7 +1009,12 @@ __global__ __launch_bounds__(NW * 64, 1) void k_conv_mfma_halo(MfmaGeom mg, EpiA
     auto bn = [&](int v, const FoldEpi& f) {
         return __fadd_rn(__fmul_rn(__fadd_rn((float)v, f.nb), f.ninv), f.nshift);
     };
-    auto epilogue = [&](long pq0, int image) {
+    // ALLPOS: every BN scale of this wave's two filter halves is >= 0, so the 2x2 window is pooled by its maximum alone;
+    // otherwise maximum and minimum are both formed and a channel takes the one its sign asks for.  The caller branches on
+    // the wave-uniform all_pos around the whole epilogue (one lambda with a run-time test is if-converted: max, min and a
+    // select per value on every path).
+    auto epilogue = [&](auto allpos, long pq0, int image) {
+        constexpr bool ALLPOS = decltype(allpos)::value;
         uint32_t* ytile = reinterpret_cast<uint32_t*>(y) + pq0 * e.ocw;
         int dacc[16];
         if constexpr (HEAD) {
@@ -1003,25 +1029,23 @@ __global__ __launch_bounds__(NW * 64, 1) void k_conv_mfma_halo(MfmaGeom mg, EpiA
             for (int a = 0; a < 2; ++a)
 #pragma unroll
                 for (int g4 = 0; g4 < 4; ++g4) {
-                    if constexpr (FP6) {                 // exact integers: the float order is the integer order
+                    int i0, i1, i2, i3;
+                    if constexpr (FP6) {                 // seeded accumulators: the bit patterns order like the sums
                         const float f0 = acc6[a][b][4 * g4], f1 = acc6[a][b][4 * g4 + 1];
                         const float f2 = acc6[a][b][4 * g4 + 2], f3 = acc6[a][b][4 * g4 + 3];
-                        float pf = fmaxf(fmaxf(f0, f1), fmaxf(f2, f3));
-                        if (!all_pos) {
-                            const float mn = fminf(fminf(f0, f1), fminf(f2, f3));
-                            pf = ke[b].neg ? mn : pf;
-                        }
-                        // 256 S + the fold's offset: the int8 kernel's pooled accumulator
-                        pv[a * 4 + g4] = (int)(((uint32_t)(int)pf << 8) + (uint32_t)fdb[b]);
-                        continue;
+                        i0 = __float_as_int(f0); i1 = __float_as_int(f1); i2 = __float_as_int(f2); i3 = __float_as_int(f3);
+                    } else {
+                        i0 = acc[a][b][4 * g4]; i1 = acc[a][b][4 * g4 + 1];
+                        i2 = acc[a][b][4 * g4 + 2]; i3 = acc[a][b][4 * g4 + 3];
                     }
-                    const int i0 = acc[a][b][4 * g4], i1 = acc[a][b][4 * g4 + 1];
-                    const int i2 = acc[a][b][4 * g4 + 2], i3 = acc[a][b][4 * g4 + 3];
-                    const int mx = max(max(i0, i1), max(i2, i3));
-                    int pooled = mx;
-                    if (!all_pos) {
+                    int pooled = max(max(i0, i1), max(i2, i3));
+                    if constexpr (!ALLPOS) {
                         const int mn = min(min(i0, i1), min(i2, i3));
-                        pooled = ke[b].neg ? mn : mx;
+                        pooled = ke[b].neg ? mn : pooled;
+                    }
+                    if constexpr (FP6) {                 // 256 S + the fold's offset: the int8 kernel's pooled accumulator
+                        pv[a * 4 + g4] = (int)(((uint32_t)pooled << 8) + (uint32_t)fdb[b]);
+                        continue;
                     }
                     if constexpr (FOLD) pv[a * 4 + g4] = pooled;
                     else tv[a * 4 + g4] = bn(pooled, fe[b]);
@@ -1073,16 +1097,17 @@ __global__ __launch_bounds__(NW * 64, 1) void k_conv_mfma_halo(MfmaGeom mg, EpiA
                 for (int mt = 0; mt < 2; ++mt) {
                     const v4i lo = *reinterpret_cast<const v4i*>(smem + (dy == 1 ? a_odd[mt] : a_even[mt]) + dy * PITCH + dx * 32);
                     const v2i hi = *reinterpret_cast<const v2i*>(smem + (dy == 1 ? ab_odd[mt] : ab_even[mt]) + dy * PITCHB + dx * 16);
-                    A[mt] = v8i{lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, 0, 0};
+                    A[mt] = v8i{lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, 0, 0};  // (the e2m3 instruction reads six registers)
                 }
 #pragma unroll
                 for (int b = 0; b < 2; ++b) {
                     const v4i lo = *reinterpret_cast<const v4i*>(smem + fb6a + tap * 2048 + b * 1024);
-                    const v2i hi = *reinterpret_cast<const v2i*>(smem + fb6b + tap * 1024 + b * 512);
+                    const v2i hi = *reinterpret_cast<const v2i*>(smem + fb6b[b] + tap * 1024);
                     B[b] = v8i{lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, 0, 0};
                 }
             };
             frags(0, fa[0], fb[0]);
+            __builtin_amdgcn_sched_barrier(0);             // (keeps the reads of taps 0 and 1 from being merged into ds_read2)
 #pragma unroll
             for (int st = 0; st < 9; ++st) {
                 if (st + 1 < 9) frags(st + 1, fa[(st + 1) & 1], fb[(st + 1) & 1]);
@@ -1092,15 +1117,15 @@ __global__ __launch_bounds__(NW * 64, 1) void k_conv_mfma_halo(MfmaGeom mg, EpiA
                 for (int a = 0; a < 2; ++a)
 #pragma unroll
                     for (int b = 0; b < 2; ++b) {
-                        const v16f c0 = {};
                         // formats 2 / 2 = e2m3 x e2m3, E8M0 scales 130 = 2^3 on both operands
                         acc6[a][b] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(fa[st & 1][a], fb[st & 1][b],
-                                                                                     st == 0 ? c0 : acc6[a][b], 2, 2, 0, 130, 0, 130);
+                                                                                     st == 0 ? seed6 : acc6[a][b], 2, 2, 0, 130, 0, 130);
                     }
                 __builtin_amdgcn_s_setprio(0);
                 __builtin_amdgcn_sched_barrier(0);
             }
-            epilogue(pq0, image);
+            if (all_pos) epilogue(BoolTag<true>{}, pq0, image);
+            else epilogue(BoolTag<false>{}, pq0, image);
             continue;
         }
         // 18 K-steps (tap, kk); the fragments of step s + 1 are requested before the MFMAs of step s are issued (two register
@@ -1138,7 +1163,8 @@ __global__ __launch_bounds__(NW * 64, 1) void k_conv_mfma_halo(MfmaGeom mg, EpiA
             __builtin_amdgcn_s_setprio(0);
             __builtin_amdgcn_sched_barrier(0);
         }
-        epilogue(pq0, image);
+        if (all_pos) epilogue(BoolTag<true>{}, pq0, image);
+        else epilogue(BoolTag<false>{}, pq0, image);
     }
 }
 

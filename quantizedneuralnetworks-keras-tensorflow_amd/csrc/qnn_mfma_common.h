@@ -30,6 +30,12 @@ typedef int v2i __attribute__((ext_vector_type(2)));
 typedef int v8i __attribute__((ext_vector_type(8)));
 typedef float v16f __attribute__((ext_vector_type(16)));
 
+// a compile-time flag as an argument: selects one instantiation of a generic lambda under a wave-uniform run-time branch
+template <bool B>
+struct BoolTag {
+    static constexpr bool value = B;
+};
+
 // (outside the anonymous namespace: it appears in the signatures of the cross-TU launchers below)
 struct MfmaGeom {
     ConvGeom g;
