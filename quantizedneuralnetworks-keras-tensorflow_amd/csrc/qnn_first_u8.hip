@@ -34,15 +34,37 @@ constexpr int kWaveLdsU = kRingU + 4;          // words per wave (a multiple of 
 // domain flag otherwise (qnn_weights_check), exactly like the fixed-point variant.  An accepted x is within 1.5e-7 of
 // k/255, so the result is within 27 * 1.5e-7 + one rounding of the real convolution of the floats: inside the 1e-5
 // contract for anything the check lets through, and the typed entry's exact result for real images.
-// Five instructions per element: t + 2^23 rounds t to an integer k (ties to even, as rint) and leaves k in the low bits of
-// the sum; the distance is taken to k CLAMPED to [0, 255], so an integer outside the byte range fails the same test as
-// a fraction does (NaN and infinities fail it too: every comparison with NaN is false).
-__device__ __forceinline__ uint32_t image_byte(float x, bool& bad) {
-    const float t = __fmul_rn(x, 255.0f);
-    const float u = __fadd_rn(t, 8388608.0f);
-    const float r = __builtin_amdgcn_fmed3f(__fsub_rn(u, 8388608.0f), 0.0f, 255.0f);
-    bad |= !(fabsf(__fsub_rn(t, r)) <= 0x1p-15f);
-    return __float_as_uint(u);                      // low byte = k for every accepted x; only that byte is stored
+// Per element: t = 255 x (v_mul_f32, kept out of the packed-float form: v_pk_mul_f32 costs more than two plain
+// multiplies beside MFMAs), u = t + 2^23 (rounds t to an integer k, ties to even as rint, and leaves k in the low bits of
+// the sum), r0 = u - 2^23, z = bits(u) ^ 0x4B000080, d = t - r0.  The low byte of z is the signed byte the LDS takes
+// (k ^ 0x80).  Nothing is decided per element: the lane keeps two running accumulators, orbits |= z and
+// err = max(err, |d|), and the kernel tests them once at its end,  bad = (orbits & ~0xFF) != 0 || !(err <= 2^-15).
+// That accepts and rejects exactly what the test against k clamped to [0, 255] did (|t - med3(r0, 0, 255)| <= 2^-15):
+//   * bits 8..31 of z are zero exactly when u is one of the floats 2^23 + k, k = 0..255.  Then r0 = k, the clamp was
+//     the identity, and both tests compare the same |t - k| with 2^-15 (a maximum over elements exceeds the bound
+//     exactly when one element does; d is never NaN here).
+//   * otherwise the bit test rejects, and so did the old test: u = NaN or +-inf has t = NaN or +-inf, whose distance
+//     to any clamped value is NaN or inf; a finite u >= 2^23 + 256 needs t >= 255.5, at least 0.5 from the clamp's
+//     255; a finite u < 2^23 needs t < -0.25 (2^23 - 0.25 is the tie, and it rounds to the even 2^23), more than 0.25
+//     from the clamp's 0.  What v_max_f32 does with a NaN d is therefore irrelevant: its element already failed the
+//     bit test.
+struct ImageDomain {
+    uint32_t orbits = 0u;
+    float err = 0.0f;
+    __device__ __forceinline__ bool bad() const { return (orbits & ~0xFFu) != 0u || !(err <= 0x1p-15f); }
+};
+// two staged elements at once: one v_or3_b32 and one v_max3_f32 serve both
+__device__ __forceinline__ void image_bytes2(uint32_t& b0, uint32_t& b1, ImageDomain& dom) {
+    float t0, t1, u0, u1;                        // (asm: the compiler pairs these into v_pk_mul_f32 / v_pk_add_f32)
+    asm("v_mul_f32 %0, 0x437f0000, %1" : "=v"(t0) : "v"(__uint_as_float(b0)));
+    asm("v_mul_f32 %0, 0x437f0000, %1" : "=v"(t1) : "v"(__uint_as_float(b1)));
+    asm("v_add_f32 %0, 0x4b000000, %1" : "=v"(u0) : "v"(t0));
+    asm("v_add_f32 %0, 0x4b000000, %1" : "=v"(u1) : "v"(t1));
+    const float d0 = __fsub_rn(t0, __fsub_rn(u0, 8388608.0f)), d1 = __fsub_rn(t1, __fsub_rn(u1, 8388608.0f));
+    b0 = __float_as_uint(u0) ^ 0x4B000080u;
+    b1 = __float_as_uint(u1) ^ 0x4B000080u;
+    dom.orbits |= b0 | b1;
+    dom.err = fmaxf(fmaxf(dom.err, fabsf(d0)), fabsf(d1));
 }
 
 // (QNN_STORE_I4, 2, BIN): the fused pipeline, quantized_tanh / binary_tanh codes;  (QNN_STORE_F32, 1, false): the layer
@@ -66,9 +88,13 @@ __global__ __launch_bounds__(256, 4) void k_conv_first_u8(ConvGeom g, EpiArgs e,
     uint4* tab = reinterpret_cast<uint4*>(smem_u8 + 4 * kWaveLdsU * 4);      // [filter block][lane][2]
     for (int i = lane; i < kWaveLdsU; i += 64) lds[i] = 0x80808080u;        // code 0 everywhere; the constant block
 
-    // ---- filters: B operand of block nt = filter nt*16 + r, K-block kq.  Wave nt prepares block nt for the workgroup ----
+    // ---- filters: B operand of block nt, column r, K-block kq.  Wave nt prepares block nt for the workgroup.
+    // The pooled int4 forms DEAL the filters: column r of block nt is channel 4 r + nt, so the four blocks of a lane are
+    // four consecutive channels of one pooled pixel = one 16-bit half of an output word, already in the order the
+    // packing leaves them -- no transpose across lanes (the strip kernels' deal, qnn_mfma_strip.hip).  Everything
+    // per-channel below (codes, the negation, A / B, the fold's A2 / C2) follows c. ----
     {
-        const int c = wave * 16 + r;
+        const int c = POOL == 2 ? 4 * r + wave : wave * 16 + r;
         const float bias = e.bias ? e.bias[c] : 0.0f;
         const float inv = e.bn_inv ? e.bn_inv[c] : 1.0f;
         const float shift = e.bn_inv ? e.bn_shift[c] : 0.0f;
@@ -114,11 +140,14 @@ __global__ __launch_bounds__(256, 4) void k_conv_first_u8(ConvGeom g, EpiArgs e,
         bw[nt] = __builtin_bit_cast(v4i, t0);
         fa[nt] = __uint_as_float(t1.x); fb[nt] = __uint_as_float(t1.y);
     }
-    LaneEpi ke;
-    lane_epi_init<QNN_STORE_I4>(ke, e, r, r);
     constexpr int kMagicBits = 0x4B400008;                       // 1.5 * 2^23 + 8: see qnn_mfma_strip.hip
     const float magic = __int_as_float(kMagicBits);
     const int code_lo = kMagicBits - (int)e.act_m, code_hi = kMagicBits + (int)e.act_m - 1;
+    // A lane's packed word P holds its four channels of tile 0 in the low half and of tile 1 in the high half.  Lanes r
+    // and r ^ 1 hold the two halves of the same output words: one DPP exchange and one v_perm_b32 leave the even lane
+    // with the whole word of tile 0 and the odd lane with that of tile 1.
+    const uint32_t sel_join = (r & 1) ? 0x03020706u : 0x05040100u;
+    auto join_tiles = [&](uint32_t P) { return __builtin_amdgcn_perm(dpp_xor1(P), P, sel_join); };
     // ---- operand addresses (dword index): position m = r: window w = r >> 2, (py, px) = bits of r.  A step works on
     // conv rows yy0 = 2*rp and yy0 + 1; with rp0 even the ring slot of input row yy0 + py + dy - 1 is
     // (2*(rp & 1) + py + kq) & 3.  K-block 3 reads the constant block for every tile ----
@@ -137,7 +166,7 @@ __global__ __launch_bounds__(256, 4) void k_conv_first_u8(ConvGeom g, EpiArgs e,
     const int st1 = e1ok ? kRowPitchU * 4 + e1px * 4 + e1ch : kRowPitchU * 4 + 30 * 4;     // pixel 30 of a row is never read
     constexpr int EB = F32IN ? 4 : 1;                            // bytes per input element
     const int rowb = g.W * 3 * EB;                               // bytes per input row
-    bool bad = false;                                            // F32IN: this lane staged a value off the byte grid
+    ImageDomain dom;                                             // F32IN: what this lane staged, tested once at the end
 
     for (int task = wid; task < ntasks; task += nw) {
         const uint32_t rest = qnn_div((uint32_t)task, fd_nch);
@@ -153,7 +182,8 @@ __global__ __launch_bounds__(256, 4) void k_conv_first_u8(ConvGeom g, EpiArgs e,
         // goes into the scalar offset of the store -- no per-step address arithmetic on the vector unit
         const __amdgpu_buffer_rsrc_t yr = __builtin_amdgcn_make_buffer_rsrc(
             reinterpret_cast<uint32_t*>(y) + (size_t)n * g.Hp * g.Wp * e.ocw, 0, g.Hp * g.Wp * e.ocw * 4, 0x00020000);
-        const int ylane = (((xs >> 1) + kq + 4 * ((r & 7) >> 2)) * e.ocw + (r & 3) * 2 + (r >> 3)) * 4;
+        // (after join_tiles lane r holds word r >> 1 = channels 8 (r >> 1) .. + 7 of window kq in tile r & 1)
+        const int ylane = (((xs >> 1) + kq + 4 * (r & 1)) * e.ocw + (r >> 1)) * 4;
         const int yrow = g.Wp * e.ocw * 4;
         const int c0col = xs - 1 + e0px, c1col = xs - 1 + e1px;
         const int v0 = (c0col >= 0 && c0col < g.W) ? (c0col * 3 + e0ch) * EB + e0row * rowb : (int)0x80000000;
@@ -170,12 +200,10 @@ __global__ __launch_bounds__(256, 4) void k_conv_first_u8(ConvGeom g, EpiArgs e,
         };
         auto stage_write = [&](auto slotc, uint32_t b0, uint32_t b1) {   // into the ring slots SLOT, SLOT + 1
             constexpr int SB = decltype(slotc)::value * (kRowPitchU * 4);
-            if constexpr (F32IN) {
-                b0 = image_byte(__uint_as_float(b0), bad);
-                b1 = image_byte(__uint_as_float(b1), bad);
-            }
-            ldsb[st0 + SB] = (uint8_t)(b0 ^ 0x80u);
-            ldsb[st1 + SB] = (uint8_t)(b1 ^ 0x80u);
+            if constexpr (F32IN) image_bytes2(b0, b1, dom);      // the low bytes come back as signed bytes
+            else { b0 ^= 0x80u; b1 ^= 0x80u; }
+            ldsb[st0 + SB] = (uint8_t)b0;
+            ldsb[st1 + SB] = (uint8_t)b1;
         };
         const int yy_first = 2 * rp0;
         uint32_t fa0, fa1, fb0, fb1, fc0, fc1;
@@ -239,10 +267,9 @@ __global__ __launch_bounds__(256, 4) void k_conv_first_u8(ConvGeom g, EpiArgs e,
                 const uint32_t uo = __builtin_amdgcn_perm(tp[3], tp[1], 0x07030501u);
                 const uint32_t ue = __builtin_amdgcn_perm(tp[2], tp[0], 0x07030501u);
                 const uint32_t P = (uo & 0xF0F0F0F0u) | ((ue >> 4) & 0x0F0F0F0Fu);      // nibble j = code of value j
-                __builtin_amdgcn_raw_buffer_store_b32(transpose_nib8(P, ke), yr, ylane, rp * yrow, 0);
+                __builtin_amdgcn_raw_buffer_store_b32(join_tiles(P), yr, ylane, rp * yrow, 0);
             } else if constexpr (OUT == QNN_STORE_I4) {
-                // lane (filter r, window kq): value j = 4*t + nt -> after the transpose lane (r & 7) holds the word of
-                // value j = r & 7: pooled pixel (xs/2 + kq + 4*(j >> 2)), channels (j & 3)*16 + (r & 8) .. +7
+                // lane (column r, window kq): value j = 4*t + nt = channel 4 r + nt of pooled pixel xs/2 + kq + 4 t
                 int cb[8];
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
@@ -260,7 +287,7 @@ __global__ __launch_bounds__(256, 4) void k_conv_first_u8(ConvGeom g, EpiArgs e,
 #pragma unroll
                 for (int j = 6; j >= 0; --j) asm("v_lshl_add_u32 %0, %1, 4, %2" : "=v"(P) : "v"(P), "v"(cb[j]));
                 P -= (uint32_t)(kMagicBits - 8) * 0x11111111u;
-                const uint32_t Wd = transpose_nib8(P, ke) ^ 0x88888888u;
+                const uint32_t Wd = join_tiles(P) ^ 0x88888888u;
                 __builtin_amdgcn_raw_buffer_store_b32(Wd, yr, ylane, rp * yrow, 0);
             }
         };
@@ -272,7 +299,7 @@ __global__ __launch_bounds__(256, 4) void k_conv_first_u8(ConvGeom g, EpiArgs e,
         if (rp < rp1) step(std::integral_constant<int, 0>{}, rp);
     }
     if constexpr (F32IN) {
-        if (bad) *domain_flag = 1u;          // reported by qnn_weights_check / the next qnn_conv2d_forward, never silent
+        if (dom.bad()) *domain_flag = 1u;    // reported by qnn_weights_check / the next qnn_conv2d_forward, never silent
     }
 }
 
@@ -381,7 +408,7 @@ __global__ __launch_bounds__(256, (NBLK == 1 ? 6 : 3)) void k_conv_first_u8_full
     const int st1 = e1ok ? kRowPitchU * 4 + e1px * 4 + e1ch : kRowPitchU * 4 + 30 * 4;
     constexpr int EB = F32IN ? 4 : 1;
     const int rowb = g.W * 3 * EB;
-    bool bad = false;
+    ImageDomain dom;
     // ---- where this lane's packed word of a group goes: position jj of window kq (tile t: + 8 columns) ----
     const int jj = (OUT == QNN_STORE_I8) ? (r & 3) : (r & 3);          // after the transposes a lane holds position r & 3
     const int pixb = e.ocw * 4;                                        // bytes per stored pixel
@@ -418,12 +445,10 @@ __global__ __launch_bounds__(256, (NBLK == 1 ? 6 : 3)) void k_conv_first_u8_full
         };
         auto stage_write = [&](auto slotc, uint32_t b0, uint32_t b1) {
             constexpr int SB = decltype(slotc)::value * (kRowPitchU * 4);
-            if constexpr (F32IN) {
-                b0 = image_byte(__uint_as_float(b0), bad);
-                b1 = image_byte(__uint_as_float(b1), bad);
-            }
-            ldsb[st0 + SB] = (uint8_t)(b0 ^ 0x80u);
-            ldsb[st1 + SB] = (uint8_t)(b1 ^ 0x80u);
+            if constexpr (F32IN) image_bytes2(b0, b1, dom);      // the low bytes come back as signed bytes
+            else { b0 ^= 0x80u; b1 ^= 0x80u; }
+            ldsb[st0 + SB] = (uint8_t)b0;
+            ldsb[st1 + SB] = (uint8_t)b1;
         };
         const int yy_first = 2 * rp0;
         uint32_t fa0, fa1, fb0, fb1, fc0, fc1;
@@ -521,7 +546,7 @@ __global__ __launch_bounds__(256, (NBLK == 1 ? 6 : 3)) void k_conv_first_u8_full
         if (rp < rp1) step(std::integral_constant<int, 0>{}, rp);
     }
     if constexpr (F32IN) {
-        if (bad) *domain_flag = 1u;
+        if (dom.bad()) *domain_flag = 1u;
     }
 }
 
