@@ -31,19 +31,10 @@ void qnn_set_kernel_name(const char* name);
         }                                                                      \
     } while (0)
 
-// ---- measurement scaffolding ------------------------------------------------------
-// A/B switches read from the environment and the operand-load ablations of the GEMM exist ONLY in builds made with
-// -DQNN_EXPERIMENTS (tools/build_variant.py <name> <file.hip> -DQNN_EXPERIMENTS ...).  The default library reads no
-// environment variable on its dispatch paths and carries no ablation code: every switch is its compiled-in default.
-#ifdef QNN_EXPERIMENTS
-#define QNN_ENV_INT(name, dflt) (getenv(name) ? atoi(getenv(name)) : (dflt))
-#define QNN_ENV_STR(name) getenv(name)
-#define QNN_ABLATE(word, bit) (((word) & (bit)) != 0)
-#else
-#define QNN_ENV_INT(name, dflt) (dflt)
-#define QNN_ENV_STR(name) ((const char*)nullptr)
-#define QNN_ABLATE(word, bit) false
-#endif
+// ---- no measurement scaffolding ---------------------------------------------------
+// The sources carry no run-time switch: nothing here reads the environment, and there is no ablation code.  Kernel
+// selection is qnn_set_conv_impl() and the per-call QNN_EPI_* flags; A/B work compares against the parent commit, or
+// rebuilds one file with a -D tuning constant (QNN_*_WPS, QNN_*_DEPTH, QNN_DMA_NBUF, ...) through tools/build_variant.py.
 
 // ---- opaque weights handle --------------------------------------------------
 struct qnn_weights {

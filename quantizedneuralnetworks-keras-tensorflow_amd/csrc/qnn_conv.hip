@@ -1026,9 +1026,7 @@ int try_launch_xnor_f32(const ConvGeom& g, const EpiArgs& e, int in_fn, const fl
     // strip height: whole image if it fits in ~32 KB of LDS, else as many rows as fit
     int TR = g.H;
     while ((size_t)(TR + 2) * g.W * cw * 4 > 32768 && TR > 1) TR = (TR + 1) / 2;
-    static const int tr_env = QNN_ENV_INT("QNN_XNOR_TR", 0);
-    if (tr_env > 0 && tr_env < TR) TR = tr_env;
-    else if (tr_env == 0 && TR > 8 && (TR % 8) == 0) TR = 8;    // measured: more, smaller items overlap load and compute better
+    if (TR > 8 && (TR % 8) == 0) TR = 8;    // measured: more, smaller items overlap load and compute better
     const int strips = (g.H + TR - 1) / TR;
     const size_t lds = (size_t)(TR + 2) * g.W * cw * 4;
     snprintf(name, name_len, "xnor_f32_cw%d", cw);
@@ -1672,7 +1670,7 @@ extern "C" int qnn_conv2d_dense_forward(const qnn_weights_t* wc, const qnn_weigh
         qnn_set_error("qnn_conv2d_dense_forward: tensor too large for one launch");
         return QNN_EUNSUPPORTED;
     }
-    mg.x_bytes = (uint32_t)xb; mg.w_bytes = (uint32_t)wb; mg.ablate = 0;
+    mg.x_bytes = (uint32_t)xb; mg.w_bytes = (uint32_t)wb;
     e.scale = e.scale * (1.0f / 256.0f);                    // both conv operands carry *16 (as qnn_route_gemm)
     const char* kname = "";
     if (qnn_launch_areg_head(mg, e, x, wc->d_mfma, qnn_halo_fp6(wc, e), wd, ed, y, (hipStream_t)stream, &kname) != 0) {

@@ -156,11 +156,8 @@ __global__ __launch_bounds__(256, (NT <= 2 ? 3 : 2)) void k_conv_first_mfma(Conv
 // Wp % 8 == 0); POOL==1: 32 pixels in a row (needs W % 32 == 0): tiles never straddle
 // the image edge, so no store needs a bounds check.  No barriers: the LDS tile is
 // private to the wave.
-#ifndef QNN_FIRST_PRIO
-// 1 = a wave's MFMA phase runs at raised priority (s_setprio 1): the other waves' epilogue VALU then only takes the
-// issue slots the matrix chain leaves (measured 141 -> 133 us; raising the epilogue instead: 135 us; 0 = off)
-#define QNN_FIRST_PRIO 1
-#endif
+// A wave's MFMA phase runs at raised priority (s_setprio 1): the other waves' epilogue VALU then only takes the issue
+// slots the matrix chain leaves (measured 141 -> 133 us; raising the epilogue instead: 135 us).
 
 constexpr int first_lds_row_stride(int roww) {          // smallest stride >= roww with stride % 32 == 16
     int rs = (roww / 32) * 32 + 16;
@@ -173,7 +170,8 @@ __global__ __launch_bounds__(256, QNN_FIRST_WPS) void k_conv_first_lds(ConvGeom 
                                                            const float* __restrict__ wq,
                                                            void* __restrict__ y, long total_q,
                                                            int tiles, int tiles_per_row,
-                                                           FastDiv fd_tpr, uint32_t x_bytes, int abl) {
+                                                           FastDiv fd_tpr, uint32_t x_bytes) {
+    static_assert(NT == 2, "launched on 64-filter slices only (launch_first)");
     constexpr int K = 9 * CIN;
     constexpr int KS = (K + 1) / 2;
     constexpr int TROWS = (POOL == 2) ? 4 : 3;        // conv rows + halo
@@ -374,31 +372,19 @@ __global__ __launch_bounds__(256, QNN_FIRST_WPS) void k_conv_first_lds(ConvGeom 
             for (int u = 0; u < 2; ++u)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) acc[u][r] = 0.0f;
-#if QNN_FIRST_PRIO == 1
             __builtin_amdgcn_s_setprio(1);
-#elif QNN_FIRST_PRIO == 2
-            __builtin_amdgcn_s_setprio(0);
-#endif
 #pragma unroll
             for (int s = 0; s < KS; ++s)
 #pragma unroll
                 for (int u = 0; u < 2; ++u)
                     acc[u] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[s], wb[nc + u][s], acc[u], 0, 0, 0);
-#if QNN_FIRST_PRIO == 1
             __builtin_amdgcn_s_setprio(0);
-#elif QNN_FIRST_PRIO == 2
-            __builtin_amdgcn_s_setprio(1);
-#endif
-            if (nc + 2 >= NT && !QNN_ABLATE(abl, 2)) {
+            if (nc + 2 >= NT) {
                 __builtin_amdgcn_sched_barrier(0);
                 stage_write(0);
                 fetch_operands();
                 if (periodic) stage_load_next(); else stage_load(min(t + 2 * nwaves, tiles - 1));
                 __builtin_amdgcn_sched_barrier(0);
-            }
-            if (QNN_ABLATE(abl, 1)) {                       // timing experiment: no epilogue arithmetic, one raw store
-                if (acc[0][0] + acc[1][0] == 123.456f) ytile[lane_off + nc * 4] = 1u;
-                continue;
             }
             auto bn = [&](float v, const FoldEpi& f) {
                 return __fadd_rn(__fmul_rn(__fadd_rn(v, f.nb), f.ninv), f.nshift);
@@ -472,36 +458,36 @@ int launch_first(const ConvGeom& g, const EpiArgs& e, const void* x, const float
     const double xb = (double)g.N * g.H * g.W * CIN * 4.0;
     if (xb >= 2.0e9) return 1;                  // 31-bit buffer offsets
     const uint32_t x_bytes = (uint32_t)xb;
-    static const int no_lds = QNN_ENV_INT("QNN_FIRST_GATHER", 0);
-    const bool lds_ok = !no_lds && NT == 2 && g.stride == 1 && g.pt == 1 && g.pl == 1 &&
-                        ((g.pool == 2 && (g.Wp % 8) == 0 && (g.H % 2) == 0 && (g.W % 2) == 0) ||
-                         (g.pool == 1 && (g.W % 32) == 0));
-    if (lds_ok) {
-        const int tpr = g.pool == 2 ? g.Wp / 8 : g.W / 32;
-        const int rows = g.pool == 2 ? g.Hp : g.H;
-        const long ntiles = (long)g.N * rows * tpr;
-        if (ntiles < 2.0e9) {
-            long lblocks = (ntiles + 3) / 4;
-            const long lmax = 256 * QNN_FIRST_WPS / ny;   // persistent: QNN_FIRST_WPS waves per SIMD
-            if (lblocks > lmax) lblocks = lmax;
-            const dim3 lgrid((unsigned)lblocks, (unsigned)ny);
-            const FastDiv fd_tpr = qnn_fastdiv((uint32_t)tpr);
-            const size_t lds_bytes = (size_t)4 * (g.pool == 2 ? 4 * first_lds_row_stride(18 * CIN) : 3 * 34 * CIN) * 4   // one tile per wave
-                                     + (size_t)NT * 32 * 9 * CIN * 4;                                                  // + the block's filters
-            static const int abl = QNN_ENV_INT("QNN_FIRST_ABL", 0);   // timing ablations: experiment builds only
+    if constexpr (NT == 2) {                     // the LDS-staged kernel works on 64-filter slices only
+        const bool lds_ok = g.stride == 1 && g.pt == 1 && g.pl == 1 &&
+                            ((g.pool == 2 && (g.Wp % 8) == 0 && (g.H % 2) == 0 && (g.W % 2) == 0) ||
+                             (g.pool == 1 && (g.W % 32) == 0));
+        if (lds_ok) {
+            const int tpr = g.pool == 2 ? g.Wp / 8 : g.W / 32;
+            const int rows = g.pool == 2 ? g.Hp : g.H;
+            const long ntiles = (long)g.N * rows * tpr;
+            if (ntiles < 2.0e9) {
+                long lblocks = (ntiles + 3) / 4;
+                const long lmax = 256 * QNN_FIRST_WPS / ny;   // persistent: QNN_FIRST_WPS waves per SIMD
+                if (lblocks > lmax) lblocks = lmax;
+                const dim3 lgrid((unsigned)lblocks, (unsigned)ny);
+                const FastDiv fd_tpr = qnn_fastdiv((uint32_t)tpr);
+                const size_t lds_bytes = (size_t)4 * (g.pool == 2 ? 4 * first_lds_row_stride(18 * CIN) : 3 * 34 * CIN) * 4   // one tile per wave
+                                         + (size_t)NT * 32 * 9 * CIN * 4;                                                  // + the block's filters
 #define FIRST_LDS_CASE(OUT)                                                                      \
-            if (e.out_store == OUT) {                                                            \
-                if (g.pool == 2)                                                                 \
-                    hipLaunchKernelGGL((k_conv_first_lds<CIN, NT, OUT, 2>), lgrid, block, lds_bytes, s, g, e, xf, wq, y, total_q, (int)ntiles, tpr, fd_tpr, x_bytes, abl); \
-                else                                                                             \
-                    hipLaunchKernelGGL((k_conv_first_lds<CIN, NT, OUT, 1>), lgrid, block, lds_bytes, s, g, e, xf, wq, y, total_q, (int)ntiles, tpr, fd_tpr, x_bytes, abl); \
-                return 0;                                                                        \
-            }
-            FIRST_LDS_CASE(QNN_STORE_F32)
-            FIRST_LDS_CASE(QNN_STORE_BIN)
-            FIRST_LDS_CASE(QNN_STORE_I4)
-            FIRST_LDS_CASE(QNN_STORE_I8)
+                if (e.out_store == OUT) {                                                            \
+                    if (g.pool == 2)                                                                 \
+                        hipLaunchKernelGGL((k_conv_first_lds<CIN, NT, OUT, 2>), lgrid, block, lds_bytes, s, g, e, xf, wq, y, total_q, (int)ntiles, tpr, fd_tpr, x_bytes); \
+                    else                                                                             \
+                        hipLaunchKernelGGL((k_conv_first_lds<CIN, NT, OUT, 1>), lgrid, block, lds_bytes, s, g, e, xf, wq, y, total_q, (int)ntiles, tpr, fd_tpr, x_bytes); \
+                    return 0;                                                                        \
+                }
+                FIRST_LDS_CASE(QNN_STORE_F32)
+                FIRST_LDS_CASE(QNN_STORE_BIN)
+                FIRST_LDS_CASE(QNN_STORE_I4)
+                FIRST_LDS_CASE(QNN_STORE_I8)
 #undef FIRST_LDS_CASE
+            }
         }
     }
 #define FIRST_CASE(OUT)                                                                      \

@@ -584,8 +584,7 @@ int qnn_try_launch_first_u8(const ConvGeom& g, const EpiArgs& e, const void* x, 
                        ((e.fn == QNN_FN_QUANTIZED_TANH && e.act_m <= 8.0f) || e.fn == QNN_FN_BINARY_TANH);
     const bool full = !fused && g.pool == 1 && e.out_store != QNN_STORE_F32;
     // persistent grid = what is resident: four workgroups per CU (three for the un-pooled packed form, launch bounds)
-    const int bpc = QNN_ENV_INT("QNN_U8_BPC", full ? (g.cout == 16 ? 6 : 3) : 4);   // (override: experiment builds only)
-    const int blocks_cap = 256 * (bpc >= 1 && bpc <= 8 ? bpc : 4);
+    const int blocks_cap = 256 * (full ? (g.cout == 16 ? 6 : 3) : 4);
     const long nwaves = (long)blocks_cap * 4;
     int best_rc = hp2, best_nch = 1;
     double best_cost = 1e300;

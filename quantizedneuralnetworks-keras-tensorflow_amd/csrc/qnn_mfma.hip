@@ -40,6 +40,8 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN >= 16 ? 4 : WM * WN >= 8 ? 2
     constexpr int NA = BM / RPP, NB = BN / RPP;
     constexpr int XCH = (XS == QNN_STORE_I8) ? 16 : 8;     // stored bytes per 16-channel chunk
     static_assert(NA >= 1 && NB >= 1, "tile too small for the workgroup");
+    static_assert(WM == 4 && (WN == 1 || ((WN == 2 || WN == 4) && OUT == QNN_STORE_BIN)),
+                  "launched for the 256 x 64 tile and for 1-bit outputs only (qnn_route_gemm, launch_tile)");
     const ConvGeom& g = mg.g;
 
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -57,8 +59,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN >= 16 ? 4 : WM * WN >= 8 ? 2
     {
         const unsigned nb_ = gridDim.x, b_ = blockIdx.x;
         const unsigned q_ = nb_ / 8, r_ = nb_ % 8, xcd = b_ % 8, idx = b_ / 8;
-        tile = QNN_ABLATE(mg.ablate, 4) ? (long)b_
-                               : (long)((xcd < r_ ? xcd * (q_ + 1) : r_ * (q_ + 1) + (xcd - r_) * q_) + idx);
+        tile = (long)((xcd < r_ ? xcd * (q_ + 1) : r_ * (q_ + 1) + (xcd - r_) * q_) + idx);
     }
     const int nbase = blockIdx.y * BN;
 
@@ -127,11 +128,10 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN >= 16 ? 4 : WM * WN >= 8 ? 2
     uint4 rbA[NB], rbB[NB];
     auto stage_load = [&](araw_t (&ra)[NA], uint4 (&rb)[NB]) {
         const int xoff = (s_dy * g.W + s_dx) * mg.x_pix_bytes + s_kc * (4 * XCH);
-        const int woff = (s_tap < g.kh * g.kw && !QNN_ABLATE(mg.ablate, 2)) ? s_tap * g.cin + s_kc * 64
-                                                                    : (int)0x40000000;   // past the end -> zeros
+        const int woff = s_tap < g.kh * g.kw ? s_tap * g.cin + s_kc * 64 : (int)0x40000000;   // past the end -> zeros
 #pragma unroll
         for (int p = 0; p < NA; ++p) {
-            const bool ok = ((a_mask[p] >> s_tap) & 1u) && !QNN_ABLATE(mg.ablate, 1);
+            const bool ok = (a_mask[p] >> s_tap) & 1u;
             const int voff = ok ? a_voff[p] + xoff : (int)0x80000000;   // out of range -> zeros
             if constexpr (XS == QNN_STORE_I8)
                 ra[p] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(xrsrc, voff, 0, 0));
@@ -177,13 +177,13 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN >= 16 ? 4 : WM * WN >= 8 ? 2
                 fa[t] = *reinterpret_cast<const v4i*>(smem + fa_addr[t][kk] + bufoff_a);
                 fb[t] = *reinterpret_cast<const v4i*>(smem + fb_addr[t][kk] + bufoff_b);
             }
-            if (!QNN_ABLATE(mg.ablate, 8)) __builtin_amdgcn_s_setprio(1);
+            __builtin_amdgcn_s_setprio(1);
 #pragma unroll
             for (int a = 0; a < 2; ++a)
 #pragma unroll
                 for (int b = 0; b < 2; ++b)
                     acc[a][b] = __builtin_amdgcn_mfma_i32_32x32x32_i8(fa[a], fb[b], acc[a][b], 0, 0, 0);
-            if (!QNN_ABLATE(mg.ablate, 8)) __builtin_amdgcn_s_setprio(0);
+            __builtin_amdgcn_s_setprio(0);
         }
     };
 
@@ -246,51 +246,45 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN >= 16 ? 4 : WM * WN >= 8 ? 2
     }
 }
 
-// 16x16x64 variant, defined below (it uses the folded-epilogue helpers)
+// 16x16x64 variants, defined below (they use the folded-epilogue helpers)
 template <int XS, int WM, int WN, int OUT, int POOL>
 __global__ void k_conv_mfma16(MfmaGeom mg, EpiArgs e, const uint8_t* __restrict__ x,
                               const uint8_t* __restrict__ wq8, void* __restrict__ y);
+template <int XS, int WM, int WN, int OUT, int POOL>
+__global__ void k_conv_mfma16_dma(MfmaGeom mg, EpiArgs e, const uint8_t* __restrict__ x,
+                                  const uint8_t* __restrict__ wq8, void* __restrict__ y);
 
-// launch of the LDS-DMA variant (defined after the kernel: it takes the kernel's address)
-template <int XS, int WM, int WN, int OUT>
-void launch_dma16(const MfmaGeom& mg, const EpiArgs& e, const void* x, const uint8_t* w, void* y, hipStream_t s,
-                  dim3 grid, dim3 block);
+template <int XS, int WM, int WN, int OUT, int POOL>
+void launch_tile(const MfmaGeom& mg, const EpiArgs& e, const void* x, const uint8_t* w, void* y,
+                 hipStream_t s) {
+    constexpr int BM = 64 * WM, BN = 64 * WN;
+    const long rows = mg.total_q * POOL * POOL;
+    const dim3 grid((unsigned)((rows + BM - 1) / BM), (unsigned)(mg.g.cout / BN));
+    const dim3 block(64 * WM * WN);
+    const size_t lds = 2 * (BM + BN) * 64;
+    // the large tiles (16 / 8 waves per workgroup, four waves per SIMD) use the 16x16x64 shape; 1-bit outputs and the
+    // 256 x 64 tile the 32x32x32 kernel
+    if constexpr (OUT != QNN_STORE_BIN && WN >= 2 && XS == QNN_STORE_I8) {
+        // int8 activations: both operands go global -> LDS by LDS-DMA (see conv_mfma16_body)
+        const size_t lds3 = (size_t)QNN_DMA_NBUF * (BM + BN) * 64;
+        (void)hipFuncSetAttribute((const void*)k_conv_mfma16_dma<XS, WM, WN, OUT, POOL>,
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3);
+        hipLaunchKernelGGL((k_conv_mfma16_dma<XS, WM, WN, OUT, POOL>), grid, block, lds3, s, mg, e,
+                           (const uint8_t*)x, w, y);
+    } else if constexpr (OUT != QNN_STORE_BIN && WN >= 2) {
+        hipLaunchKernelGGL((k_conv_mfma16<XS, WM, WN, OUT, POOL>), grid, block, lds, s, mg, e,
+                           (const uint8_t*)x, w, y);
+    } else {
+        hipLaunchKernelGGL((k_conv_mfma<XS, WM, WN, OUT, POOL>), grid, block, lds, s, mg, e,
+                           (const uint8_t*)x, w, y);
+    }
+}
 
 template <int XS, int WM, int WN, int OUT>
 void launch_pool(const MfmaGeom& mg, const EpiArgs& e, const void* x, const uint8_t* w, void* y,
                  hipStream_t s) {
-    constexpr int BM = 64 * WM, BN = 64 * WN;
-    const long rows = mg.total_q * (mg.g.pool == 2 ? 4 : 1);
-    const dim3 grid((unsigned)((rows + BM - 1) / BM), (unsigned)(mg.g.cout / BN));
-    const dim3 block(64 * WM * WN);
-    const size_t lds = 2 * (BM + BN) * 64;
-    // the large tiles (16 / 8 waves per workgroup, four waves per SIMD) use the 16x16x64 shape
-    if constexpr (OUT != QNN_STORE_BIN && WM == 4 && WN >= 2) {
-        static const int shape = QNN_ENV_INT("QNN_MFMA_SHAPE", 16);
-        // int8 activations on the 256 x 256 tile: both operands go global -> LDS by LDS-DMA (see k_conv_mfma16)
-        if constexpr (XS == QNN_STORE_I8 && WM == 4 && (WN == 4 || WN == 2)) {
-            static const int dma = QNN_ENV_INT("QNN_MFMA_DMA", 1);   // A/B switch (experiment builds only)
-            if (shape == 16 && dma) {
-                launch_dma16<XS, WM, WN, OUT>(mg, e, x, w, y, s, grid, block);
-                return;
-            }
-        }
-        if (shape == 16) {
-            if (mg.g.pool == 2)
-                hipLaunchKernelGGL((k_conv_mfma16<XS, WM, WN, OUT, 2>), grid, block, lds, s, mg, e,
-                                   (const uint8_t*)x, w, y);
-            else
-                hipLaunchKernelGGL((k_conv_mfma16<XS, WM, WN, OUT, 1>), grid, block, lds, s, mg, e,
-                                   (const uint8_t*)x, w, y);
-            return;
-        }
-    }
-    if (mg.g.pool == 2)
-        hipLaunchKernelGGL((k_conv_mfma<XS, WM, WN, OUT, 2>), grid, block, lds, s, mg, e,
-                           (const uint8_t*)x, w, y);
-    else
-        hipLaunchKernelGGL((k_conv_mfma<XS, WM, WN, OUT, 1>), grid, block, lds, s, mg, e,
-                           (const uint8_t*)x, w, y);
+    if (mg.g.pool == 2) launch_tile<XS, WM, WN, OUT, 2>(mg, e, x, w, y, s);
+    else launch_tile<XS, WM, WN, OUT, 1>(mg, e, x, w, y, s);
 }
 
 template <int XS, int WM, int WN>
@@ -338,7 +332,8 @@ __device__ __forceinline__ void conv_mfma16_body(const MfmaGeom& mg, const EpiAr
     constexpr int A_BUF = BM * 64, B_BUF = BN * 64;
     constexpr int NBUF = DMA ? QNN_DMA_NBUF : 2;
     constexpr int B_BASE = NBUF * A_BUF;
-    static_assert(!DMA || XS == QNN_STORE_I8, "LDS-DMA staging: int8 rows (int4 rows are widened in registers)");
+    static_assert(WM == 4 && (WN == 2 || WN == 4), "launched for the 256 x 128 and 256 x 256 tiles only (qnn_route_gemm)");
+    static_assert(DMA == (XS == QNN_STORE_I8), "int8 rows are staged by LDS-DMA, int4 rows are widened in registers");
     constexpr int NLD = NA + NB;             // LDS-DMA loads per thread and K-step
 
     const int tid = threadIdx.x;
@@ -352,8 +347,7 @@ __device__ __forceinline__ void conv_mfma16_body(const MfmaGeom& mg, const EpiAr
     {
         const unsigned nb_ = gridDim.x, b_ = blockIdx.x;
         const unsigned q_ = nb_ / 8, r_ = nb_ % 8, xcd = b_ % 8, idx = b_ / 8;
-        tile = QNN_ABLATE(mg.ablate, 4) ? (long)b_
-                               : (long)((xcd < r_ ? xcd * (q_ + 1) : r_ * (q_ + 1) + (xcd - r_) * q_) + idx);
+        tile = (long)((xcd < r_ ? xcd * (q_ + 1) : r_ * (q_ + 1) + (xcd - r_) * q_) + idx);
     }
     const int nbase = blockIdx.y * BN;
 
@@ -420,11 +414,10 @@ __device__ __forceinline__ void conv_mfma16_body(const MfmaGeom& mg, const EpiAr
     uint4 rbA[NB], rbB[NB];
     auto stage_load = [&](araw_t (&ra)[NA], uint4 (&rb)[NB]) {
         const int xoff = (s_dy * g.W + s_dx) * mg.x_pix_bytes + s_kc * (4 * XCH);
-        const int woff = (s_tap < g.kh * g.kw && !QNN_ABLATE(mg.ablate, 2)) ? s_tap * g.cin + s_kc * 64
-                                                                    : (int)0x40000000;   // past the end -> zeros
+        const int woff = s_tap < g.kh * g.kw ? s_tap * g.cin + s_kc * 64 : (int)0x40000000;   // past the end -> zeros
 #pragma unroll
         for (int p = 0; p < NA; ++p) {
-            const bool ok = ((a_mask[p] >> s_tap) & 1u) && !QNN_ABLATE(mg.ablate, 1);
+            const bool ok = (a_mask[p] >> s_tap) & 1u;
             const int voff = ok ? a_voff[p] + xoff : (int)0x80000000;   // out of range -> zeros
             if constexpr (XS == QNN_STORE_I8)
                 ra[p] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(xrsrc, voff, 0, 0));
@@ -484,13 +477,12 @@ __device__ __forceinline__ void conv_mfma16_body(const MfmaGeom& mg, const EpiAr
         using lds_ptr = __attribute__((address_space(3))) void*;
         auto dma_issue = [&](int buf) {
             const int xoff = (s_dy * g.W + s_dx) * mg.x_pix_bytes + s_kc * (4 * XCH);
-            const int woff = (s_tap < g.kh * g.kw && !QNN_ABLATE(mg.ablate, 2)) ? s_tap * g.cin + s_kc * 64
-                                                                        : (int)0x40000000;   // past the end -> zeros
+            const int woff = s_tap < g.kh * g.kw ? s_tap * g.cin + s_kc * 64 : (int)0x40000000;   // past the end -> zeros
             // pass p of a tile = rows [p * RPP, (p + 1) * RPP): wave w writes the 1 KiB at p * RPP * 64 + w * 1024
 #pragma unroll
             for (int p = 0; p < NA; ++p) {
-                const bool ok = ((a_mask[p] >> s_tap) & 1u) && !QNN_ABLATE(mg.ablate, 1);                 // (ablate: timing experiments)
-                const int voff = ok ? a_voff[p] + xoff : (int)0x80000000;                        // out of range -> zeros
+                const bool ok = (a_mask[p] >> s_tap) & 1u;
+                const int voff = ok ? a_voff[p] + xoff : (int)0x80000000;   // out of range -> zeros
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(
                     xrsrc, (lds_ptr)(smem + buf * A_BUF + p * (RPP * 64) + wave * 1024), 16, voff, 0, 0, 0);
             }
@@ -503,14 +495,13 @@ __device__ __forceinline__ void conv_mfma16_body(const MfmaGeom& mg, const EpiAr
                 if (++s_dx == g.kw) { s_dx = 0; ++s_dy; }
             }
         };
-#if QNN_DMA_PREFETCH
         // Fragment prefetch: the operand registers of step k + 1 are filled WHILE the MFMAs of step k run (the B
         // fragments into a second register set, each A fragment into its own registers as soon as its row of MFMAs has
         // been issued), so a step starts on the matrix pipe right after its barrier instead of after 8 LDS reads that
         // all 16 waves issue at once.  The wait / barrier at the top of step k therefore covers the loads of step
         // k + 1, and the loads issued at step k go three steps ahead, into the buffer step k just vacated.
         static_assert(NBUF == 3, "the prefetching schedule rotates three buffers");
-        if (true) {
+        {
             dma_issue(0); dma_issue(1); dma_issue(2);
             v4i fa[4], fb[2][4];
             auto read_a = [&](int t, int b_) { return *reinterpret_cast<const v4i*>(smem + fa_addr + b_ * A_BUF + t * 1024); };
@@ -546,23 +537,6 @@ __device__ __forceinline__ void conv_mfma16_body(const MfmaGeom& mg, const EpiAr
             }
             if (ks < S) step(std::integral_constant<int, 0>{});
             __builtin_amdgcn_s_waitcnt(0x0070);        // vmcnt(0), lgkmcnt(0): nothing may land after the kernel's LDS is gone
-        } else
-#endif
-        {
-#pragma unroll
-        for (int i = 0; i < NBUF - 1; ++i) dma_issue(i);                   // steps 0 .. NBUF-2
-        int buf = 0, nxt = NBUF - 1;                   // buffer of step ks, buffer of step ks + NBUF - 1
-        for (int ks = 0; ks < S; ++ks) {
-            // vmcnt(2 * (NBUF - 2)): step ks has landed, the later steps may be in flight
-            __builtin_amdgcn_s_waitcnt(0x0F70 | (NLD * (NBUF - 2)));
-            __builtin_amdgcn_s_barrier();
-            dma_issue(nxt);                            // step ks + 2 (past the end: zeros, never read)
-            compute(buf * A_BUF, buf * B_BUF);
-            __builtin_amdgcn_s_waitcnt(0xC07F);        // lgkmcnt(0): the fragment reads of this step are done
-            buf = buf == NBUF - 1 ? 0 : buf + 1;
-            nxt = nxt == NBUF - 1 ? 0 : nxt + 1;
-        }
-        __builtin_amdgcn_s_waitcnt(0x0F70);            // vmcnt(0): no load may land after the kernel's LDS is gone
         }
     } else {
     // ---- main loop: one barrier per K-step; the loads of step k+2 are issued before the
@@ -729,25 +703,6 @@ __global__ __launch_bounds__(64 * WM * WN, 4) void k_conv_mfma16_dma(MfmaGeom mg
     conv_mfma16_body<XS, WM, WN, OUT, POOL, true>(mg, e, x, wq8, y);
 }
 
-template <int XS, int WM, int WN, int OUT>
-void launch_dma16(const MfmaGeom& mg, const EpiArgs& e, const void* x, const uint8_t* w, void* y, hipStream_t s,
-                  dim3 grid, dim3 block) {
-    if constexpr (XS == QNN_STORE_I8 && WM == 4 && (WN == 4 || WN == 2) && OUT != QNN_STORE_BIN) {
-        const size_t lds3 = (size_t)QNN_DMA_NBUF * (64 * WM + 64 * WN) * 64;
-        if (mg.g.pool == 2) {
-            (void)hipFuncSetAttribute((const void*)k_conv_mfma16_dma<XS, WM, WN, OUT, 2>,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3);
-            hipLaunchKernelGGL((k_conv_mfma16_dma<XS, WM, WN, OUT, 2>), grid, block, lds3, s, mg, e,
-                               (const uint8_t*)x, w, y);
-        } else {
-            (void)hipFuncSetAttribute((const void*)k_conv_mfma16_dma<XS, WM, WN, OUT, 1>,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3);
-            hipLaunchKernelGGL((k_conv_mfma16_dma<XS, WM, WN, OUT, 1>), grid, block, lds3, s, mg, e,
-                               (const uint8_t*)x, w, y);
-        }
-    }
-}
-
 // int8 weight image for the I4 path: every packed word (8 nibbles) -> two words of
 // (code*16) bytes in the same even/odd order the activation staging produces
 __global__ __launch_bounds__(256) void k_expand_i4_weights(const uint32_t* __restrict__ packed,
@@ -849,7 +804,6 @@ int qnn_route_first_f32(const ConvCall& c, char* name, size_t name_len) {
     const bool lds_shape = g.stride == 1 && g.pt == 1 && g.pl == 1 &&
                            ((g.pool == 2 && (g.Wp % 8) == 0 && (g.H % 2) == 0 && (g.W % 2) == 0) ||
                             (g.pool == 1 && (g.W % 32) == 0));
-    // (QNN_FIRST_GATHER, read once in qnn_first.hip, selects the gather variant for A/B timing)
     if (lds_shape || g.cout == 64) return qnn_launch_first(g.cin, 2, g, e, c.x, c.w->d_wq, c.y, c.s);
     return qnn_launch_first(g.cin, 4, g, e, c.x, c.w->d_wq, c.y, c.s);
 }
@@ -884,7 +838,7 @@ static int route_strip_i8(const ConvCall& c, char* name, size_t name_len) {
     ms.total_q = (long)g.N * g.Ho * g.Wo;
     const double wb_ = (double)g.cout * 9 * g.cin;
     if (wb_ >= 2.0e9) return 1;
-    ms.x_bytes = 0; ms.w_bytes = (uint32_t)wb_; ms.ablate = 0;
+    ms.x_bytes = 0; ms.w_bytes = (uint32_t)wb_;
     snprintf(name, name_len, g.stride == 2 ? "strip_i8_c%d_s2" : "strip_i8_c%d", g.cin);
     return qnn_launch_strip_i8(g.cin, ms, e, c.x, w->d_mfma, c.y, c.s);
 }
@@ -897,7 +851,6 @@ int qnn_route_strip(const ConvCall& c, char* name, size_t name_len) {
     if (!w->d_mfma) return 1;
     if (c.x_store == QNN_STORE_I8) return route_strip_i8(c, name, name_len);
     if (c.x_store != QNN_STORE_I4) return 1;
-    static const bool small_off = QNN_ENV_STR("QNN_MFMA_SMALL_OFF") != nullptr;   // A/B switch (experiment builds only)
     // 3x3 stride-1 int4 layers with 16 / 32 / 64 input channels: row-walking strip kernel (qnn_mfma_strip.hip).
     // The residual's post-scale (models/resnet.py:128: 0.5) must be a power of two so that it folds exactly into the
     // activation's code scale.
@@ -926,14 +879,13 @@ int qnn_route_strip(const ConvCall& c, char* name, size_t name_len) {
             ms.total_q = (long)g.N * g.H * g.W;
             const double wb_ = (double)g.cout * 9 * g.cin;
             if (wb_ < 2.0e9) {
-                ms.x_bytes = 0; ms.w_bytes = (uint32_t)wb_; ms.ablate = 0;
+                ms.x_bytes = 0; ms.w_bytes = (uint32_t)wb_;
                 EpiArgs es = e;
                 es.scale = e.scale * (1.0f / 256.0f);        // both operands carry *16
                 es.proj_scale = e.proj_scale * (1.0f / 256.0f);
                 // 16 -> 16 channels with a usable fold and an even width: the LDS-staged form (qnn_mfma_strip16.hip: a sixth
                 // of the load and a quarter of the store instructions)
-                static const bool lds16_off = QNN_ENV_STR("QNN_STRIP16_LDS_OFF") != nullptr;   // A/B switch (experiment builds only)
-                if (g.cin == 16 && !lds16_off && !(e.flags & QNN_EPI_NO_LDS16) && qnn_launch_strip16_lds(ms, es, c.x, w->d_mfma, c.y, c.s) == 0) {
+                if (g.cin == 16 && !(e.flags & QNN_EPI_NO_LDS16) && qnn_launch_strip16_lds(ms, es, c.x, w->d_mfma, c.y, c.s) == 0) {
                     snprintf(name, name_len, "strip_i4_c16_lds");
                     return 0;
                 }
@@ -948,13 +900,13 @@ int qnn_route_strip(const ConvCall& c, char* name, size_t name_len) {
         g.kw == 3 && g.stride == 1 && g.pt == 1 && g.pl == 1 && g.pool == 1 && (g.W % 16) == 0 &&
         e.out_store == QNN_STORE_I4 && (g.cout % (g.cin == 16 ? 16 : 32)) == 0 &&
         (!e.res || (e.res_store == QNN_STORE_I4 && e.res_cw == e.ocw) ||
-         (e.res_store == QNN_STORE_F32 && e.res_cw == g.cout)) && !small_off) {
+         (e.res_store == QNN_STORE_F32 && e.res_cw == g.cout))) {
         MfmaGeom ms;
         ms.g = g; ms.kc = 1; ms.steps = 0; ms.x_pix_bytes = g.cin / 2;
         ms.total_q = (long)g.N * g.H * g.W;
         const double xb_ = (double)g.N * g.H * g.W * ms.x_pix_bytes, wb_ = (double)g.cout * 9 * g.cin;
         if (xb_ < 2.0e9 && wb_ < 2.0e9) {
-            ms.x_bytes = (uint32_t)xb_; ms.w_bytes = (uint32_t)wb_; ms.ablate = 0;
+            ms.x_bytes = (uint32_t)xb_; ms.w_bytes = (uint32_t)wb_;
             EpiArgs es = e;
             es.scale = e.scale * (1.0f / 256.0f);            // both operands carry *16
             snprintf(name, name_len, "mfma_i4_small_c%d", g.cin);
@@ -991,28 +943,15 @@ int qnn_route_gemm(const ConvCall& c, char* name, size_t name_len) {
     if (xb >= 2.0e9 || wb >= 2.0e9) return 1;          // 31-bit buffer offsets
     mg.x_bytes = (uint32_t)xb;
     mg.w_bytes = (uint32_t)wb;
-    static const int ablate = QNN_ENV_INT("QNN_MFMA_ABLATE", 0);
-    mg.ablate = ablate;
     EpiArgs e2 = e;
     if (x_store == QNN_STORE_I4) e2.scale = e.scale * (1.0f / 256.0f);   // both operands carry *16
-    // tile shape: waves along M x waves along N (64x64 per wave)
-    static const char* tile_env = QNN_ENV_STR("QNN_MFMA_TILE");
-    int wm_ = 4, wn_ = 1;
-    if ((g.cout % 256) == 0) { wm_ = 4; wn_ = 4; }          // measured: 256x256 > 128x256 > 256x128 > 128x128
-    else if ((g.cout % 128) == 0) { wm_ = 4; wn_ = 2; }
-    if (tile_env && strlen(tile_env) == 3) {
-        const int em = tile_env[0] - '0', en = tile_env[2] - '0';
-        if (em >= 1 && en >= 1 && (g.cout % (64 * en)) == 0) { wm_ = em; wn_ = en; }
-    }
-    // short-K layers with one 64-filter slice: weight-resident persistent kernel
-    static const int wres_env = QNN_ENV_INT("QNN_MFMA_WRES", -1);
+    // tile shape: waves along M x waves along N (64x64 per wave); measured: 256x256 > 128x256 > 256x128 > 128x128
+    const int wn_ = (g.cout % 256) == 0 ? 4 : (g.cout % 128) == 0 ? 2 : 1;
     const long rows_ = mg.total_q * (g.pool == 2 ? 4 : 1);
-    const bool wres_fit = mg.steps <= 12 && rows_ < 2000000000L;
-    const bool wres = wres_env == 0 ? false : wres_env == 1 ? wres_fit : (wres_fit && g.cout == 64 && !tile_env);
-    // 3x3, Cin <= 128: operands straight into registers (QNN_MFMA_AREG=0 disables, =1 also for Cout > 64)
-    static const int areg_env = QNN_ENV_INT("QNN_MFMA_AREG", -1);
-    const bool areg_fit = g.kh == 3 && g.kw == 3 && mg.kc <= 2 && rows_ < 2000000000L;
-    const bool areg = areg_env == 0 ? false : areg_env == 1 ? areg_fit : (areg_fit && g.cout == 64 && !tile_env && wres_env < 0);
+    // one 64-filter slice, 3x3, Cin <= 128: operands straight into registers
+    const bool areg = g.cout == 64 && g.kh == 3 && g.kw == 3 && mg.kc <= 2 && rows_ < 2000000000L;
+    // one 64-filter slice, short K: weight-resident persistent kernel
+    const bool wres = g.cout == 64 && mg.steps <= 12 && rows_ < 2000000000L;
     if (e.res && !(areg && g.pool == 1)) return 1;          // the other MFMA kernels have no residual epilogue
     // pooled int4 layers whose pooled map tiles into 8 x 2 / 4 x 4 rectangles: receptive field staged once through LDS
     // (k_conv_mfma_halo, qnn_mfma_areg.hip; QNN_EPI_NO_HALO keeps them on the per-tap kernel below)
@@ -1029,13 +968,11 @@ int qnn_route_gemm(const ConvCall& c, char* name, size_t name_len) {
         snprintf(name, name_len, "mfma_%s_wres256x64", x_store == QNN_STORE_I8 ? "i8" : "i4");
         return qnn_launch_wres(x_store, mg, e2, x, w->d_mfma, y, s);
     }
-    snprintf(name, name_len, "mfma_%s_%dx%d", x_store == QNN_STORE_I8 ? "i8" : "i4", 64 * wm_, 64 * wn_);
+    snprintf(name, name_len, "mfma_%s_256x%d", x_store == QNN_STORE_I8 ? "i8" : "i4", 64 * wn_);
 #define TILE_CASE(XS_, M_, N_) \
-    if (x_store == XS_ && wm_ == M_ && wn_ == N_) return launch_out<XS_, M_, N_>(mg, e2, x, w->d_mfma, y, s);
-    TILE_CASE(QNN_STORE_I8, 4, 1) TILE_CASE(QNN_STORE_I8, 2, 2) TILE_CASE(QNN_STORE_I8, 4, 2)
-    TILE_CASE(QNN_STORE_I8, 2, 4) TILE_CASE(QNN_STORE_I8, 4, 4)
-    TILE_CASE(QNN_STORE_I4, 4, 1) TILE_CASE(QNN_STORE_I4, 2, 2) TILE_CASE(QNN_STORE_I4, 4, 2)
-    TILE_CASE(QNN_STORE_I4, 2, 4) TILE_CASE(QNN_STORE_I4, 4, 4)
+    if (x_store == XS_ && wn_ == N_) return launch_out<XS_, M_, N_>(mg, e2, x, w->d_mfma, y, s);
+    TILE_CASE(QNN_STORE_I8, 4, 1) TILE_CASE(QNN_STORE_I8, 4, 2) TILE_CASE(QNN_STORE_I8, 4, 4)
+    TILE_CASE(QNN_STORE_I4, 4, 1) TILE_CASE(QNN_STORE_I4, 4, 2) TILE_CASE(QNN_STORE_I4, 4, 4)
 #undef TILE_CASE
     return 1;
 }

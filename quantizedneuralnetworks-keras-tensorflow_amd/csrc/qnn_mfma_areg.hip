@@ -1339,8 +1339,6 @@ int qnn_launch_areg(int x_store, int kc, const MfmaGeom& mg, const EpiArgs& e, c
 // 4 below that so that small batches still reach every CU.
 static int halo_waves(const MfmaGeom& mg, int tw) {
     const long ntiles = (long)mg.g.N * (mg.g.Wp / tw) * (mg.g.Hp / (16 / tw));
-    static const int forced = QNN_ENV_INT("QNN_HALO_NW", 0);
-    if (forced == 4 || forced == 8) return forced;
     return ntiles >= 256 * 8 ? 8 : 4;
 }
 

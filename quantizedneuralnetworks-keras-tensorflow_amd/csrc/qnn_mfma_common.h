@@ -16,9 +16,6 @@
 #ifndef QNN_DMA_NBUF
 #define QNN_DMA_NBUF 3          // LDS buffers of the LDS-DMA implicit GEMM (qnn_mfma.hip): loads run NBUF-1 K-steps ahead
 #endif
-#ifndef QNN_DMA_PREFETCH
-#define QNN_DMA_PREFETCH 1      // LDS-DMA implicit GEMM: fill the next K-step's operand registers under this step's MFMAs
-#endif
 #ifndef QNN_FIRST_WPS
 #define QNN_FIRST_WPS 3
 #endif
@@ -44,7 +41,6 @@ struct MfmaGeom {
     int x_pix_bytes;   // bytes per input pixel as stored
     long total_q;      // stored output pixels
     uint32_t x_bytes, w_bytes;   // sizes of the x tensor / int8 weight image (buffer descriptors)
-    int ablate;                  // timing experiments only (QNN_MFMA_ABLATE): 1 = no A traffic, 2 = no B traffic
 };
 
 namespace {

@@ -252,8 +252,7 @@ int qnn_launch_strip16_lds(const MfmaGeom& mg, const EpiArgs& e, const void* x, 
     const int spr = (g.W + 15) / 16;
     const double img = (double)g.H * g.W * 8.0;
     if (img >= 1.0e9) return 1;
-    static const int wps = QNN_ENV_INT("QNN_S16_WPS", QNN_S16_WPS);       // (A/B switch, experiment builds only)
-    const int blocks_cap = 256 * wps;
+    const int blocks_cap = 256 * QNN_S16_WPS;
     const long nwaves = (long)blocks_cap * 4;
     // rows per task: whole rounds of the persistent grid; a round costs rc rows + ~3 rows of pipeline fill.  Multiples of
     // four keep every store group full except the image's last.

@@ -229,13 +229,20 @@ def test_one_bit_layers_choose_the_matrix_pipe_by_shape_and_impl():
 
 
 def test_default_library_carries_no_measurement_scaffolding():
-    """The A/B environment switches and the GEMM's operand ablations are compiled in only with -DQNN_EXPERIMENTS
-    (tools/build_variant.py): the shipped library must not even contain their names."""
+    """The shipped library must not even contain the names of the A/B environment switches and of the GEMM's operand
+    ablations; since the experiment mode was deleted the sources read no environment
+    variable either: no csrc file calls getenv or names the experiment mode."""
     import importlib
     b = importlib.import_module("quantizedneuralnetworks-keras-tensorflow_amd._build")
     blob = open(b.LIB, "rb").read()
     for name in (b"QNN_MFMA_ABLATE", b"QNN_FIRST_ABL", b"QNN_MFMA_TILE", b"QNN_MFMA_SHAPE", b"QNN_MFMA_DMA",
                  b"QNN_MFMA_AREG", b"QNN_MFMA_WRES", b"QNN_MFMA_SMALL_OFF", b"QNN_FIRST_GATHER", b"QNN_FIXED_BPC",
-                 b"QNN_XNOR_TR"):
+                 b"QNN_XNOR_TR", b"QNN_U8_BPC", b"QNN_HALO_NW", b"QNN_S16_WPS", b"QNN_STRIP16_LDS_OFF", b"QNN_STRIP_ABL"):
         assert name not in blob, name
     assert "-DQNN_EXPERIMENTS" not in " ".join(b.CFLAGS)
+    sources = [os.path.join(b.CSRC, f) for f in sorted(os.listdir(b.CSRC)) if f.endswith((".hip", ".h"))]
+    assert len(sources) >= len(b.SOURCES) + 2
+    for path in sources:
+        text = open(path).read()
+        for word in ("getenv(", "QNN_EXPERIMENTS"):
+            assert word not in text, (os.path.basename(path), word)

@@ -230,6 +230,11 @@ ROUTES = [
     ("areg_i8", 0, lambda: _conv_i4(64, 64, 8, 16, pool=2, x_store=S.STORE_I8), "mfma_i8_areg64x64"),
     ("wres", 0, lambda: _conv_i4(64, 64, 8, 16, k=1), "mfma_i4_wres256x64"),
     ("tile", 0, lambda: _conv_i4(128, 128, 8, 16), "mfma_i4_256x128"),
+    # (Cin = 64, un-pooled, output in the input's store: the strip kernels come first; NO_STRIP64 is their per-call switch)
+    ("tile_i4_256", 0, lambda: _conv_i4(64, 256, 8, 16, flags=NO_STRIP64), "mfma_i4_256x256"),
+    ("tile_i8_256", 0, lambda: _conv_i4(64, 256, 8, 16, x_store=S.STORE_I8, flags=NO_STRIP64), "mfma_i8_256x256"),
+    ("tile_i8_128", 0, lambda: _conv_i4(64, 128, 8, 16, x_store=S.STORE_I8, flags=NO_STRIP64), "mfma_i8_256x128"),
+    ("tile_i4_192", 0, lambda: _conv_i4(64, 192, 8, 16, flags=NO_STRIP64), "mfma_i4_256x64"),
     ("tile_res", 0, lambda: _conv_i4(128, 128, 8, 16, res=S.STORE_I4), "ps_i4_cw16_k3"),
     # 10, 11: XNOR and the pixel-stationary kernels
     ("xnor_pk", 0, lambda: _conv_bin(64, 64, 8, 8), "xnor_pk_cw2"),
@@ -259,3 +264,47 @@ def test_route_table(case):
     with impl(pref):
         got = call()
     assert got == want, (got, want)
+
+
+# Every kernel the tiled GEMM translation unit (csrc/qnn_mfma.hip) emits: 32x32x32 on the 256 x 64 tile (Cout = 192) and for
+# 1-bit outputs, 16x16x64 on 256 x 128 / 256 x 256 (Cout = 128 / 256) for int4 inputs, its LDS-DMA form for int8 inputs.
+# No combination is skipped: each output store is called with an activation check_epilogue accepts for it (BIN needs
+# binary_tanh).
+GEMM_OUT = {S.STORE_F32: (S.FN_NONE, 0), S.STORE_BIN: (S.FN_BINARY_TANH, 0), S.STORE_I4: (QT, 4), S.STORE_I8: (QT, 8)}
+GEMM_TILE = {192: 64, 128: 128, 256: 256}
+GEMM_CASES = [(xs, cout, out, pool) for xs in (S.STORE_I4, S.STORE_I8) for cout in (192, 128, 256)
+              for out in (S.STORE_F32, S.STORE_BIN, S.STORE_I4, S.STORE_I8) for pool in (1, 2)]
+_gemm_layers = {}
+
+
+def _gemm_layer(xs, cout):
+    """Weights, BN vectors and the packed inputs (N = 2 and N = 3) of one (input store, Cout): built once."""
+    if (xs, cout) not in _gemm_layers:
+        rng = np.random.default_rng(1000 * xs + cout)
+        bits = 4 if xs == S.STORE_I4 else 8
+        w = _weights(rng, 64, cout, 3, xs, nb=bits)
+        _gemm_layers[xs, cout] = (w, _bn(rng, cout), bits,
+                                  {n: _abi.pack(dev(rng.standard_normal((n, 8, 16, 64)).astype(F32)), 64, QT, bits, xs)
+                                   for n in (2, 3)})
+    return _gemm_layers[xs, cout]
+
+
+@pytest.mark.parametrize("xs,cout,out,pool", GEMM_CASES,
+                         ids=["i%d_c%d_out%d_pool%d" % c for c in GEMM_CASES])
+def test_gemm_tiles_match_valu(xs, cout, out, pool):
+    """8 x 16 pixels, 3x3, Cin = 64.  N = 2 fills the 256-row tile exactly (256 conv rows; pooled: 64 windows = 256 rows),
+    N = 3 leaves a ragged second tile (384 rows).  Bit for bit against k_conv_ps (IMPL_VALU), an independent kernel.
+    QNN_EPI_NO_STRIP64 keeps the un-pooled int4 -> int4 and int8 -> int8 calls off the Cin = 64 strip kernels, which come
+    first in the route list; it changes nothing for the other calls."""
+    w, (inv, shift), bits, xp = _gemm_layer(xs, cout)
+    fn, ab = GEMM_OUT[out]
+    for n in (2, 3):
+        got = {}
+        for pref in (_abi.IMPL_AUTO, VALU):
+            with impl(pref), epi_flags(NO_STRIP64):
+                y = _abi.conv2d(w, xp[n], xs, bits, n, 8, 16, inv, shift, fn, ab, pool, out)[0]
+            got[pref] = (_abi.last_kernel(), y.cpu().numpy())
+        assert got[_abi.IMPL_AUTO][0] == "mfma_i%d_256x%d" % (bits, GEMM_TILE[cout]), got[_abi.IMPL_AUTO][0]
+        assert got[VALU][0] == "ps_i%d_cw%d_k3" % (bits, 64 * bits // 32), got[VALU][0]
+        assert got[_abi.IMPL_AUTO][1].shape == got[VALU][1].shape
+        assert np.array_equal(got[_abi.IMPL_AUTO][1], got[VALU][1]), (n, np.count_nonzero(got[_abi.IMPL_AUTO][1] != got[VALU][1]))

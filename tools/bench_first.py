@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Time the float-input first layer of a BASELINE config on its own (HIP events behind queued launches).
 Env: IDX (baseline config index, default 2), N (batch, default 4096), FIXED=1 (fixed-point variant), U8=1 (typed uint8
-image entry, QNN_STORE_U8), QNN_FIRST_ABL (kernel ablations, experiment builds only).
+image entry, QNN_STORE_U8).
 Prints one JSON line: kernel tag, us per launch, fraction of the 157.3 TFLOP/s f32 matrix peak."""
 import importlib
 import json
@@ -62,7 +62,7 @@ for rep in range(5):
     best = min(best, e0.elapsed_time(e1) / 20)
 kh, kw, cin, cout = st["w"].shape
 flops = 2.0 * N * cf.dim * cf.dim * kh * kw * cin * cout
-print(json.dumps({"kernel": abi.last_kernel(), "idx": idx, "N": N, "rotate": ROT, "abl": os.environ.get("QNN_FIRST_ABL", "0"),
+print(json.dumps({"kernel": abi.last_kernel(), "idx": idx, "N": N, "rotate": ROT,
                   "us": round(best * 1e3, 2), "TFLOPs": round(flops / best / 1e9, 1),
                   "GBps": round((x.numel() * x.element_size() + N * (cf.dim // st["pool"]) ** 2 * cout // 2) / best / 1e6, 1),
                   "frac_f32_mfma": round(flops / best / 1e9 / 157.3, 3)}))

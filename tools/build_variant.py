@@ -3,7 +3,6 @@
 the extra compiler flags given for ONE translation unit (or several: a comma-separated list).  Select it at run time with
 QNN_LIB=<path>.
     python tools/build_variant.py wps2 qnn_first.hip -DQNN_FIRST_WPS=2
-    python tools/build_variant.py exp qnn_first_u8.hip,qnn_mfma_areg.hip -DQNN_EXPERIMENTS
 Variants are build artefacts (git-ignored); they travel to the GPU box with gpurun like the main library."""
 import importlib
 import os
