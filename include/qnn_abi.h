@@ -387,6 +387,25 @@ int qnn_conv2d_dense_forward(const qnn_weights_t* wconv, const qnn_weights_t* wd
                              int x_bits, int N, int H, int W, const qnn_epilogue_t* epi_conv,
                              const qnn_epilogue_t* epi_dense, float* y, void* stream);
 
+/*
+ * The classifier tail of models/resnet.py:134-140 (AveragePooling2D(size) -> Flatten -> Dense [-> softmax]) in ONE launch:
+ *     y = softmax(dense(flatten(avgpool_size(x)))),  float32 (N, units)
+ * Bit-identical to qnn_avgpool_packed_f32, qnn_dense_forward (float32 input, handle prepacked for QNN_STORE_F32) and
+ * qnn_softmax_f32 issued one after the other: the averages and the logits never leave the chip.
+ *   x          : DEVICE, packed NHWC codes, x_store = QNN_STORE_BIN | _I4 | _I8, value = code / 2^(x_bits-1) (BIN: +-1)
+ *   wd         : dense handle prepacked for QNN_STORE_F32 with cin == (H/size) * (W/size) * C (flatten order oy, ox, c)
+ *   epi_dense  : bias (from the handle) and BN as qnn_dense_forward applies them; fn NONE, pool 1, float32 output
+ *   softmax    : 0 = y receives the logits (a network without the softmax op)
+ *   logits_or_null : with softmax != 0, the logits are also written here (N, units) unless NULL
+ * QNN_EUNSUPPORTED (issue the three calls): QNN_STORE_T2 input, a handle prepacked for another store, more than 64 KiB of
+ * averages + logits per image (the kernel keeps them in LDS), an epilogue with an activation, pooling, residual or trick.
+ * N == 0 launches nothing (x and y, the pointers of empty tensors, may then be NULL).  qnn_last_kernel(): "tail_avg_dense_softmax" / "tail_avg_dense".
+ * Added without an ABI version step (qnn_version() stays 4): callers that never call it see no change.
+ */
+int qnn_avgpool_dense_softmax_forward(const qnn_weights_t* wd, const void* x, int x_store, int x_bits,
+                                      int N, int H, int W, int C, int size, const qnn_epilogue_t* epi_dense,
+                                      int softmax, float* logits_or_null, float* y, void* stream);
+
 /* Name of the kernel variant the last qnn_conv2d_forward / qnn_dense_forward on
  * this thread dispatched to ("ps_bin_cw2_k3", "generic", "mfma_i8", ...). */
 const char* qnn_last_kernel(void);

@@ -27,7 +27,7 @@ EXPORTS = [
     "qnn_packed_bytes", "qnn_pack_f32", "qnn_unpack_f32", "qnn_avgpool_packed_f32", "qnn_softmax_f32",
     "qnn_prepack_weights", "qnn_free_weights", "qnn_weights_dequant", "qnn_weights_check",
     "qnn_conv2d_forward", "qnn_dense_forward", "qnn_conv2d_forward_f32in", "qnn_conv2d_workspace_bytes",
-    "qnn_conv2d_dense_forward",
+    "qnn_conv2d_dense_forward", "qnn_avgpool_dense_softmax_forward",
     "qnn_fold_prepare", "qnn_fold_free", "qnn_fold_info", "qnn_fold_constants", "qnn_fold_eval",
 ]
 
@@ -59,8 +59,8 @@ class QnnError(RuntimeError):
 
 
 class QnnUnsupported(QnnError):
-    """QNN_EUNSUPPORTED from an optional fused form (a projection shortcut computed inside the launch): the caller keeps
-    the form it had."""
+    """QNN_EUNSUPPORTED from an optional fused form (a projection shortcut computed inside the launch, the classifier tail
+    in one launch): the caller keeps the form it had."""
 
 
 class NotFusable(QnnError):
@@ -116,6 +116,8 @@ def load():
     lib.qnn_dense_forward.argtypes = [vp, vp, ci, ci, ci, ctypes.POINTER(Epilogue), vp, vp]
     lib.qnn_conv2d_dense_forward.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, ctypes.POINTER(Epilogue),
                                              ctypes.POINTER(Epilogue), vp, vp]
+    lib.qnn_avgpool_dense_softmax_forward.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, ci, ctypes.POINTER(Epilogue), ci, vp,
+                                                      vp, vp]
     lib.qnn_fold_prepare.argtypes = [vp, ci, ci, ctypes.POINTER(Epilogue), vp, ctypes.POINTER(vp)]
     lib.qnn_fold_free.argtypes = [vp]
     lib.qnn_fold_info.argtypes = [vp, ctypes.POINTER(FoldInfo)]
@@ -275,6 +277,28 @@ def softmax(x, out=None):
     y = out if out is not None else torch.empty_like(x)
     cols = x.shape[-1]
     check(load().qnn_softmax_f32(ptr(x), ptr(y), x.numel() // cols, cols, stream_ptr()), "qnn_softmax_f32")
+    return y
+
+
+def avgpool_dense_softmax(weights, packed, store, bits, N, H, W, C, size, softmax=True, bn_inv=None, bn_shift=None,
+                          logits=None, out=None, fn=FN_NONE):
+    """qnn_avgpool_dense_softmax_forward: AveragePooling2D(size) -> Flatten -> Dense [-> softmax] of a packed NHWC tensor
+    in one launch (models/resnet.py:134-140), bit-identical to avgpool_packed -> dense (QNN_STORE_F32 handle) -> softmax.
+    Returns the (N, classes) float32 tensor (the logits with softmax=False); `logits`: an (N, classes) float32 tensor
+    that also receives the logits.  Raises QnnUnsupported where the library has no fused kernel: issue the three calls."""
+    classes = weights.shape[3]
+    y = out if out is not None else torch.empty((N, classes), dtype=torch.float32, device=packed.device)
+    for t, what in ((y, "out"), (logits, "logits")):
+        if t is not None and (tuple(t.shape) != (N, classes) or t.dtype != torch.float32 or not t.is_contiguous()
+                              or t.device != packed.device):
+            raise QnnError("avgpool_dense_softmax: `%s` must be a contiguous float32 tensor of shape %s on %s"
+                           % (what, (N, classes), packed.device))
+    epi = make_epilogue(bn_inv, bn_shift, fn, 0, 1, STORE_F32)
+    rc = load().qnn_avgpool_dense_softmax_forward(weights.handle, ptr(packed), store, bits, N, H, W, C, size,
+                                                  ctypes.byref(epi), 1 if softmax else 0, ptr(logits), ptr(y), stream_ptr())
+    if rc == QNN_EUNSUPPORTED:
+        raise QnnUnsupported("qnn_avgpool_dense_softmax_forward: " + load().qnn_last_error().decode(errors="replace"))
+    check(rc, "qnn_avgpool_dense_softmax_forward")
     return y
 
 

@@ -5,8 +5,9 @@
                       model); inter-layer tensors never exist in float32.  What nets.Model runs for a
                       chain, and what bench.py times step by step (steps / run_step / bind).
   ResidualFusedModel  every other topology (ResNet): the same fusion plus the residual merge
-                      conv -> BN -> add(shortcut) -> [x0.5] -> act in one launch, evaluated on demand from the output;
-                      what is not on the low-bit path (avg-pool, softmax, ...) runs as float32 torch ops.  What
+                      conv -> BN -> add(shortcut) -> [x0.5] -> act in one launch, evaluated on demand from the output,
+                      and the classifier tail avg-pool -> Flatten -> Dense -> softmax behind a packed activation in one
+                      launch; what is on neither path runs as float32 torch ops.  What
                       nets.Model runs for everything FusedModel refuses (NotFusable).
   Pipelined           a fused engine's forward with several batches in flight: bound launch plans (FusedModel.bind) or
                       hipGraphs of model(x) per lane.  What nets.Model.predict and bench.py's timed region run.
@@ -136,6 +137,56 @@ class _SpecGraph:
         self.bn = {i: tuple(torch.as_tensor(c).to(self.device) for c in bn_constants(op))
                    for i, op in enumerate(spec) if op["op"] == "bn"}
         self.packed = {}                     # (op index, store) -> _abi.Weights
+        self.tails = {}                      # op index -> tail() of it
+        self.tail_no = set()                 # tails (index of their last op) the library had no fused kernel for
+
+    def _behind(self, name, kind):
+        """Index of the op producing `name` if it is of `kind` and nothing else reads `name`."""
+        i = self.prod.get(name)
+        return i if i is not None and self.spec[i]["op"] == kind and len(self.cons.get(name, [])) == 1 else None
+
+    def tail(self, i):
+        """The classifier tail of models/resnet.py:134-140 that ends in op `i`, as (avgpool, flatten, dense, softmax or
+        None) op indices, or None: `i` is a softmax, or a dense that is the spec's last op, behind dense <- flatten <-
+        avgpool, every link read by the next one alone (nothing else needs the averages or the logits)."""
+        if i not in self.tails:
+            spec, t = self.spec, None
+            sm = i if spec[i]["op"] == "softmax" else None
+            de = self._behind(self.srcs[i][0], "dense") if sm is not None else \
+                i if spec[i]["op"] == "dense" and i == len(spec) - 1 else None
+            fl = self._behind(self.srcs[de][0], "flatten") if de is not None else None
+            ap = self._behind(self.srcs[fl][0], "avgpool") if fl is not None else None
+            if ap is not None:
+                t = (ap, fl, de, sm)
+            self.tails[i] = t
+        return self.tails[i]
+
+    def tail_from(self, ap):
+        """The tail() that starts at avgpool op `ap`, or None (for an interpreter that walks the spec front to back)."""
+        def only(i, kind):
+            c = self.cons.get(self.names[i], []) if i is not None else []
+            return c[0] if len(c) == 1 and self.spec[c[0]]["op"] == kind else None
+        de = only(only(ap, "flatten"), "dense")
+        if de is None:
+            return None
+        sm = only(de, "softmax")
+        t = self.tail(de if sm is None else sm)
+        return t if t is not None and t[0] == ap else None
+
+    def run_tail(self, t, src):
+        """The tail `t` on the packed activation `src` in ONE launch (qnn_avgpool_dense_softmax_forward: bit-identical to
+        avgpool_packed -> dense on the QNN_STORE_F32 handle -> softmax), or None where the library has no fused kernel
+        (remembered: it is asked once) -- the caller then runs the ops one by one, as both interpreters did before."""
+        ap, _, de, sm = t
+        end = de if sm is None else sm
+        if end in self.tail_no or src.store not in (_abi.STORE_BIN, _abi.STORE_I4, _abi.STORE_I8):
+            return None
+        try:
+            return _abi.avgpool_dense_softmax(self.weights(de, _abi.STORE_F32), src.t, src.store, src.bits, *src.shape,
+                                              self.spec[ap].get("size", 8), softmax=sm is not None)
+        except _abi.QnnUnsupported:
+            self.tail_no.add(end)
+            return None
 
     def weights(self, i, store):
         if (i, store) not in self.packed:
@@ -580,6 +631,22 @@ class GraphModel:
         self.device = torch.device(device)
         self.spec = spec
         self.graph = _SpecGraph(spec, device)
+        self.fuse_tail = True                # avg-pool + Flatten + Dense [+ softmax] in one launch (_SpecGraph.run_tail)
+
+    def _tail(self, i, src):
+        """The classifier tail that starts at avgpool op `i`, fused: (its op indices, result) or None.  The clip in front
+        of it is packed as its other consumers pack it on load."""
+        t = self.graph.tail_from(i) if self.fuse_tail and isinstance(src, _Virtual) else None
+        if t is None or src.fn not in (_abi.FN_BINARY_TANH, _abi.FN_QUANTIZED_TANH):
+            return None
+        end = t[2] if t[3] is None else t[3]
+        if end in self.graph.tail_no:
+            return None
+        bits = 1 if src.fn == _abi.FN_BINARY_TANH else src.nb
+        store = _abi.STORE_BIN if bits == 1 else _abi.store_for_bits(bits)
+        xp = _Packed(_abi.pack(src.pre, src.pre.shape[-1], src.fn, bits, store), store, bits, src.pre.shape)
+        y = self.graph.run_tail(t, xp)
+        return None if y is None else (t, y)
 
     @staticmethod
     def _plain(t):
@@ -626,7 +693,12 @@ class GraphModel:
                 continue
             kind, name = op["op"], g.names[i]
             src = env[g.srcs[i][0]]
-            if kind in ("conv", "dense"):
+            fused = self._tail(i, src) if kind == "avgpool" else None
+            if fused is not None:
+                t, y = fused
+                skip.update(k for k in t[1:] if k is not None)      # flatten, dense, softmax: nothing else reads them
+                name = g.names[t[2] if t[3] is None else t[3]]
+            elif kind in ("conv", "dense"):
                 # fuse an immediately following BN that is this tensor's only consumer
                 inv = shift = None
                 if g.cons.get(name, []) == [i + 1] and spec[i + 1]["op"] == "bn":
@@ -707,7 +779,9 @@ class ResidualFusedModel(_DomainFlag):
     launch whose epilogue reads the shortcut (packed codes of the previous activation, or the
     float32 output of the 1x1 projection) and writes the next activation packed.  Evaluation is
     demand-driven from the output so the shortcut operand is always computed before the conv
-    that merges it.  Anything that is not on the low-bit path (avg-pool, softmax, ...) runs as
+    that merges it.  The classifier tail AveragePooling2D -> Flatten -> Dense [-> softmax]
+    (models/resnet.py:134-140) behind a packed activation is one launch as well (fuse_tail,
+    qnn_avgpool_dense_softmax_forward).  Anything else that is not on the low-bit path runs as
     float32 torch ops on unpacked tensors.
     """
 
@@ -729,6 +803,7 @@ class ResidualFusedModel(_DomainFlag):
         self._folds = {}                     # (conv, bn, shortcut kind, ...) -> _abi.Fold or None
         self.fuse_projection = bool(fuse_projection)   # projection shortcuts inside the second conv's launch (qnn_projection_t)
         self._proj_ok = {}                   # conv index -> False once the library had no kernel for the pair
+        self.fuse_tail = True                # avg-pool + Flatten + Dense [+ softmax] in one launch (_SpecGraph.run_tail)
         self._plans = {}                     # tensor name -> what _plan() matched in front of it
         self.device = torch.device(device)
         g = self.graph = _SpecGraph(spec, device)
@@ -983,6 +1058,14 @@ class ResidualFusedModel(_DomainFlag):
             return _add(self._f32(memo, s0), self._f32(memo, self.srcs[i][1]))
         if kind != "dense" and kind not in _GLUE:
             raise ValueError(kind)
+        tail = self.graph.tail(i) if self.fuse_tail and kind in ("dense", "softmax") else None
+        if tail is not None:
+            # the classifier tail behind a packed activation: one launch; declined (remembered) or not packed: the ops
+            # below, one by one, as before
+            pooled = self._ev(memo, self.srcs[tail[0]][0])
+            y = self.graph.run_tail(tail, pooled) if isinstance(pooled, _Packed) else None
+            if y is not None:
+                return y
         src = self._ev(memo, s0)
         if isinstance(src, _Packed):         # the ops that read packed words as they are
             if kind == "dense" and _wstore(op) is not None:

@@ -2,7 +2,8 @@
 """BASELINE config 5: synthetic ImageNet-224 ResNet (nres=10, pfilt=1) full-qnn 4/4 through GraphModel.
 Environment: B (batch, 64), CHECK (1: one image against the oracle first), WBITS / ABITS (other full-qnn widths, e.g. 8 / 8),
 DIM / NRES (e.g. DIM=32 NRES=3: the CIFAR ResNet-20), PREDICT=1 (time nets.Model(...).predict on IMAGES resident images, the
-product call with its hipGraph lanes, instead of GraphModel)."""
+product call with its hipGraph lanes, instead of GraphModel), FUSE_TAIL=0 (with PREDICT=1: the classifier tail as three
+launches instead of one)."""
 import importlib, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -23,6 +24,7 @@ if os.environ.get("PREDICT") == "1":
     n = int(os.environ.get("IMAGES", str(8 * B)))
     m = nets.Model(cf, spec)
     m.engine.kernel_log = []
+    m.engine.fuse_tail = os.environ.get("FUSE_TAIL", "1") == "1"
     x = torch.as_tensor(nets.synthetic_images(cf, n, 6)).cuda()
     m.engine(x[:min(B, 4)])
     kernels = sorted(set(m.engine.kernel_log))
