@@ -149,7 +149,8 @@ struct ConvCall {
     hipStream_t s;
     bool dense;
 };
-// the matrix-pipe routes of qnn_mfma.hip: 0 = launched (and `name` set), 1 = declined
+// the matrix-pipe routes: 0 = launched (and `name` set), 1 = declined.  qnn_route_first_f32 and qnn_route_gemm are in
+// qnn_mfma.hip, qnn_route_strip is in qnn_route_strip.hip.
 int qnn_route_first_f32(const ConvCall& c, char* name, size_t name_len);
 int qnn_route_strip(const ConvCall& c, char* name, size_t name_len);
 int qnn_route_gemm(const ConvCall& c, char* name, size_t name_len);

@@ -23,6 +23,7 @@
 #include <type_traits>
 
 #include "qnn_mfma_common.h"
+#include "qnn_strip_plan.h"
 
 namespace {
 
@@ -271,27 +272,16 @@ int qnn_try_launch_first_fixed(const ConvGeom& g, const EpiArgs& e, const void* 
     const int spr = g.W / 16;
     const double img_x = (double)g.H * g.W * 3 * 4.0;
     if (img_x >= 1.0e9 || (double)g.N * g.Hp * g.Wp * 8.0 >= 2.0e9 * 4) return 1;
-    const int hp2 = g.H / 2;
-    const int blocks_cap = 256 * 4;                          // persistent grid: four workgroups per CU
-    const long nwaves = (long)blocks_cap * 4;
-    int best_rc = hp2, best_nch = 1;
-    double best_cost = 1e300;
-    for (int rc = 2; rc <= hp2 + 1; rc += 2) {              // even: every chunk starts on an even row pair
-        const int nch = (hp2 + rc - 1) / rc;
-        const long rounds = ((long)g.N * spr * nch + nwaves - 1) / nwaves;
-        const double cost = (double)rounds * (rc + 1.5);
-        if (cost < best_cost) { best_cost = cost; best_rc = rc; best_nch = nch; }
-    }
-    const long ntasks_l = (long)g.N * spr * best_nch;
-    if (ntasks_l >= 2000000000L) return 1;
-    long blocks = (ntasks_l + 3) / 4;
-    if (blocks > blocks_cap) blocks = blocks_cap;
-    const dim3 grid((unsigned)blocks), block(256);
+    // persistent grid: four workgroups per CU.  The walk is over row pairs, an even number per task (every chunk starts
+    // on an even row pair); 1.5 pairs of fill
+    StripPlan p;
+    if (!qnn_strip_plan(&p, g.N, spr, g.H / 2, 256 * 4, 1.5, 2)) return 1;
+    const dim3 grid(p.blocks), block(256);
     const size_t lds = (size_t)4 * kWaveLds * 4 + 4 * 64 * 2 * 16;
 #define FIXED_LAUNCH(OUT_, POOL_, BIN_)                                                                                   \
     hipLaunchKernelGGL((k_conv_first_fixed<OUT_, POOL_, BIN_>), grid, block, lds, s, g, e, (const float*)x, w->d_wq, y,    \
-                       (int)ntasks_l, spr, qnn_fastdiv((uint32_t)spr), best_nch, qnn_fastdiv((uint32_t)best_nch), best_rc, \
-                       (uint32_t)img_x, wscale, vscale, 1.0f / vscale, (e.dom_flag ? e.dom_flag : w->d_flag))
+                       QNN_STRIP_PLAN_ARGS(p), (uint32_t)img_x, wscale, vscale, 1.0f / vscale,                              \
+                       (e.dom_flag ? e.dom_flag : w->d_flag))
     if (!fused) FIXED_LAUNCH(QNN_STORE_F32, 1, false);
     else if (e.fn == QNN_FN_BINARY_TANH) FIXED_LAUNCH(QNN_STORE_I4, 2, true);
     else FIXED_LAUNCH(QNN_STORE_I4, 2, false);

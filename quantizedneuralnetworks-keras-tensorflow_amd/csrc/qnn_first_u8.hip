@@ -20,6 +20,7 @@
 // channels with negative BN scale are negated, A[c] with them).
 #include "qnn_mfma_common.h"
 #include "qnn_fold.h"
+#include "qnn_strip_plan.h"
 
 namespace {
 
@@ -579,39 +580,27 @@ int qnn_try_launch_first_u8(const ConvGeom& g, const EpiArgs& e, const void* x, 
     const double img_x = (double)g.H * g.W * 3 * (f32in ? 4 : 1);
     const float D = 255.0f * wscale;                             // the divisor of the affine map (qnn_abi.h)
     if (img_x >= 1.0e9 || (double)g.N * g.Hp * g.Wp * 8.0 >= 2.0e9 * 4) return 1;
-    const int hp2 = g.H / 2;
     const bool fused = g.cout == 64 && w->wshift <= 6 && g.pool == 2 && e.out_store == QNN_STORE_I4 &&
                        ((e.fn == QNN_FN_QUANTIZED_TANH && e.act_m <= 8.0f) || e.fn == QNN_FN_BINARY_TANH);
     const bool full = !fused && g.pool == 1 && e.out_store != QNN_STORE_F32;
     // persistent grid = what is resident: four workgroups per CU (three for the un-pooled packed form, launch bounds)
     const int blocks_cap = 256 * (full ? (g.cout == 16 ? 6 : 3) : 4);
-    const long nwaves = (long)blocks_cap * 4;
-    int best_rc = hp2, best_nch = 1;
-    double best_cost = 1e300;
-    for (int rc = 2; rc <= hp2 + 1; rc += 2) {              // even: every chunk starts on an even row pair
-        const int nch = (hp2 + rc - 1) / rc;
-        const long rounds = ((long)g.N * spr * nch + nwaves - 1) / nwaves;
-        const double cost = (double)rounds * (rc + 1.5);
-        if (cost < best_cost) { best_cost = cost; best_rc = rc; best_nch = nch; }
-    }
-    const long ntasks_l = (long)g.N * spr * best_nch;
-    if (ntasks_l >= 2000000000L) return 1;
-    long blocks = (ntasks_l + 3) / 4;
-    if (blocks > blocks_cap) blocks = blocks_cap;
-    const dim3 grid((unsigned)blocks), block(256);
+    // the walk is over row pairs, an even number per task (every chunk starts on an even row pair); 1.5 pairs of fill
+    StripPlan p;
+    if (!qnn_strip_plan(&p, g.N, spr, g.H / 2, blocks_cap, 1.5, 2)) return 1;
+    const dim3 grid(p.blocks), block(256);
     const size_t lds = (size_t)4 * kWaveLdsU * 4 + 4 * 64 * 2 * 16;
     if (full && !fused) {
         if ((double)g.H * g.W * e.ocw * 4.0 >= 2.0e9) return 1;
         const int nblk = g.cout == 16 ? 1 : 4;
         const int gy = g.cout / (16 * nblk);
         long bx = blocks_cap / gy > 0 ? blocks_cap / gy : 1;
-        if (bx > (ntasks_l + 3) / 4) bx = (ntasks_l + 3) / 4;
+        if (bx > (p.ntasks + 3L) / 4) bx = (p.ntasks + 3L) / 4;
         const dim3 fgrid((unsigned)bx, (unsigned)gy);
         const bool bin = e.fn == QNN_FN_BINARY_TANH;
 #define U8_FULL(OUT_, NB_, BIN_, F32_)                                                                                      \
         hipLaunchKernelGGL((k_conv_first_u8_full<OUT_, NB_, BIN_, F32_>), fgrid, block, lds, s, g, e, x, w->d_wq, y,         \
-                           (int)ntasks_l, spr, qnn_fastdiv((uint32_t)spr), best_nch, qnn_fastdiv((uint32_t)best_nch),       \
-                           best_rc, (uint32_t)img_x, wscale, D, (e.dom_flag ? e.dom_flag : w->d_flag))
+                           QNN_STRIP_PLAN_ARGS(p), (uint32_t)img_x, wscale, D, (e.dom_flag ? e.dom_flag : w->d_flag))
 #define U8_FULL_B(OUT_, NB_)                                                                                                \
         do {                                                                                                               \
             if (bin) { if (f32in) U8_FULL(OUT_, NB_, true, true); else U8_FULL(OUT_, NB_, true, false); }                   \
@@ -627,24 +616,20 @@ int qnn_try_launch_first_u8(const ConvGeom& g, const EpiArgs& e, const void* x, 
     do {                                                                                                                   \
         if (f32in)                                                                                                         \
             hipLaunchKernelGGL((k_conv_first_u8<OUT_, POOL_, BIN_, true>), grid, block, lds, s, g, e, x, w->d_wq, y,        \
-                               (int)ntasks_l, spr, qnn_fastdiv((uint32_t)spr), best_nch, qnn_fastdiv((uint32_t)best_nch),  \
-                               best_rc, (uint32_t)img_x, wscale, D, (e.dom_flag ? e.dom_flag : w->d_flag));                                            \
+                               QNN_STRIP_PLAN_ARGS(p), (uint32_t)img_x, wscale, D, (e.dom_flag ? e.dom_flag : w->d_flag)); \
         else                                                                                                               \
             hipLaunchKernelGGL((k_conv_first_u8<OUT_, POOL_, BIN_, false>), grid, block, lds, s, g, e, x, w->d_wq, y,       \
-                               (int)ntasks_l, spr, qnn_fastdiv((uint32_t)spr), best_nch, qnn_fastdiv((uint32_t)best_nch),  \
-                               best_rc, (uint32_t)img_x, wscale, D, (e.dom_flag ? e.dom_flag : w->d_flag));                                            \
+                               QNN_STRIP_PLAN_ARGS(p), (uint32_t)img_x, wscale, D, (e.dom_flag ? e.dom_flag : w->d_flag)); \
     } while (0)
     if (!fused) U8_LAUNCH(QNN_STORE_F32, 1, false);
     else if (e.fn == QNN_FN_BINARY_TANH) U8_LAUNCH(QNN_STORE_I4, 2, true);
     else if (e.fold_a && e.fold_c && e.act_m == 8.0f) {       // folded epilogue (mode 3 handle of this layer, qnn_fold.h)
         if (f32in)
             hipLaunchKernelGGL((k_conv_first_u8<QNN_STORE_I4, 2, false, true, true>), grid, block, lds, s, g, e, x, w->d_wq, y,
-                               (int)ntasks_l, spr, qnn_fastdiv((uint32_t)spr), best_nch, qnn_fastdiv((uint32_t)best_nch),
-                               best_rc, (uint32_t)img_x, wscale, D, (e.dom_flag ? e.dom_flag : w->d_flag));
+                               QNN_STRIP_PLAN_ARGS(p), (uint32_t)img_x, wscale, D, (e.dom_flag ? e.dom_flag : w->d_flag));
         else
             hipLaunchKernelGGL((k_conv_first_u8<QNN_STORE_I4, 2, false, false, true>), grid, block, lds, s, g, e, x, w->d_wq, y,
-                               (int)ntasks_l, spr, qnn_fastdiv((uint32_t)spr), best_nch, qnn_fastdiv((uint32_t)best_nch),
-                               best_rc, (uint32_t)img_x, wscale, D, (e.dom_flag ? e.dom_flag : w->d_flag));
+                               QNN_STRIP_PLAN_ARGS(p), (uint32_t)img_x, wscale, D, (e.dom_flag ? e.dom_flag : w->d_flag));
     }
     else U8_LAUNCH(QNN_STORE_I4, 2, false);
 #undef U8_LAUNCH

@@ -752,13 +752,13 @@ int qnn_mfma_prepare_weights(qnn_weights* w, hipStream_t s) {
     w->d_fp6_wsum = nullptr;
     const bool small = w->store == QNN_STORE_I4 && (w->cin == 16 || w->cin == 32) && (w->cout % 16) == 0 &&
                        w->kh == 3 && w->kw == 3;
-    // the 1x1 strides-2 projection of a ResNet stage (models/resnet.py:117-124): read by the strip kernel of the block's
-    // second convolution when the shortcut is computed inside that launch (qnn_projection_t); no kernel of this file
-    // runs such a layer on its own
+    // the 1x1 strides-2 projection of a ResNet stage (models/resnet.py:117-124): read by the kernel qnn_route_strip picks
+    // for the block's second convolution when the shortcut is computed inside that launch (qnn_projection_t); no kernel
+    // of this file runs such a layer on its own
     const bool proj = w->store == QNN_STORE_I4 && (w->cin == 16 || w->cin == 32) && w->cout == 2 * w->cin &&
                       w->kh == 1 && w->kw == 1 && w->stride == 2;
-    // int8-stored 3x3 layers with 16 / 32 input channels: the int8 strip kernels (qnn_mfma_strip_i8.hip) read the codes
-    // as they are packed
+    // int8-stored 3x3 layers with 16 / 32 input channels: the int8 kernels of qnn_route_strip read the codes as they
+    // are packed
     const bool small8 = w->store == QNN_STORE_I8 && (w->cin == 16 || w->cin == 32) && (w->cout % 16) == 0 &&
                         w->kh == 3 && w->kw == 3;
     if (!small && !small8 && !proj && (w->cin % 64 != 0 || w->cout % 64 != 0)) return QNN_OK;
@@ -794,7 +794,8 @@ int qnn_route_first_f32(const ConvCall& c, char* name, size_t name_len) {
     if (g.cout != 64 && g.cout != 128 && g.cout != 256) return 1;
     const int pw = e.out_store == QNN_STORE_F32 ? 1 : qnn_per_word(e.out_store);
     if (g.cout % pw != 0) return 1;
-    // opt-in fixed-point variant (qnn_first_fixed.hip): NOT the oracle's float32 chain, see its header
+    // input declared QNN_STORE_F32_UNIT (first_mode 2): the fixed-point variant (qnn_first_fixed.hip), NOT the oracle's
+    // float32 chain, see its header
     if (e.first_mode == 2 && qnn_try_launch_first_fixed(g, e, c.x, c.w, c.y, c.s) == 0) {
         snprintf(name, name_len, "mfma_i8x3_first_fixed");
         return 0;
@@ -806,114 +807,6 @@ int qnn_route_first_f32(const ConvCall& c, char* name, size_t name_len) {
                             (g.pool == 1 && (g.W % 32) == 0));
     if (lds_shape || g.cout == 64) return qnn_launch_first(g.cin, 2, g, e, c.x, c.w->d_wq, c.y, c.s);
     return qnn_launch_first(g.cin, 4, g, e, c.x, c.w->d_wq, c.y, c.s);
-}
-
-// int8-stored activations and weights, 3x3, 16 / 32 (/ 64) input channels, un-pooled int8 output: the int8 row-walking
-// strip kernels (qnn_mfma_strip_i8.hip).  Everything else with int8 operands stays where it was: pooled layers and
-// Cin = 64 on the tiled family (qnn_route_gemm), float32 or int4 outputs and 16 / 32 channels on k_conv_ps.
-static int route_strip_i8(const ConvCall& c, char* name, size_t name_len) {
-    const ConvGeom& g = c.g;
-    const EpiArgs& e = c.e;
-    const qnn_weights* w = c.w;
-    if (w->store != QNN_STORE_I8 || (e.flags & QNN_EPI_NO_STRIP) || e.fold_a || e.proj_x) return 1;
-    int pexp = 0;
-    // the residual's post-scale (models/resnet.py:128: 0.5) folds into the activation's code scale: a power of two
-    const bool pow2 = !e.res || (e.post_scale > 0.0f && frexpf(e.post_scale, &pexp) == 0.5f);
-    const int cmul = g.cin == 16 ? 16 : 32;
-    const bool s1 = g.stride == 1 && g.pt == 1 && g.pl == 1 && (g.cin == 16 || g.cin == 32 || g.cin == 64) &&
-                    (g.cout % cmul) == 0;
-    const bool s2 = g.stride == 2 && (g.cin == 16 || g.cin == 32) && (g.cout % 32) == 0 && !e.res;
-    // Accumulator bound: K = 9 * Cin <= 576 products of two codes in [-128, 127]: |acc| <= 576 * 128 * 128 = 9 437 184
-    // < 2^24, so the kernels' int -> float32 conversion is exact (as the reference's float32 sum of the same products).
-    static_assert(576L * 128 * 128 < (1L << 24), "int8 strip kernels: accumulators must convert to float32 exactly");
-    const bool shape = g.kh == 3 && g.kw == 3 && (s1 || s2) && g.pool == 1 && e.out_store == QNN_STORE_I8 && pow2 &&
-                       (!e.res || (e.res_store == QNN_STORE_I8 && e.res_cw == e.ocw) ||
-                        (e.res_store == QNN_STORE_F32 && e.res_cw == g.cout));
-    // Cin 64 has a matrix-pipe kernel already (mfma_i8_areg64x64 for Cout = 64): QNN_EPI_NO_STRIP64 keeps it (the A/B
-    // switch, as on the int4 path); the two times are in DESIGN 3.2
-    const bool want = g.cin != 64 || !(e.flags & QNN_EPI_NO_STRIP64);
-    if (!shape || !want) return 1;
-    MfmaGeom ms;
-    ms.g = g; ms.kc = 1; ms.steps = 0; ms.x_pix_bytes = g.cin;
-    ms.total_q = (long)g.N * g.Ho * g.Wo;
-    const double wb_ = (double)g.cout * 9 * g.cin;
-    if (wb_ >= 2.0e9) return 1;
-    ms.x_bytes = 0; ms.w_bytes = (uint32_t)wb_;
-    snprintf(name, name_len, g.stride == 2 ? "strip_i8_c%d_s2" : "strip_i8_c%d", g.cin);
-    return qnn_launch_strip_i8(g.cin, ms, e, c.x, w->d_mfma, c.y, c.s);
-}
-
-// 3x3 layers with 16 / 32 / 64 input channels: the row-walking strip kernels (int4, int8), then the small-channel tile kernel
-int qnn_route_strip(const ConvCall& c, char* name, size_t name_len) {
-    const ConvGeom& g = c.g;
-    const EpiArgs& e = c.e;
-    const qnn_weights* w = c.w;
-    if (!w->d_mfma) return 1;
-    if (c.x_store == QNN_STORE_I8) return route_strip_i8(c, name, name_len);
-    if (c.x_store != QNN_STORE_I4) return 1;
-    // 3x3 stride-1 int4 layers with 16 / 32 / 64 input channels: row-walking strip kernel (qnn_mfma_strip.hip).
-    // The residual's post-scale (models/resnet.py:128: 0.5) must be a power of two so that it folds exactly into the
-    // activation's code scale.
-    {
-        int pexp = 0;
-        const bool pow2 = (!e.res && !e.proj_x) || (e.post_scale > 0.0f && frexpf(e.post_scale, &pexp) == 0.5f);
-        const int cmul = g.cin == 16 ? 16 : 32;
-        // stride 2 (the first conv of a stage: no residual, Cin 16 / 32, Cout a multiple of 32): the same walk over
-        // output rows, three fresh input rows per output row
-        const bool s1 = g.stride == 1 && g.pt == 1 && g.pl == 1 && (g.cout % cmul) == 0;
-        const bool s2 = g.stride == 2 && (g.cin == 16 || g.cin == 32) && (g.cout % 32) == 0 && !e.res;
-        const bool proj_ok = !e.proj_x || (s1 && (g.cin == 32 || g.cin == 64) && g.cout == g.cin && e.proj_cin * 2 == g.cin &&
-                                           !e.res && !e.fold_a && (e.proj_H + 1) / 2 == g.H && (e.proj_W + 1) / 2 == g.W);
-        const bool shape = w->store == QNN_STORE_I4 && proj_ok &&
-                           (g.cin == 16 || g.cin == 32 || g.cin == 64) && g.kh == 3 && g.kw == 3 && (s1 || s2) &&
-                           g.pool == 1 && e.out_store == QNN_STORE_I4 && pow2 &&
-                           (!e.res || (e.res_store == QNN_STORE_I4 && e.res_cw == e.ocw) ||
-                            (e.res_store == QNN_STORE_F32 && e.res_cw == g.cout));
-        // Cin 64 (auto): every un-pooled layer.  Measured, 64 x 56^2 / 4096 x 16^2 pixels, round 3 (one 32-bit store and one
-        // shortcut load per row): with the merge 13.9 us here against 36.4 us on the LDS-weight kernel, without it
-        // 13.1 / 43.5 against 14.0 / 46.5 (round 2, two 16-bit accesses per row: 16.3 / 54.6 against 14.1 / 47.3).
-        const bool want = g.cin == 64 ? !(e.flags & QNN_EPI_NO_STRIP64) : true;
-        if (shape && want && !(e.flags & QNN_EPI_NO_STRIP)) {
-            MfmaGeom ms;
-            ms.g = g; ms.kc = 1; ms.steps = 0; ms.x_pix_bytes = g.cin / 2;
-            ms.total_q = (long)g.N * g.H * g.W;
-            const double wb_ = (double)g.cout * 9 * g.cin;
-            if (wb_ < 2.0e9) {
-                ms.x_bytes = 0; ms.w_bytes = (uint32_t)wb_;
-                EpiArgs es = e;
-                es.scale = e.scale * (1.0f / 256.0f);        // both operands carry *16
-                es.proj_scale = e.proj_scale * (1.0f / 256.0f);
-                // 16 -> 16 channels with a usable fold and an even width: the LDS-staged form (qnn_mfma_strip16.hip: a sixth
-                // of the load and a quarter of the store instructions)
-                if (g.cin == 16 && !(e.flags & QNN_EPI_NO_LDS16) && qnn_launch_strip16_lds(ms, es, c.x, w->d_mfma, c.y, c.s) == 0) {
-                    snprintf(name, name_len, "strip_i4_c16_lds");
-                    return 0;
-                }
-                snprintf(name, name_len, g.stride == 2 ? "strip_i4_c%d_s2" : e.proj_x ? "strip_i4_c%d_proj" : "strip_i4_c%d", g.cin);
-                if (qnn_launch_strip(g.cin, ms, es, c.x, w->d_mfma, c.y, c.s) == 0) return 0;
-            }
-        }
-    }
-    // small-channel 3x3 int4 layers on the tile kernel (both operands in registers)
-    if (e.proj_x) return 1;      // the in-launch projection shortcut exists in the strip kernel only
-    if (w->store == QNN_STORE_I4 && (g.cin == 16 || g.cin == 32) && g.kh == 3 &&
-        g.kw == 3 && g.stride == 1 && g.pt == 1 && g.pl == 1 && g.pool == 1 && (g.W % 16) == 0 &&
-        e.out_store == QNN_STORE_I4 && (g.cout % (g.cin == 16 ? 16 : 32)) == 0 &&
-        (!e.res || (e.res_store == QNN_STORE_I4 && e.res_cw == e.ocw) ||
-         (e.res_store == QNN_STORE_F32 && e.res_cw == g.cout))) {
-        MfmaGeom ms;
-        ms.g = g; ms.kc = 1; ms.steps = 0; ms.x_pix_bytes = g.cin / 2;
-        ms.total_q = (long)g.N * g.H * g.W;
-        const double xb_ = (double)g.N * g.H * g.W * ms.x_pix_bytes, wb_ = (double)g.cout * 9 * g.cin;
-        if (xb_ < 2.0e9 && wb_ < 2.0e9) {
-            ms.x_bytes = (uint32_t)xb_; ms.w_bytes = (uint32_t)wb_;
-            EpiArgs es = e;
-            es.scale = e.scale * (1.0f / 256.0f);            // both operands carry *16
-            snprintf(name, name_len, "mfma_i4_small_c%d", g.cin);
-            if (qnn_launch_small(g.cin, ms, es, c.x, w->d_mfma, c.y, c.s) == 0) return 0;
-        }
-    }
-    return 1;
 }
 
 // the tiled implicit-GEMM family (Cin and Cout multiples of 64): halo, operands in registers, weight-resident, tiles

@@ -36,6 +36,7 @@
 // loads and stores get out-of-range offsets).
 #include "qnn_mfma_common.h"
 #include "qnn_fold.h"
+#include "qnn_strip_plan.h"
 
 #ifndef QNN_STRIP16_WPS
 #define QNN_STRIP16_WPS 6        // waves per SIMD (= persistent workgroups per CU): Cin 16 needs 51-67 VGPRs
@@ -627,38 +628,21 @@ int launch_strip_s2(const MfmaGeom& mg, const EpiArgs& e, const void* x, const u
     const double img_x = (double)g.H * g.W * (CIN / 2), img_y = (double)g.Ho * g.Wo * e.ocw * 4.0;
     if (img_x >= 1.0e9 || img_y >= 1.0e9 || ny < 1 || ny * 16 * NT != g.cout) return 1;
     const int wps = CIN == 16 ? 4 : 2;
-    const int blocks_cap = 256 * wps / ny > 0 ? 256 * wps / ny : 1;
-    const long nwaves = (long)blocks_cap * 4;
-    int best_rc = g.Ho, best_nch = 1;
-    double best_cost = 1e300;
-    for (int rc = g.Ho < 4 ? g.Ho : 4; rc <= g.Ho; ++rc) {
-        const int nch = (g.Ho + rc - 1) / rc;
-        const long rounds = ((long)g.N * spr * nch + nwaves - 1) / nwaves;
-        const double cost = (double)rounds * (rc + 2);
-        if (cost < best_cost) { best_cost = cost; best_rc = rc; best_nch = nch; }
+    StripPlan p;                // over output rows
+    if (!qnn_strip_plan(&p, g.N, spr, g.Ho, 256 * wps / ny > 0 ? 256 * wps / ny : 1, 2, 1)) return 1;
+    const dim3 grid(p.blocks, (unsigned)ny), block(256);
+    // a fold contains the bias: "bits" form (2), float form (1), else the plain epilogue with or without a bias
+    const int fold = !e.fold_a ? 0 : e.fold_c ? 2 : 1;
+    const bool bias = !fold && e.bias;
+#define STRIP_S2_CASE(BIAS_, FOLD_)                                                                                       \
+    if (bias == BIAS_ && fold == FOLD_) {                                                                                 \
+        hipLaunchKernelGGL((k_conv_strip_s2<CIN, NT, BIAS_, FOLD_>), grid, block, 0, s, mg, e, (const uint8_t*)x, w, y,   \
+                           QNN_STRIP_PLAN_ARGS(p), (uint32_t)img_x, (uint32_t)img_y);                                     \
+        return 0;                                                                                                         \
     }
-    const long ntasks_l = (long)g.N * spr * best_nch;
-    if (ntasks_l >= 2000000000L) return 1;
-    long blocks = (ntasks_l + 3) / 4;
-    if (blocks > blocks_cap) blocks = blocks_cap;
-    const dim3 grid((unsigned)blocks, (unsigned)ny), block(256);
-    if (e.fold_a && e.fold_c)   // folded epilogue (the bias is inside the fold), "bits" form
-        hipLaunchKernelGGL((k_conv_strip_s2<CIN, NT, false, 2>), grid, block, 0, s, mg, e, (const uint8_t*)x, w, y, (int)ntasks_l,
-                           spr, qnn_fastdiv((uint32_t)spr), best_nch, qnn_fastdiv((uint32_t)best_nch), best_rc,
-                           (uint32_t)img_x, (uint32_t)img_y);
-    else if (e.fold_a)
-        hipLaunchKernelGGL((k_conv_strip_s2<CIN, NT, false, 1>), grid, block, 0, s, mg, e, (const uint8_t*)x, w, y, (int)ntasks_l,
-                           spr, qnn_fastdiv((uint32_t)spr), best_nch, qnn_fastdiv((uint32_t)best_nch), best_rc,
-                           (uint32_t)img_x, (uint32_t)img_y);
-    else if (e.bias)
-        hipLaunchKernelGGL((k_conv_strip_s2<CIN, NT, true, 0>), grid, block, 0, s, mg, e, (const uint8_t*)x, w, y, (int)ntasks_l,
-                           spr, qnn_fastdiv((uint32_t)spr), best_nch, qnn_fastdiv((uint32_t)best_nch), best_rc,
-                           (uint32_t)img_x, (uint32_t)img_y);
-    else
-        hipLaunchKernelGGL((k_conv_strip_s2<CIN, NT, false, 0>), grid, block, 0, s, mg, e, (const uint8_t*)x, w, y, (int)ntasks_l,
-                           spr, qnn_fastdiv((uint32_t)spr), best_nch, qnn_fastdiv((uint32_t)best_nch), best_rc,
-                           (uint32_t)img_x, (uint32_t)img_y);
-    return 0;
+    STRIP_S2_CASE(false, 2) STRIP_S2_CASE(false, 1) STRIP_S2_CASE(true, 0) STRIP_S2_CASE(false, 0)
+#undef STRIP_S2_CASE
+    return 1;                   // not reached: (bias, fold) takes exactly the four values above
 }
 
 template <int CIN, int NT>
@@ -672,32 +656,18 @@ int launch_strip(const MfmaGeom& mg, const EpiArgs& e, const void* x, const uint
                          : res == 3 ? (double)e.proj_H * e.proj_W * (CIN / 4) : img_y;
     if (res == 3 && (NT != 2 || CIN < 32 || e.proj_cin * 2 != CIN)) return 1;
     if (img_x >= 1.0e9 || img_y >= 1.0e9 || img_r >= 1.0e9 || ny < 1 || ny * 16 * NT != g.cout) return 1;
-    // persistent grid: WPS waves per SIMD; rows per task chosen so that the task count fills whole
-    // rounds of that grid (a round costs rc output rows + 3 rows of pipeline fill)
+    // persistent grid: WPS waves per SIMD.  Both arguments are known to be stale and kept as measured (changing them
+    // changes grid sizes): the fill of 3 rows dates from the three-row ring, today's ring of D rows fills in D + 2; and
+    // the float32-residual (RES 2) kernels of the 32-channel stage are bounded for two waves per SIMD while wps says 1.
     const int wps = CIN == 16 ? QNN_STRIP16_WPS : CIN == 32 ? QNN_STRIP32_WPS : QNN_STRIP64_WPS;
-    const int blocks_cap = 256 * wps / ny > 0 ? 256 * wps / ny : 1;
-    const long nwaves = (long)blocks_cap * 4;
-    int best_rc = g.H, best_nch = 1;
-    double best_cost = 1e300;
-    for (int rc = g.H < 4 ? g.H : 4; rc <= g.H; ++rc) {
-        const int nch = (g.H + rc - 1) / rc;
-        const long tasks = (long)g.N * spr * nch;
-        const long rounds = (tasks + nwaves - 1) / nwaves;
-        const double cost = (double)rounds * (rc + 3);
-        if (cost < best_cost) { best_cost = cost; best_rc = rc; best_nch = nch; }
-    }
-    const long ntasks_l = (long)g.N * spr * best_nch;
-    if (ntasks_l >= 2000000000L) return 1;
-    const int ntasks = (int)ntasks_l;
-    long blocks = (ntasks + 3) / 4;
-    if (blocks > blocks_cap) blocks = blocks_cap;
-    const dim3 grid((unsigned)blocks, (unsigned)ny), block(256);
+    StripPlan p;
+    if (!qnn_strip_plan(&p, g.N, spr, g.H, 256 * wps / ny > 0 ? 256 * wps / ny : 1, 3, 1)) return 1;
+    const dim3 grid(p.blocks, (unsigned)ny), block(256);
     const bool bias = e.bias != nullptr && !(e.fold_a != nullptr && res < 2);   // a fold contains the bias
 #define STRIP_CASE(RES_, BIAS_, FOLD_)                                                                        \
     if (res == RES_ && bias == BIAS_ && fold == FOLD_) {                                                      \
         hipLaunchKernelGGL((k_conv_strip<CIN, NT, RES_, BIAS_, FOLD_>), grid, block, 0, s, mg, e, (const uint8_t*)x, w, y, \
-                           ntasks, spr, qnn_fastdiv((uint32_t)spr), best_nch, qnn_fastdiv((uint32_t)best_nch),   \
-                           best_rc, (uint32_t)img_x, (uint32_t)img_y, (uint32_t)img_r);                        \
+                           QNN_STRIP_PLAN_ARGS(p), (uint32_t)img_x, (uint32_t)img_y, (uint32_t)img_r);       \
         return 0;                                                                                             \
     }
     // folded epilogue: everything behind the accumulator (bias included) is inside the fold's two constants

@@ -30,6 +30,7 @@
 // stays on k_conv_strip.
 #include "qnn_mfma_common.h"
 #include "qnn_fold.h"
+#include "qnn_strip_plan.h"
 
 namespace {
 
@@ -252,29 +253,13 @@ int qnn_launch_strip16_lds(const MfmaGeom& mg, const EpiArgs& e, const void* x, 
     const int spr = (g.W + 15) / 16;
     const double img = (double)g.H * g.W * 8.0;
     if (img >= 1.0e9) return 1;
-    const int blocks_cap = 256 * QNN_S16_WPS;
-    const long nwaves = (long)blocks_cap * 4;
-    // rows per task: whole rounds of the persistent grid; a round costs rc rows + ~3 rows of pipeline fill.  Multiples of
-    // four keep every store group full except the image's last.
-    int best_rc = g.H, best_nch = 1;
-    double best_cost = 1e300;
-    for (int rc = 4; rc <= g.H + 3; rc += 4) {
-        const int nch = (g.H + rc - 1) / rc;
-        const long tasks = (long)g.N * spr * nch;
-        const long rounds = (tasks + nwaves - 1) / nwaves;
-        const double cost = (double)rounds * (rc + 3);
-        if (cost < best_cost) { best_cost = cost; best_rc = rc; best_nch = nch; }
-    }
-    const long ntasks_l = (long)g.N * spr * best_nch;
-    if (ntasks_l >= 2000000000L) return 1;
-    long blocks = (ntasks_l + 3) / 4;
-    if (blocks > blocks_cap) blocks = blocks_cap;
-    const dim3 grid((unsigned)blocks), block(256);
+    StripPlan p;                // rows per task in multiples of four: every store group is full except the image's last
+    if (!qnn_strip_plan(&p, g.N, spr, g.H, 256 * QNN_S16_WPS, 3, 4)) return 1;
+    const dim3 grid(p.blocks), block(256);
 #define S16_CASE(RES_, FOLD_)                                                                                            \
     if ((res != 0) == RES_ && fold == FOLD_)                                                                             \
-        hipLaunchKernelGGL((k_conv_strip16_lds<RES_, FOLD_>), grid, block, 0, s, mg, e, (const uint8_t*)x, w, y, (int)ntasks_l, \
-                           spr, qnn_fastdiv((uint32_t)spr), best_nch, qnn_fastdiv((uint32_t)best_nch), best_rc, (uint32_t)img,  \
-                           (uint32_t)img);
+        hipLaunchKernelGGL((k_conv_strip16_lds<RES_, FOLD_>), grid, block, 0, s, mg, e, (const uint8_t*)x, w, y,         \
+                           QNN_STRIP_PLAN_ARGS(p), (uint32_t)img, (uint32_t)img);
     const int fold = e.fold_c ? 2 : 1;
     S16_CASE(false, 1) S16_CASE(false, 2) S16_CASE(true, 1) S16_CASE(true, 2)
 #undef S16_CASE

@@ -1,6 +1,6 @@
 // 3x3 layers with int8-STORED activations and weights and 16 / 32 / 64 input channels (the 8-bit ResNets: full-qnn with
 // wbits = 8 and / or abits = 8, models/resnet.py:104-129) as ROW-WALKING kernels on v_mfma_i32_16x16x64_i8: the int8
-// form of qnn_mfma_strip.hip.  Dispatch: qnn_route_strip (qnn_mfma.hip).
+// form of qnn_mfma_strip.hip.  Dispatch: qnn_route_strip (qnn_route_strip.hip).
 //
 // The walk is the int4 one (see the header of qnn_mfma_strip.hip: a wave owns a 16-pixel-wide column strip of ONE image
 // and walks down its rows; A = filters, B = pixels; one buffer descriptor per image so that SAME padding is an
@@ -29,6 +29,7 @@
 //
 // Register counts and waves per SIMD: the table below.
 #include "qnn_mfma_common.h"
+#include "qnn_strip_plan.h"
 
 // Waves per SIMD and ring slots, from the register counts of the ISA (unified 512-entry file per SIMD lane: 512 / waves,
 // in steps of 8).  The ring costs 4 * ST registers per slot (twice the int4 kernel's raw ring), the filters 12 * ST * NT.
@@ -415,20 +416,6 @@ void k_conv_strip_i8_s2(MfmaGeom mg, EpiArgs e, const uint8_t* __restrict__ x, c
     }
 }
 
-// rows per task: the task count should fill whole rounds of the persistent grid (a round costs rc output rows + `fill`
-// rows of pipeline fill)
-void strip8_chunks(int N, int spr, int H, long nwaves, int fill, int* rc_out, int* nch_out) {
-    int best_rc = H, best_nch = 1;
-    double best_cost = 1e300;
-    for (int rc = H < 4 ? H : 4; rc <= H; ++rc) {
-        const int nch = (H + rc - 1) / rc;
-        const long rounds = ((long)N * spr * nch + nwaves - 1) / nwaves;
-        const double cost = (double)rounds * (rc + fill);
-        if (cost < best_cost) { best_cost = cost; best_rc = rc; best_nch = nch; }
-    }
-    *rc_out = best_rc; *nch_out = best_nch;
-}
-
 template <int CIN, int NT>
 int launch_strip8_s2(const MfmaGeom& mg, const EpiArgs& e, const void* x, const uint8_t* w, void* y, hipStream_t s) {
     const ConvGeom& g = mg.g;
@@ -437,20 +424,15 @@ int launch_strip8_s2(const MfmaGeom& mg, const EpiArgs& e, const void* x, const 
     const double img_x = (double)g.H * g.W * CIN, img_y = (double)g.Ho * g.Wo * g.cout;
     if (img_x >= 1.0e9 || img_y >= 1.0e9 || ny < 1 || ny * 16 * NT != g.cout) return 1;
     const int wps = QNN_STRIP8_S2_WPS(CIN);
-    const int blocks_cap = 256 * wps / ny > 0 ? 256 * wps / ny : 1;
-    int rc, nch;
-    strip8_chunks(g.N, spr, g.Ho, (long)blocks_cap * 4, 2, &rc, &nch);
-    const long ntasks_l = (long)g.N * spr * nch;
-    if (ntasks_l >= 2000000000L) return 1;
-    long blocks = (ntasks_l + 3) / 4;
-    if (blocks > blocks_cap) blocks = blocks_cap;
-    const dim3 grid((unsigned)blocks, (unsigned)ny), block(256);
+    StripPlan p;                // over output rows, as the int4 stride-2 form
+    if (!qnn_strip_plan(&p, g.N, spr, g.Ho, 256 * wps / ny > 0 ? 256 * wps / ny : 1, 2, 1)) return 1;
+    const dim3 grid(p.blocks, (unsigned)ny), block(256);
     if (e.bias)
-        hipLaunchKernelGGL((k_conv_strip_i8_s2<CIN, NT, true>), grid, block, 0, s, mg, e, (const uint8_t*)x, w, y, (int)ntasks_l,
-                           spr, qnn_fastdiv((uint32_t)spr), nch, qnn_fastdiv((uint32_t)nch), rc, (uint32_t)img_x, (uint32_t)img_y);
+        hipLaunchKernelGGL((k_conv_strip_i8_s2<CIN, NT, true>), grid, block, 0, s, mg, e, (const uint8_t*)x, w, y,
+                           QNN_STRIP_PLAN_ARGS(p), (uint32_t)img_x, (uint32_t)img_y);
     else
-        hipLaunchKernelGGL((k_conv_strip_i8_s2<CIN, NT, false>), grid, block, 0, s, mg, e, (const uint8_t*)x, w, y, (int)ntasks_l,
-                           spr, qnn_fastdiv((uint32_t)spr), nch, qnn_fastdiv((uint32_t)nch), rc, (uint32_t)img_x, (uint32_t)img_y);
+        hipLaunchKernelGGL((k_conv_strip_i8_s2<CIN, NT, false>), grid, block, 0, s, mg, e, (const uint8_t*)x, w, y,
+                           QNN_STRIP_PLAN_ARGS(p), (uint32_t)img_x, (uint32_t)img_y);
     return 0;
 }
 
@@ -464,21 +446,14 @@ int launch_strip8(const MfmaGeom& mg, const EpiArgs& e, const void* x, const uin
     const double img_r = res == 2 ? img_y * 4.0 : img_y;
     if (img_x >= 1.0e9 || img_y >= 1.0e9 || img_r >= 1.0e9 || ny < 1 || ny * 16 * NT != g.cout) return 1;
     const int wps = strip8_wps(CIN, res);
-    const int blocks_cap = 256 * wps / ny > 0 ? 256 * wps / ny : 1;
-    int rc, nch;
-    strip8_chunks(g.N, spr, g.H, (long)blocks_cap * 4, 3, &rc, &nch);
-    const long ntasks_l = (long)g.N * spr * nch;
-    if (ntasks_l >= 2000000000L) return 1;
-    const int ntasks = (int)ntasks_l;
-    long blocks = (ntasks + 3) / 4;
-    if (blocks > blocks_cap) blocks = blocks_cap;
-    const dim3 grid((unsigned)blocks, (unsigned)ny), block(256);
+    StripPlan p;                // fill 3: taken over from the int4 walk with its value (stale there, see launch_strip)
+    if (!qnn_strip_plan(&p, g.N, spr, g.H, 256 * wps / ny > 0 ? 256 * wps / ny : 1, 3, 1)) return 1;
+    const dim3 grid(p.blocks, (unsigned)ny), block(256);
     const bool bias = e.bias != nullptr;
 #define STRIP8_CASE(RES_, BIAS_)                                                                                  \
     if (res == RES_ && bias == BIAS_) {                                                                           \
         hipLaunchKernelGGL((k_conv_strip_i8<CIN, NT, RES_, BIAS_>), grid, block, 0, s, mg, e, (const uint8_t*)x, w, y, \
-                           ntasks, spr, qnn_fastdiv((uint32_t)spr), nch, qnn_fastdiv((uint32_t)nch), rc,          \
-                           (uint32_t)img_x, (uint32_t)img_y, (uint32_t)img_r);                                    \
+                           QNN_STRIP_PLAN_ARGS(p), (uint32_t)img_x, (uint32_t)img_y, (uint32_t)img_r);            \
         return 0;                                                                                                 \
     }
     STRIP8_CASE(0, false) STRIP8_CASE(0, true) STRIP8_CASE(1, false) STRIP8_CASE(1, true)

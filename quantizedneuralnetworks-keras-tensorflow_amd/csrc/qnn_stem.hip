@@ -9,6 +9,7 @@
 // The pixel-stationary VALU kernel this replaces needs 88 us for 64 x 224^2 x 3 -> 16; the f32 matrix pipe does the
 // 7 K-steps of a row segment in 224 cycles.
 #include "qnn_mfma_common.h"
+#include "qnn_strip_plan.h"
 
 typedef float v4f __attribute__((ext_vector_type(4)));
 
@@ -141,26 +142,13 @@ int qnn_try_launch_stem(const ConvGeom& g, const EpiArgs& e, const void* x, cons
     const double img_x = (double)g.H * g.W * g.cin * 4.0, img_y = (double)g.H * g.W * e.ocw * 4.0;
     if (img_x >= 1.0e9 || img_y >= 1.0e9) return 1;
     const int ny = g.cout / 16;
-    const int blocks_cap = 256 * 4 / ny > 0 ? 256 * 4 / ny : 1;
-    const long nwaves = (long)blocks_cap * 4;
-    int best_rc = g.H, best_nch = 1;
-    double best_cost = 1e300;
-    for (int rc = g.H < 4 ? g.H : 4; rc <= g.H; ++rc) {
-        const int nch = (g.H + rc - 1) / rc;
-        const long rounds = ((long)g.N * spr * nch + nwaves - 1) / nwaves;
-        const double cost = (double)rounds * (rc + 2);
-        if (cost < best_cost) { best_cost = cost; best_rc = rc; best_nch = nch; }
-    }
-    const long ntasks_l = (long)g.N * spr * best_nch;
-    if (ntasks_l >= 2000000000L) return 1;
-    long blocks = (ntasks_l + 3) / 4;
-    if (blocks > blocks_cap) blocks = blocks_cap;
-    const dim3 grid((unsigned)blocks, (unsigned)ny), block(256);
+    StripPlan p;                // persistent grid: four workgroups per CU, shared by the ny filter blocks
+    if (!qnn_strip_plan(&p, g.N, spr, g.H, 256 * 4 / ny > 0 ? 256 * 4 / ny : 1, 2, 1)) return 1;
+    const dim3 grid(p.blocks, (unsigned)ny), block(256);
 #define STEM_CASE(CIN_, BIAS_)                                                                                       \
     if (g.cin == CIN_ && (e.bias != nullptr) == BIAS_) {                                                             \
-        hipLaunchKernelGGL((k_conv_stem<CIN_, BIAS_>), grid, block, 0, s, g, e, (const float*)x, wq, y, (int)ntasks_l, \
-                           spr, qnn_fastdiv((uint32_t)spr), best_nch, qnn_fastdiv((uint32_t)best_nch), best_rc,      \
-                           (uint32_t)img_x, (uint32_t)img_y);                                                        \
+        hipLaunchKernelGGL((k_conv_stem<CIN_, BIAS_>), grid, block, 0, s, g, e, (const float*)x, wq, y,                \
+                           QNN_STRIP_PLAN_ARGS(p), (uint32_t)img_x, (uint32_t)img_y);                                \
         return 0;                                                                                                    \
     }
     STEM_CASE(3, false) STEM_CASE(3, true) STEM_CASE(1, false) STEM_CASE(1, true)

@@ -1,4 +1,6 @@
-"""The OPT-IN fixed-point first layer (qnn_set_option("first_fixed", 1); csrc/qnn_first_fixed.hip).
+"""The fixed-point first layer (csrc/qnn_first_fixed.hip): taken by calls whose float32 input is declared
+QNN_STORE_F32_UNIT (first_mode 2); the binding's test helper _abi.set_option("first_fixed", 1) declares it for the calls
+made here.
 
 It is deliberately NOT the oracle's float32 FMA chain, so its checks are different from every other kernel's:
 
@@ -7,7 +9,7 @@ It is deliberately NOT the oracle's float32 FMA chain, so its checks are differe
  * against the IDEAL (float64) convolution: within the north star's 1e-5 (the bound is 27 * 2^-24 + half an ulp);
  * against the oracle's codes: the measured fraction of activation codes that differ (values whose pre-activation sits
    within ~1e-6 of a rounding threshold), each by one code step, is printed and bounded.
-The default (exact) kernel is untouched: the last test checks the switch restores it.
+The default (exact) kernel is untouched: the last test checks that plain QNN_STORE_F32 calls keep it.
 """
 import zlib
 
@@ -75,7 +77,8 @@ def _case(name, shape, kind, nb, bias=True):
 
 CASES = [("q4_32", (3, 32, 32, 3), "quantized", 4), ("q2_16x48", (2, 16, 48, 3), "quantized", 2),
          ("q3_nobias", (1, 8, 16, 3), "quantized", 3), ("bin_32", (2, 32, 32, 3), "binary", None),
-         ("q4_tall", (5, 66, 16, 3), "quantized", 4), ("q4_many", (300, 4, 16, 3), "quantized", 4)]
+         ("q4_tall", (5, 66, 16, 3), "quantized", 4), ("q4_many", (300, 4, 16, 3), "quantized", 4),
+         ("q4_10x16", (2, 10, 16, 3), "quantized", 4)]        # five row pairs: tasks of 2, 2 and 1
 
 
 @pytest.mark.parametrize("case", CASES, ids=[c[0] for c in CASES])

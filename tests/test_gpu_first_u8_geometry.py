@@ -94,7 +94,9 @@ class _Conv:
 #                     cout 64: N = 769 -> the same chunks, two rounds.
 #   The int8 forms (16-byte stores) of the image entry wrote wrong first dwords at N = 64 and 385 before the wait state
 #   behind their store (csrc/qnn_first_u8.hip); N <= 17 never showed it.
-FULL = [("stem_q4", 16, "quantized", 4, Q(4), _abi.STORE_I4, [(224, 224, [1, 44]), (112, 112, [1, 512]), (222, 208, [1, 48])]),
+#   stem 10 x 16: the smallest seam -- five row pairs in tasks of 2, 2 and 1, one strip, one round.
+FULL = [("stem_q4", 16, "quantized", 4, Q(4), _abi.STORE_I4,
+         [(224, 224, [1, 44]), (112, 112, [1, 512]), (222, 208, [1, 48]), (10, 16, [2])]),
         ("stem_bin", 16, "binary", None, BIN_ACT, _abi.STORE_I4,
          [(224, 224, [1, 44]), (112, 112, [1, 512]), (222, 208, [1, 48])]),
         ("vgg_q8", 256, "quantized", 8, Q(8), _abi.STORE_I8, [(32, 32, [1, 385])]),

@@ -572,6 +572,21 @@ def test_small_channel_layers_on_the_matrix_pipe(cin, cout, hw, n):
                 _abi.set_option("strip64", -1)
 
 
+def test_stem_chunk_seams():
+    """The ResNet stem (3 -> 16, csrc/qnn_stem.hip) where an image is cut into tasks of 4, 4 and 2 rows beside a ragged
+    last strip: the float32 chain of the oracle, bit for bit."""
+    rng = np.random.default_rng(1020)
+    x = (rng.integers(0, 256, (2, 10, 20, 3)).astype(F32) / F32(255)).astype(F32)
+    bn = _rand_bn(rng, 16, 27 * 0.3)
+    for bias in (True, False):
+        op = {"op": "conv", "kind": "quantized", "nb": 4, "kernel": rng.uniform(-1, 1, (3, 3, 3, 16)).astype(F32),
+              "bias": (rng.standard_normal(16) * 0.05).astype(F32) if bias else None, "strides": (1, 1), "padding": "same"}
+        for act in (Q(4), BIN_ACT):
+            got, kern = _run_group(x, None, op, bn, act, 1, _abi.STORE_I4)
+            assert kern == "mfma_f32_stem_cin3", kern
+            np.testing.assert_array_equal(got, _oracle_group(x, op, bn, act, 1, float_conv="device"))
+
+
 @pytest.mark.parametrize("cin,cout,hw,n", [(16, 32, (224, 224), 1), (32, 64, (112, 112), 2), (16, 32, (8, 8), 3),
                                            (32, 64, (7, 9), 2), (16, 64, (5, 33), 2), (32, 32, (1, 1), 2), (16, 32, (2, 40), 5)])
 def test_stride2_layers_on_the_strip_kernel(cin, cout, hw, n):

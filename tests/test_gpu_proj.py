@@ -30,7 +30,8 @@ def _proj_layer(rng, cin0, cout, bias):
 
 
 @pytest.mark.parametrize("cin,hw0,n", [(32, (224, 224), 1), (64, (112, 112), 2), (32, (13, 17), 3), (64, (26, 63), 5),
-                                        (32, (2, 2), 4), (64, (1, 1), 2), (32, (31, 66), 70), (64, (9, 40), 260)])
+                                        (32, (2, 2), 4), (64, (1, 1), 2), (32, (31, 66), 70), (64, (9, 40), 260),
+                                        (32, (20, 40), 2)])      # 10 x 20: tasks of 4, 4 and 2 rows, ragged strip
 @pytest.mark.parametrize("bias", [(False, False), (True, True), (True, False)])
 def test_projection_inside_the_launch_equals_the_two_launch_form(cin, hw0, n, bias):
     """Block input H0 x W0 x cin/2 (odd sizes: 'same' padding of a strides-2 1x1 window reads pixel (2y, 2x)), block

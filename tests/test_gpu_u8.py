@@ -77,6 +77,7 @@ CASES = [("q4_32", (3, 32, 32, 3), "quantized", 4, 64, 3, 1, "mfma_i8_first_u8")
          ("bin_32", (2, 32, 32, 3), "binary", None, 64, 3, 1, "mfma_i8_first_u8"),
          ("q4_tall", (5, 66, 16, 3), "quantized", 4, 64, 3, 1, "mfma_i8_first_u8"),
          ("q4_many", (300, 4, 16, 3), "quantized", 4, 64, 3, 1, "mfma_i8_first_u8"),
+         ("q4_10x16", (2, 10, 16, 3), "quantized", 4, 64, 3, 1, "mfma_i8_first_u8"),  # five row pairs: tasks of 2, 2 and 1
          ("q8_32", (2, 32, 32, 3), "quantized", 8, 64, 3, 1, "generic_u8"),          # |code| up to 128: generic
          ("q4_stem16", (2, 24, 20, 3), "quantized", 4, 16, 3, 1, "generic_u8"),      # ResNet stem 3 -> 16
          ("bin_mnist", (3, 28, 28, 1), "binary", None, 64, 3, 1, "generic_u8"),      # MNIST, one channel
