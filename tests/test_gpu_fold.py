@@ -34,11 +34,13 @@ def _layer(rng, cin, cout, k=3, bias=True, stride=1, gamma_sign=None):
 
 def _chain_codes(acc, sc, c, op, bn, x_bits=4):
     """The reference chain on integer accumulators of channel c (float32, one rounding per operation): conv value =
-    acc * 2^-(wshift + xshift) (exact), K.bias_add, BatchNormalization, [(shortcut + y) * 0.5], quantized_tanh(nb=4)."""
+    acc * 2^-(wshift + xshift) (exact), K.bias_add, BatchNormalization (bn None: a layer without one), [(shortcut + y) *
+    0.5], quantized_tanh(nb=4).  Shared with test_gpu_epilogue_grid.py."""
     v = (acc.astype(F32) * F32(2.0 ** -(3 + x_bits - 1))).astype(F32)
     if op["bias"] is not None:
         v = O.bias_add(v, op["bias"][c])
-    v = O.batchnorm_inference(v, bn["gamma"][c], bn["beta"][c], bn["mean"][c], bn["var"][c], bn["eps"])
+    if bn is not None:
+        v = O.batchnorm_inference(v, bn["gamma"][c], bn["beta"][c], bn["mean"][c], bn["var"][c], bn["eps"])
     if sc is not None:
         r = (sc.astype(F32) * F32(0.125)).astype(F32)
         v = ((r + v).astype(F32) * F32(0.5)).astype(F32)
