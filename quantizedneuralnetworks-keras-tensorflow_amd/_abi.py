@@ -379,9 +379,22 @@ class Weights:
 
 
 def out_hw(size, k, stride, same_pad):
+    """Output size of one axis, the rule of csrc/qnn_conv_geom.h: 'valid' with a window larger than the image is 0."""
     if same_pad:
         return -(-size // stride)
-    return (size - k) // stride + 1
+    return (size - k) // stride + 1 if size >= k else 0
+
+
+def _stored_hw(what, w, H, W, pool):
+    """(Hp, Wp) of a conv call's stored output; an empty one (before or after pooling) is refused here, before any
+    library call, as conv_describe refuses it ("empty output")."""
+    kh, kw = w.shape[0], w.shape[1]
+    Ho, Wo = out_hw(H, kh, w.stride, w.same_pad), out_hw(W, kw, w.stride, w.same_pad)
+    if Ho // pool <= 0 or Wo // pool <= 0:
+        raise QnnError("%s: empty output: %dx%d input, %dx%d window, stride %d, %s padding gives %dx%d%s"
+                       % (what, H, W, kh, kw, w.stride, "same" if w.same_pad else "valid", Ho, Wo,
+                          ", pooled by %d" % pool if pool != 1 else ""))
+    return Ho // pool, Wo // pool
 
 
 def make_epilogue(bn_inv, bn_shift, fn, act_bits, pool, out_store, res=None, res_store=STORE_F32,
@@ -478,9 +491,8 @@ def conv2d(w, x, x_store, x_bits, N, H, W, bn_inv=None, bn_shift=None, fn=FN_NON
     """Run qnn_conv2d_forward; x is a float32 NHWC tensor, a uint8 NHWC tensor or an int32 packed tensor.
     Returns (y, Hp, Wp): y float32 (N,Hp,Wp,cout) or int32 (N*Hp*Wp, words); `out` = a tensor of that shape to write
     into instead of a fresh one.  proj: see make_epilogue (raises QnnUnsupported where no kernel computes it)."""
-    kh, kw, cin, cout = w.shape
-    Ho = out_hw(H, kh, w.stride, w.same_pad) // pool
-    Wo = out_hw(W, kw, w.stride, w.same_pad) // pool
+    cout = w.shape[3]
+    Ho, Wo = _stored_hw("conv2d", w, H, W, pool)
     if out_store == STORE_F32:
         shape, dt = (N, Ho, Wo, cout), torch.float32
     else:
@@ -506,6 +518,7 @@ def conv2d_dense(wc, wd, x, x_store, x_bits, N, H, W, c_inv, c_shift, c_fn, c_ac
     """qnn_conv2d_dense_forward: the last conv group (2x2 pool, packed int4 codes) and the dense head behind it in one
     launch.  Returns the (N, units) float32 logits, or None when no fused kernel covers the pair (QNN_EUNSUPPORTED)."""
     units = wd.shape[3]
+    _stored_hw("conv2d_dense", wc, H, W, 2)
     y = out if out is not None else torch.empty((N, units), dtype=torch.float32, device=x.device)
     ec = make_epilogue(c_inv, c_shift, c_fn, c_act_bits, 2, STORE_I4, fold=fold)
     ed = make_epilogue(d_inv, d_shift, FN_NONE, 0, 1, STORE_F32)
@@ -571,9 +584,8 @@ def conv2d_f32in(w, x, in_fn, in_bits, bn_inv=None, bn_shift=None, fn=FN_NONE, a
     """qnn_conv2d_forward_f32in: float32 NHWC x, activation clip `in_fn` fused on load."""
     x = require_cuda(x, "conv2d_f32in")
     N, H, W, _ = x.shape
-    kh, kw, cin, cout = w.shape
-    Ho = out_hw(H, kh, w.stride, w.same_pad) // pool
-    Wo = out_hw(W, kw, w.stride, w.same_pad) // pool
+    cout = w.shape[3]
+    Ho, Wo = _stored_hw("conv2d_f32in", w, H, W, pool)
     if out_store == STORE_F32:
         y = torch.empty((N, Ho, Wo, cout), dtype=torch.float32, device=x.device)
     else:

@@ -170,18 +170,8 @@ QNN_HD static inline int qnn_words(int store, int channels) {
     return (channels + pw - 1) / pw;
 }
 
-// TF 'SAME' padding (documented TF semantics; oracle: same_padding()).
-static inline void qnn_same_pad(int in, int k, int s, int same, int* out, int* before) {
-    if (same) {
-        *out = (in + s - 1) / s;
-        int total = (*out - 1) * s + k - in;
-        if (total < 0) total = 0;
-        *before = total / 2;
-    } else {
-        *out = (in - k) / s + 1;
-        *before = 0;
-    }
-}
+// qnn_same_pad: output size and leading padding of one axis (TF 'SAME' / 'VALID'), plain C++
+#include "qnn_conv_geom.h"
 
 #ifdef __HIPCC__
 // ---- float32 activation clips, replayed op by op ------------------------------

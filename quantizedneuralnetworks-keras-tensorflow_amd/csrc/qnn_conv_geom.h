@@ -1,0 +1,20 @@
+// Output size and leading padding of one axis of a convolution, TensorFlow semantics.  Plain C++ without HIP, so that
+// the rule is compiled and tested on its own (tests/test_conv_geom.py); qnn_common.h includes it for every launcher.
+#pragma once
+
+// SAME:  out = ceil(in / s), total padding = max((out - 1) * s + k - in, 0), `before` = total / 2 (the odd cell goes
+//        after) -- oracle: same_padding().
+// VALID: out = number of window starts 0, s, 2s, ... whose k cells lie inside the image = (in - k) / s + 1 for
+//        in >= k and 0 for in < k.  The quotient alone is not enough: C division truncates toward zero, so
+//        (in - k) / s + 1 is 1, not 0, for 0 < k - in < s.
+static inline void qnn_same_pad(int in, int k, int s, int same, int* out, int* before) {
+    if (same) {
+        *out = (in + s - 1) / s;
+        int total = (*out - 1) * s + k - in;
+        if (total < 0) total = 0;
+        *before = total / 2;
+    } else {
+        *out = in < k ? 0 : (in - k) / s + 1;
+        *before = 0;
+    }
+}
