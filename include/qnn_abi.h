@@ -192,6 +192,12 @@ typedef struct qnn_epilogue {
  *   QNN_EPI_NO_LDS16     16 -> 16 channel layers with a fold: k_conv_strip instead of the LDS-staged k_conv_strip16_lds
  *   QNN_EPI_NO_FP6       folded pooled int4 layers: k_conv_mfma_halo on the int8 matrix pipe instead of its FP6 (e2m3)
  *                        form
+ *   QNN_EPI_NO_FIRST_TAB the byte first layer with a fold of the image entry: every wave derives its MFMA operands and
+ *                        constants from the weights in the kernel's preamble, and the epilogue keeps the conversion,
+ *                        instead of loading the operand table that qnn_fold_prepare built into the handle
+ *   QNN_EPI_NO_FIRST_BITS  read by qnn_fold_prepare, not by a launch: the image entry's fold does not search the
+ *                        bits form, so the handle's table carries the mode-3 constants (what a handle holds when the
+ *                        search fails on some channel; tests)
  * The restricted-domain first-layer kernels are selected by the TYPED input stores QNN_STORE_F32_IMAGE /
  * QNN_STORE_F32_UNIT of the call (above), never by a switch.
  */
@@ -200,6 +206,8 @@ typedef struct qnn_epilogue {
 #define QNN_EPI_NO_HALO     4u
 #define QNN_EPI_NO_LDS16    8u
 #define QNN_EPI_NO_FP6      16u
+#define QNN_EPI_NO_FIRST_TAB   32u
+#define QNN_EPI_NO_FIRST_BITS  64u
 
 /* ---- library ------------------------------------------------------------ */
 int         qnn_version(void);
@@ -321,7 +329,9 @@ typedef struct qnn_fold_info {
 } qnn_fold_info_t;
 int qnn_fold_info(const qnn_fold_t* f, qnn_fold_info_t* info);
 /* DEVICE copies of A[cout] (float32), beta[cout] (int32; mode 2: + 0x4B400000) and, if C != NULL, C[cout] (float32) --
- * tests and diagnostics */
+ * tests and diagnostics.  Mode 3 has no offset: A and C are its constants, and beta reports the search for the bits form
+ * of the byte first layer's operand table: that form's offset + 0x4B400000 on a channel where it was proven, else 0.  The
+ * table carries the bits form if and only if beta is non-zero on every channel. */
 int qnn_fold_constants(const qnn_fold_t* f, float* A, int32_t* beta, float* C, void* stream);
 /* Evaluate the FOLDED epilogue (the very device function the kernels inline) for channel `c` on n accumulator values
  * acc[i] (true integer units, DEVICE int32) and, with a shortcut, shortcut codes sc[i] (DEVICE int32, else NULL):

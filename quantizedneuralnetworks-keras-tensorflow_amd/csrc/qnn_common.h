@@ -135,6 +135,10 @@ struct EpiArgs {
     const float* proj_bias;    // or nullptr
     float proj_scale;          // 2^-(wshift + x_bits - 1) of the projection
     int proj_cin, proj_H, proj_W;
+    // byte first layer with a mode-3 fold: the handle's operand table (qnn_fold.h, qnn_first_u8_entry) or nullptr = the
+    // in-kernel preamble (QNN_EPI_NO_FIRST_TAB); first_tab_bits: the table carries the bits form of the fold
+    const void* first_tab;
+    int first_tab_bits;
 };
 
 // One conv call as every route of the dispatch sees it: validated, geometry and epilogue filled in once

@@ -1141,6 +1141,8 @@ int check_epilogue(const qnn_weights* w, const qnn_epilogue_t* epi, int xshift, 
     e->fold_a = nullptr;
     e->fold_b = nullptr;
     e->fold_c = nullptr;
+    e->first_tab = nullptr;
+    e->first_tab_bits = 0;
     e->dom_flag = epi->domain_flag;
     e->flags = epi->flags;
     e->first_mode = 0;
@@ -1181,6 +1183,10 @@ int check_epilogue(const qnn_weights* w, const qnn_epilogue_t* epi, int xshift, 
                         epi->trick_s == 0.0f,
                     QNN_EINVAL, "epilogue: the fold handle was prepared for another layer / epilogue (qnn_fold_prepare)");
         if (f->folded == f->cout) { e->fold_a = f->d_a; e->fold_b = f->d_b; e->fold_c = f->mode >= 2 ? f->d_c : nullptr; }
+        if (f->folded == f->cout && f->mode == 3 && f->d_tab && !(epi->flags & QNN_EPI_NO_FIRST_TAB)) {
+            e->first_tab = f->d_tab;
+            e->first_tab_bits = f->tab_bits;
+        }
     }
     QNN_REQUIRE(epi->trick_s == 0.0f || (epi->trick_s > 0.0f && epi->trick_s < 1.0e6f), QNN_EINVAL,
                 "epilogue: trick_s=%g (the layer's kernel_lr_multiplier, or 0)", (double)epi->trick_s);

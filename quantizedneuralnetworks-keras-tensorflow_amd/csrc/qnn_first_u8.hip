@@ -73,7 +73,13 @@ __device__ __forceinline__ void image_bytes2(uint32_t& b0, uint32_t& b1, ImageDo
 // FOLD (round 4): the epilogue of the pooled int4 form as qnn_fold.h's mode 3 -- u = fma(float(S), A2, C2), one
 // v_cvt_pknorm_i16_f32 per pair, two v_perm_b32 + shift + v_bfi_b32 per eight values -- with A2 / C2 from a fold handle that
 // qnn_fold_prepare accepted only after it reproduced  clip(rint(fma(float(S), A, B)))  on every S the filter can produce.
-template <int OUT, int POOL, bool BIN, bool F32IN, bool FOLD = false>
+// TAB (with FOLD): 1 = the operands and constants come from the fold handle's table (qnn_fold.h, qnn_first_u8_entry: built once
+// by qnn_fold_prepare with the function the preamble below calls) -- six 16-byte loads per lane, no LDS table, no workgroup
+// barrier; 2 = that table carries the BITS form of the fold: the accumulator starts from a kept splat of 0x4B400000, the
+// offset block's last A byte is +1 and meets beta[c], so the pooled maximum IS the bit pattern of the float
+// 12582912 + S + beta (patterns of one binade order like the sums) and one FMA per value replaces conversion + FMA.
+// 0 = the in-kernel preamble and the conversion (no handle, or QNN_EPI_NO_FIRST_TAB).
+template <int OUT, int POOL, bool BIN, bool F32IN, bool FOLD = false, int TAB = 0>
 __global__ __launch_bounds__(256, 4) void k_conv_first_u8(ConvGeom g, EpiArgs e, const void* __restrict__ x,
                                                            const float* __restrict__ wq, void* __restrict__ y,
                                                            int ntasks, int spr, FastDiv fd_spr, int nch, FastDiv fd_nch,
@@ -86,60 +92,43 @@ __global__ __launch_bounds__(256, 4) void k_conv_first_u8(ConvGeom g, EpiArgs e,
     const int wid = blockIdx.x * 4 + wave, nw = gridDim.x * 4;
     uint32_t* lds = reinterpret_cast<uint32_t*>(smem_u8) + wave * kWaveLdsU;
     uint8_t* ldsb = reinterpret_cast<uint8_t*>(lds);
-    uint4* tab = reinterpret_cast<uint4*>(smem_u8 + 4 * kWaveLdsU * 4);      // [filter block][lane][2]
-    for (int i = lane; i < kWaveLdsU; i += 64) lds[i] = 0x80808080u;        // code 0 everywhere; the constant block
+    static_assert(TAB == 0 || FOLD, "the operand table belongs to a fold handle");
+    // code 0 everywhere; the constant block (bits form: its last byte is +1, the A byte that beta meets)
+    for (int i = lane; i < kWaveLdsU; i += 64) lds[i] = (TAB == 2 && i == kConstU + 3) ? 0x01808080u : 0x80808080u;
 
     // ---- filters: B operand of block nt, column r, K-block kq.  Wave nt prepares block nt for the workgroup.
     // The pooled int4 forms DEAL the filters: column r of block nt is channel 4 r + nt, so the four blocks of a lane are
     // four consecutive channels of one pooled pixel = one 16-bit half of an output word, already in the order the
     // packing leaves them -- no transpose across lanes (the strip kernels' deal, qnn_mfma_strip.hip).  Everything
     // per-channel below (codes, the negation, A / B, the fold's A2 / C2) follows c. ----
-    {
-        const int c = POOL == 2 ? 4 * r + wave : wave * 16 + r;
-        const float bias = e.bias ? e.bias[c] : 0.0f;
-        const float inv = e.bn_inv ? e.bn_inv[c] : 1.0f;
-        const float shift = e.bn_inv ? e.bn_shift[c] : 0.0f;
-        const bool flip = POOL == 2 && inv < 0.0f;               // pool with max only: negate the filter and A[c]
-        const float* wrow = wq + (size_t)c * 27 + (kq < 3 ? kq : 2) * 9;
-        int part = 0;
-        uint32_t wd[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-        for (int i = 0; i < 9; ++i) {
-            int code = (int)rintf(__fmul_rn(wrow[i], wscale));
-            if (flip) code = -code;
-            if (kq == 3) code = 0;
-            part += code;
-            wd[i / 3] |= (uint32_t)(code & 0xFF) << (8 * (i % 3));
-        }
-        part += __shfl_xor(part, 16);                            // sum of the 27 codes of filter c (all four K-block
-        part += __shfl_xor(part, 32);                            // lanes end up with it)
-        if (kq == 3) {
-            // sixteen bytes that sum to -part: against A bytes of -128 they contribute +128 * sum k
-            int rem = -part;
-#pragma unroll
-            for (int j = 0; j < 16; ++j) {
-                const int b = min(max(rem, -127), 127);
-                rem -= b;
-                wd[j >> 2] |= (uint32_t)(b & 0xFF) << (8 * (j & 3));
-            }
-        }
-        // the affine map behind S (qnn_abi.h): float64 from the float32 constants, one rounding each
-        const double m = e.fn == QNN_FN_QUANTIZED_TANH ? (double)e.act_m : 1.0;
-        float A = (float)((double)inv * m / (double)D);
-        float B = (float)(((double)bias * (double)inv + (double)shift) * m);
-        if constexpr (FOLD) { A = e.fold_a[c]; B = e.fold_c[c]; }
-        if (flip) A = -A;
-        tab[(wave * 64 + lane) * 2] = make_uint4(wd[0], wd[1], wd[2], wd[3]);
-        tab[(wave * 64 + lane) * 2 + 1] = make_uint4(__float_as_uint(A), __float_as_uint(B), 0u, 0u);
-    }
-    __syncthreads();
     v4i bw[4];
     float fa[4], fb[4];
+    if constexpr (TAB != 0) {
+        const uint4* __restrict__ tb = reinterpret_cast<const uint4*>(e.first_tab);
 #pragma unroll
-    for (int nt = 0; nt < 4; ++nt) {
-        const uint4 t0 = tab[(nt * 64 + lane) * 2], t1 = tab[(nt * 64 + lane) * 2 + 1];
-        bw[nt] = __builtin_bit_cast(v4i, t0);
-        fa[nt] = __uint_as_float(t1.x); fb[nt] = __uint_as_float(t1.y);
+        for (int nt = 0; nt < 4; ++nt) bw[nt] = __builtin_bit_cast(v4i, tb[nt * 64 + lane]);
+        const uint4 ta = tb[4 * 64 + lane], tc = tb[5 * 64 + lane];
+        fa[0] = __uint_as_float(ta.x); fa[1] = __uint_as_float(ta.y); fa[2] = __uint_as_float(ta.z); fa[3] = __uint_as_float(ta.w);
+        fb[0] = __uint_as_float(tc.x); fb[1] = __uint_as_float(tc.y); fb[2] = __uint_as_float(tc.z); fb[3] = __uint_as_float(tc.w);
+    } else {
+        uint4* tab = reinterpret_cast<uint4*>(smem_u8 + 4 * kWaveLdsU * 4);  // [filter block][lane][2]
+        const FirstU8Entry t = qnn_first_u8_entry<POOL == 2>(e, wq, wscale, D, wave, lane, FOLD ? e.fold_a : nullptr,
+                                                             FOLD ? e.fold_c : nullptr, nullptr);
+        tab[(wave * 64 + lane) * 2] = make_uint4(t.wd[0], t.wd[1], t.wd[2], t.wd[3]);
+        tab[(wave * 64 + lane) * 2 + 1] = make_uint4(__float_as_uint(t.A), __float_as_uint(t.B), 0u, 0u);
+        __syncthreads();
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt) {
+            const uint4 t0 = tab[(nt * 64 + lane) * 2], t1 = tab[(nt * 64 + lane) * 2 + 1];
+            bw[nt] = __builtin_bit_cast(v4i, t0);
+            fa[nt] = __uint_as_float(t1.x); fb[nt] = __uint_as_float(t1.y);
+        }
+    }
+    // the accumulators' initial value: zero, or (bits form) four registers kept for the whole kernel
+    v4i z = {0, 0, 0, 0};
+    if constexpr (TAB == 2) {
+        z = v4i{kFoldMagicBits, kFoldMagicBits, kFoldMagicBits, kFoldMagicBits};
+        asm volatile("" : "+v"(z));
     }
     constexpr int kMagicBits = 0x4B400008;                       // 1.5 * 2^23 + 8: see qnn_mfma_strip.hip
     const float magic = __int_as_float(kMagicBits);
@@ -232,7 +221,6 @@ __global__ __launch_bounds__(256, 4) void k_conv_first_u8(ConvGeom g, EpiArgs e,
             // is consumed
             v4i acc[2];
             int T[8];
-            const v4i z = {0, 0, 0, 0};
             auto consume = [&](int gq, const v4i& a) {
                 const int t = gq >> 2, nt = gq & 3;
                 if constexpr (POOL == 2) {
@@ -264,7 +252,8 @@ __global__ __launch_bounds__(256, 4) void k_conv_first_u8(ConvGeom g, EpiArgs e,
                 uint32_t tp[4];
 #pragma unroll
                 for (int j = 0; j < 4; ++j)             // pairs (value j, value j + 4): same filter block, tiles 0 and 1
-                    tp[j] = qnn_fold_pair_fma(T[j], T[j + 4], fa[j], fa[j], fb[j], fb[j]);
+                    tp[j] = TAB == 2 ? qnn_fold_pair_bits(T[j], T[j + 4], fa[j], fa[j], fb[j], fb[j])
+                                     : qnn_fold_pair_fma(T[j], T[j + 4], fa[j], fa[j], fb[j], fb[j]);
                 const uint32_t uo = __builtin_amdgcn_perm(tp[3], tp[1], 0x07030501u);
                 const uint32_t ue = __builtin_amdgcn_perm(tp[2], tp[0], 0x07030501u);
                 const uint32_t P = (uo & 0xF0F0F0F0u) | ((ue >> 4) & 0x0F0F0F0Fu);      // nibble j = code of value j
@@ -623,6 +612,15 @@ int qnn_try_launch_first_u8(const ConvGeom& g, const EpiArgs& e, const void* x, 
     } while (0)
     if (!fused) U8_LAUNCH(QNN_STORE_F32, 1, false);
     else if (e.fn == QNN_FN_BINARY_TANH) U8_LAUNCH(QNN_STORE_I4, 2, true);
+    else if (e.fold_a && e.fold_c && e.act_m == 8.0f && e.first_tab) {     // ... with the handle's operand table
+        const size_t lds_ring = (size_t)4 * kWaveLdsU * 4;
+#define U8_TAB(F32_, TAB_)                                                                                                  \
+        hipLaunchKernelGGL((k_conv_first_u8<QNN_STORE_I4, 2, false, F32_, true, TAB_>), grid, block, lds_ring, s, g, e, x,   \
+                           w->d_wq, y, QNN_STRIP_PLAN_ARGS(p), (uint32_t)img_x, wscale, D, (e.dom_flag ? e.dom_flag : w->d_flag))
+        if (e.first_tab_bits) { if (f32in) U8_TAB(true, 2); else U8_TAB(false, 2); }
+        else { if (f32in) U8_TAB(true, 1); else U8_TAB(false, 1); }
+#undef U8_TAB
+    }
     else if (e.fold_a && e.fold_c && e.act_m == 8.0f) {       // folded epilogue (mode 3 handle of this layer, qnn_fold.h)
         if (f32in)
             hipLaunchKernelGGL((k_conv_first_u8<QNN_STORE_I4, 2, false, true, true>), grid, block, lds, s, g, e, x, w->d_wq, y,

@@ -38,9 +38,15 @@ __device__ __forceinline__ uint32_t qnn_fold_pair_bits(int acc0, int acc1, float
     return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pknorm_i16(u0, u1));
 }
 // Third form (mode 3): the typed image entry (QNN_STORE_U8 / QNN_STORE_F32_IMAGE first layers), whose accumulator is the
-// exact integer S = sum byte * code in units of ONE (no widening, so no sub-step offset to play with): the folded form
-// keeps the conversion and takes its offset in the FMA,  u = fma(float(S), A, C),  and only the rounding add, the
-// integer median and the shift-adds of the packing go (v_cvt_pknorm_i16_f32 + v_perm_b32 / v_bfi_b32 instead).
+// exact integer S = sum byte * code in units of ONE (no widening).  The folded form takes its offset in the FMA,
+// u = fma(float(S), A, C),  and the rounding add, the integer median and the shift-adds of the packing go
+// (v_cvt_pknorm_i16_f32 + v_perm_b32 / v_bfi_b32 instead).  These are the constants the handle reports and evaluates.
+// The sub-step offset the bits form needs exists here too: with the accumulator seeded with 0x4B400000 the FMA's
+// constant C' = float(C - 12582912 A') has magnitude in the hundreds, so its ulp is a sizeable fraction of one step of
+// S, and an integer beta (|beta| <= 127, one more product of the MFMA's offset K-block) moves the thresholds by whole
+// steps: neighbouring C' and beta together place them anywhere.  qnn_fold_prepare searches (A', C', beta) behind the
+// mode-3 search and proves them on the whole domain with qnn_fold_pair_bits; if every channel passes, the layer's
+// operand table (below) carries them and the kernel drops the conversion.
 __device__ __forceinline__ uint32_t qnn_fold_pair_fma(int s0, int s1, float a0, float a1, float c0, float c1) {
     const float u0 = __fmaf_rn((float)s0, a0, c0), u1 = __fmaf_rn((float)s1, a1, c1);
     return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pknorm_i16(u0, u1));
@@ -65,6 +71,75 @@ __device__ __forceinline__ int qnn_fold_code(int accw, float a, float c, int mod
     if (res) t = qnn_fold_merge(t, (uint32_t)((sc + 8) << 10) * 0x00010001u);
     return qnn_fold_code_lo(t);
 }
+
+// ---- operands of the byte first layer (qnn_first_u8.hip), per (filter block nt, lane = 16 kq + r) -------------------
+// B operand of MFMA column r, K-block kq (kq < 3: the nine taps x (3 channels + one zero byte) of tap row kq and four
+// zero bytes; kq = 3: the offset block, against A bytes of -128) and the two constants of the map behind the sum.
+// DEAL (pooled int4 forms): column r of block nt is channel 4 r + nt, and the filter of a channel with negative BN
+// scale is negated, A with it (pooling is a max on the integers).  fa / fc: per-channel constants of a fold that
+// replace the affine map, or nullptr.  fbeta (bits form only, with fa / fc): byte 15 of the offset block carries
+// beta[c] -- it meets an A byte of +1 -- and the other fifteen bytes sum to -sum k.
+// ONE definition: the kernel's own preamble and the table qnn_fold_prepare builds once per handle both call it, so the
+// table holds, bit for bit, what a launch without it computes.  Every lane of the wave must call it (two shuffles).
+struct FirstU8Entry {
+    uint32_t wd[4];
+    float A, B;
+};
+template <bool DEAL>
+__device__ __forceinline__ FirstU8Entry qnn_first_u8_entry(const EpiArgs& e, const float* __restrict__ wq, float wscale,
+                                                           float D, int nt, int lane, const float* __restrict__ fa,
+                                                           const float* __restrict__ fc,
+                                                           const int32_t* __restrict__ fbeta) {
+    const int r = lane & 15, kq = lane >> 4;
+    const int c = DEAL ? 4 * r + nt : nt * 16 + r;
+    const float bias = e.bias ? e.bias[c] : 0.0f;
+    const float inv = e.bn_inv ? e.bn_inv[c] : 1.0f;
+    const float shift = e.bn_inv ? e.bn_shift[c] : 0.0f;
+    const bool flip = DEAL && inv < 0.0f;                    // pool with max only: negate the filter and A[c]
+    const float* wrow = wq + (size_t)c * 27 + (kq < 3 ? kq : 2) * 9;
+    int part = 0;
+    FirstU8Entry t;
+    t.wd[0] = t.wd[1] = t.wd[2] = t.wd[3] = 0u;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) {
+        int code = (int)rintf(__fmul_rn(wrow[i], wscale));
+        if (flip) code = -code;
+        if (kq == 3) code = 0;
+        part += code;
+        t.wd[i / 3] |= (uint32_t)(code & 0xFF) << (8 * (i % 3));
+    }
+    part += __shfl_xor(part, 16);                            // sum of the 27 codes of filter c (all four K-block
+    part += __shfl_xor(part, 32);                            // lanes end up with it)
+    if (kq == 3) {
+        // bytes that sum to -part: against A bytes of -128 they contribute +128 * sum k (sixteen, or fifteen and beta)
+        int rem = -part;
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+            int b = min(max(rem, -127), 127);
+            if (fbeta && j == 15) b = fbeta[c];
+            else rem -= b;
+            t.wd[j >> 2] |= (uint32_t)(b & 0xFF) << (8 * (j & 3));
+        }
+    }
+    if (fa) {
+        t.A = fa[c]; t.B = fc[c];
+    } else {
+        // the affine map behind S (qnn_abi.h): float64 from the float32 constants, one rounding each
+        const double m = e.fn == QNN_FN_QUANTIZED_TANH ? (double)e.act_m : 1.0;
+        t.A = (float)((double)inv * m / (double)D);
+        t.B = (float)(((double)bias * (double)inv + (double)shift) * m);
+    }
+    if (flip) t.A = -t.A;
+    return t;
+}
+// The table in device memory, in uint4 units: [nt][lane] the B operands, then [lane] {A of blocks 0..3}, then [lane]
+// {B (the FMA's constant) of blocks 0..3}: six coalesced 16-byte loads per lane.
+constexpr int kFirstTabVec = 6 * 64;
+__device__ __forceinline__ void qnn_first_u8_tab_store(uint4* __restrict__ tab, int nt, int lane, const FirstU8Entry& t) {
+    tab[nt * 64 + lane] = make_uint4(t.wd[0], t.wd[1], t.wd[2], t.wd[3]);
+    reinterpret_cast<float*>(tab + 4 * 64 + lane)[nt] = t.A;
+    reinterpret_cast<float*>(tab + 5 * 64 + lane)[nt] = t.B;
+}
 #endif
 
 // host side of the handle
@@ -80,8 +155,11 @@ struct qnn_fold {
     int mode;                      // 1: u = float(accw + beta) * A;  2 ("bits"): u = fma(as_float(accw + beta'), A, C);
                                    // 3 (image entry, x_store = QNN_STORE_U8): u = fma(float(S), A, C), no offset
     float* d_a;                    // [cout] slope
-    int32_t* d_b;                  // [cout] offset, units of acc / 256 (mode 2: + 0x4B400000)
+    int32_t* d_b;                  // [cout] offset, units of acc / 256 (mode 2: + 0x4B400000); mode 3: what the bits search
+                                   // found for the table below (beta + 0x4B400000, or 0), reported only
     float* d_c;                    // [cout] mode 2: C = float(-12582912 * A); mode 1: zeros
+    void* d_tab;                   // mode 3, usable, 64 filters: the first layer's operand table (kFirstTabVec uint4), or NULL
+    int tab_bits;                  // the table carries the bits form (A', C', beta in the offset block) -- every channel passed
     int folded;                    // channels whose fold reproduced the chain on the whole domain
     long long points;
     int acc_lo, acc_hi;

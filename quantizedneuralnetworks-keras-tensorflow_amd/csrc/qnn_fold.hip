@@ -198,7 +198,20 @@ struct FoldProblemU8 {
     int32_t* status;
     int32_t* dom;
     unsigned long long* points;
+    // second search, the bits form of the same fold (qnn_fold.h), or A2 == nullptr: not searched
+    float* A2;
+    float* C2;
+    int32_t* beta2;
+    int32_t* status2;
 };
+
+// bits form: A' = the mode-3 slope and +-1 .. +-24 float32 neighbours, C' = float(C - 12582912 A') and +-1 .. +-100
+// neighbours.  One ulp of C' is 0.75 .. 1.5 steps of S and one ulp of A' moves 12582912 A' by 1.5 times as much, so the
+// candidates place the thresholds at multiples of half that ratio modulo one step; where the ratio sits next to a simple
+// fraction the multiples bunch and a channel may find nothing (the handle then keeps mode 3 in its table).
+constexpr int kBitsSlopes = 49;
+constexpr int kBitsConsts = 201;
+constexpr int kBitsBeta = 127;       // |beta|: one signed byte of the MFMA's offset block
 
 __global__ __launch_bounds__(kThreads) void k_fold_prepare_u8(FoldProblemU8 p) {
     __shared__ long long sh[kThreads];
@@ -211,7 +224,10 @@ __global__ __launch_bounds__(kThreads) void k_fold_prepare_u8(FoldProblemU8 p) {
     }
     lo = block_sum(lo, sh);
     hi = block_sum(hi, sh);
-    if (t == 0) { p.dom[2 * c] = (int)lo; p.dom[2 * c + 1] = (int)hi; p.status[c] = 0; p.A[c] = 0.0f; p.C[c] = 0.0f; p.points[c] = 0; }
+    if (t == 0) {
+        p.dom[2 * c] = (int)lo; p.dom[2 * c + 1] = (int)hi; p.status[c] = 0; p.A[c] = 0.0f; p.C[c] = 0.0f; p.points[c] = 0;
+        if (p.A2) { p.A2[c] = 0.0f; p.C2[c] = 0.0f; p.beta2[c] = 0; p.status2[c] = 0; }
+    }
     const U8Affine af = qnn_u8_affine(p.e, c);
     if (!(af.A == af.A) || !(af.B == af.B) || af.A == 0.0f) return;                    // uniform
     const double k12 = 4096.0 / 32767.0;
@@ -219,6 +235,8 @@ __global__ __launch_bounds__(kThreads) void k_fold_prepare_u8(FoldProblemU8 p) {
     // snorm16 rounds to nearest and the code is the floor of the Q12 value: the -1/8192 centres the thresholds on k - 1/2
     const float c_nom = (float)(((double)af.B + 0.5 - 1.0 / 8192.0) * k12);
     const long long npts = hi - lo + 1;
+    float A3 = 0.0f, C3 = 0.0f;
+    bool found = false;
     for (int cand = 0; cand < 5 * 33; ++cand) {
         const int ia = cand / 33, ic = cand % 33;
         const int da = ia == 0 ? 0 : ((ia & 1) ? (ia + 1) / 2 : -(ia / 2));
@@ -233,9 +251,92 @@ __global__ __launch_bounds__(kThreads) void k_fold_prepare_u8(FoldProblemU8 p) {
         bad = block_sum(bad, sh);
         if (bad == 0) {
             if (t == 0) { p.A[c] = A; p.C[c] = C; p.status[c] = 1; p.points[c] = (unsigned long long)npts; }
+            A3 = A; C3 = C; found = true;
+            break;
+        }
+    }
+    if (!found || !p.A2) return;                                                       // uniform
+    // ---- the bits form of the same fold: code = snorm16(fma(as_float(0x4B400000 + z + beta), A', C')) >> 12 on the sum the
+    // kernel pools, z = S, or -S for a channel with negative BN scale (negated filter, negated slope: qnn_first_u8_entry).
+    // The chain is non-decreasing in z.  Per candidate (A', C'): the folded thresholds X(k) in t = z + beta by bisection on
+    // the device function the kernel inlines, the interval of beta that puts them on the chain's thresholds T(k), then the
+    // proof on every point, as for the other modes. ----
+    const bool flip = p.e.bn_inv && p.e.bn_inv[c] < 0.0f;
+    const int sgn = flip ? -1 : 1;
+    const long long zlo = flip ? -hi : lo, zhi = flip ? -lo : hi;
+    const int m = (int)p.e.act_m;
+    const int nk = 2 * m - 1;
+    const bool active = t < nk;
+    const int k = active ? t - (m - 1) : 0;
+    auto want_z = [&](long long z) { return (int)qnn_u8_value(__fmaf_rn((float)(int)(sgn * z), af.A, af.B), p.e); };
+    long long Tz = zhi + 1;
+    if (active) {
+        long long a = zlo, b = zhi + 1;
+        while (a < b) {
+            const long long mid = a + ((b - a) >> 1);
+            if (want_z(mid) >= k) b = mid; else a = mid + 1;
+        }
+        Tz = a;
+    }
+    const long long Zlo = zlo - 2 * kBitsBeta, Zhi = zhi + 2 * kBitsBeta;
+    for (int cand = 0; cand < kBitsSlopes * kBitsConsts; ++cand) {
+        const int ia = cand / kBitsConsts, ic = cand % kBitsConsts;
+        const int da = ia == 0 ? 0 : ((ia & 1) ? (ia + 1) / 2 : -(ia / 2));
+        const int dc = ic == 0 ? 0 : ((ic & 1) ? (ic + 1) / 2 : -(ic / 2));
+        const float A = __int_as_float(__float_as_int(A3) + da);
+        const float Az = flip ? -A : A;
+        const float c_nom = (float)((double)C3 - kFoldMagic * (double)Az);
+        const float C = __int_as_float(__float_as_int(c_nom) + dc);
+        long long blo = -kBitsBeta, bhi = kBitsBeta;
+        if (active) {
+            long long X;
+            if (qnn_fold_code(kFoldMagicBits + (int)Zhi, Az, C, 2, false, 0) < k) X = kInf;
+            else if (qnn_fold_code(kFoldMagicBits + (int)Zlo, Az, C, 2, false, 0) >= k) X = -kInf;
+            else {
+                long long a = Zlo, b = Zhi;                                    // F(a) < k <= F(b)
+                while (b - a > 1) {
+                    const long long mid = a + ((b - a) >> 1);
+                    if (qnn_fold_code(kFoldMagicBits + (int)mid, Az, C, 2, false, 0) >= k) b = mid; else a = mid;
+                }
+                X = b;
+            }
+            if (Tz > zlo && Tz <= zhi) {               // threshold inside the domain: X - beta == T
+                if (X == kInf || X == -kInf) { blo = kInf; bhi = -kInf; }
+                else { blo = X - Tz; bhi = X - Tz; }
+            } else if (Tz == zlo) {                    // the chain is >= k everywhere
+                if (X == kInf) { blo = kInf; bhi = -kInf; }
+                else if (X != -kInf) blo = X - zlo;
+            } else {                                   // never
+                if (X == -kInf) { blo = kInf; bhi = -kInf; }
+                else if (X != kInf) bhi = X - zhi - 1;
+            }
+        }
+        blo = block_reduce(blo, true, sh);
+        bhi = block_reduce(bhi, false, sh);
+        if (blo < -kBitsBeta) blo = -kBitsBeta;
+        if (bhi > kBitsBeta) bhi = kBitsBeta;
+        if (blo > bhi) continue;                       // uniform
+        const int beta = (int)(blo > 0 ? blo : bhi < 0 ? bhi : 0);             // the admissible offset nearest to zero
+        long long bad = 0;
+        for (long long i = t; i < npts; i += kThreads) {
+            const int z = (int)(zlo + i);
+            bad += want_z(z) != qnn_fold_code(kFoldMagicBits + z + beta, Az, C, 2, false, 0);
+        }
+        bad = block_sum(bad, sh);
+        if (bad == 0) {
+            if (t == 0) { p.A2[c] = A; p.C2[c] = C; p.beta2[c] = beta; p.status2[c] = 1; }
             return;
         }
     }
+}
+
+// the operand table of the byte first layer (qnn_fold.h): one workgroup, wave nt = filter block nt, as the kernel's own
+// preamble lays it out
+__global__ __launch_bounds__(256) void k_first_u8_table(EpiArgs e, const float* __restrict__ wq, float wscale, float D,
+                                                        const float* __restrict__ fa, const float* __restrict__ fc,
+                                                        const int32_t* __restrict__ fbeta, uint4* __restrict__ tab) {
+    const int lane = threadIdx.x & 63, nt = threadIdx.x >> 6;
+    qnn_first_u8_tab_store(tab, nt, lane, qnn_first_u8_entry<true>(e, wq, wscale, D, nt, lane, fa, fc, fbeta));
 }
 
 __global__ __launch_bounds__(kThreads) void k_fold_eval(const float* __restrict__ A, const int32_t* __restrict__ beta,
@@ -289,10 +390,13 @@ extern "C" int qnn_fold_prepare(const qnn_weights_t* w, int x_store, int x_bits,
     f->cout = w->cout;
     int32_t *d_status = nullptr, *d_dom = nullptr;
     unsigned long long* d_points = nullptr;
+    float* d_bits = nullptr;         // image entry: the bits search's A'[cout], C'[cout], beta[cout], status[cout]
     auto fail = [&](int code) {
         if (f->d_a) (void)hipFree(f->d_a);
         if (f->d_b) (void)hipFree(f->d_b);
         if (f->d_c) (void)hipFree(f->d_c);
+        if (f->d_tab) (void)hipFree(f->d_tab);
+        if (d_bits) (void)hipFree(d_bits);
         if (d_status) (void)hipFree(d_status);
         if (d_dom) (void)hipFree(d_dom);
         if (d_points) (void)hipFree(d_points);
@@ -328,7 +432,7 @@ extern "C" int qnn_fold_prepare(const qnn_weights_t* w, int x_store, int x_bits,
     p.res_scale = ldexpf(1.0f, -(4 - 1));
     p.post_scale = f->post_scale;
     p.A = f->d_a; p.beta = f->d_b; p.C = f->d_c; p.status = d_status; p.dom = d_dom; p.points = d_points;
-    int32_t* h_status = (int32_t*)malloc(sizeof(int32_t) * 3 * (size_t)w->cout);
+    int32_t* h_status = (int32_t*)malloc(sizeof(int32_t) * 4 * (size_t)w->cout);
     unsigned long long* h_points = (unsigned long long*)malloc(sizeof(unsigned long long) * (size_t)w->cout);
     if (!h_status || !h_points) { free(h_status); free(h_points); qnn_set_error("qnn_fold_prepare: out of host memory"); return fail(QNN_ENOMEM); }
     FoldProblemU8 pu;
@@ -340,6 +444,15 @@ extern "C" int qnn_fold_prepare(const qnn_weights_t* w, int x_store, int x_bits,
         pu.A = f->d_a; pu.C = f->d_c; pu.status = d_status; pu.dom = d_dom; pu.points = d_points;
         (void)hipMemsetAsync(f->d_b, 0, sizeof(int32_t) * w->cout, s);
     }
+    // the layers k_conv_first_u8's folded form takes (qnn_try_launch_first_u8) get the operand table, and with it the
+    // search for the bits form
+    const bool table = image && w->cout == 64 && w->wshift <= 6;
+    const bool bits = table && !(epi->flags & QNN_EPI_NO_FIRST_BITS);
+    if (bits) {
+        FOLD_HIP(hipMalloc(&d_bits, sizeof(float) * 4 * w->cout));
+        pu.A2 = d_bits; pu.C2 = d_bits + w->cout;
+        pu.beta2 = (int32_t*)(d_bits + 2 * w->cout); pu.status2 = (int32_t*)(d_bits + 3 * w->cout);
+    }
     // the "bits" form first (one instruction fewer per value; needs the accumulators inside +-2^22 on every channel),
     // the conversion form if some channel has no fold in it; the image entry has its own single form (mode 3)
     for (int mode = image ? 3 : 2; mode >= (image ? 3 : 1); --mode) {
@@ -350,6 +463,8 @@ extern "C" int qnn_fold_prepare(const qnn_weights_t* w, int x_store, int x_bits,
         if (he == hipSuccess) he = hipMemcpyAsync(h_status, d_status, sizeof(int32_t) * w->cout, hipMemcpyDeviceToHost, s);
         if (he == hipSuccess) he = hipMemcpyAsync(h_status + w->cout, d_dom, sizeof(int32_t) * 2 * w->cout, hipMemcpyDeviceToHost, s);
         if (he == hipSuccess) he = hipMemcpyAsync(h_points, d_points, sizeof(unsigned long long) * w->cout, hipMemcpyDeviceToHost, s);
+        if (he == hipSuccess && bits)
+            he = hipMemcpyAsync(h_status + 3 * w->cout, pu.status2, sizeof(int32_t) * w->cout, hipMemcpyDeviceToHost, s);
         if (he == hipSuccess) he = hipStreamSynchronize(s);
         if (he != hipSuccess) {
             free(h_status); free(h_points);
@@ -368,8 +483,35 @@ extern "C" int qnn_fold_prepare(const qnn_weights_t* w, int x_store, int x_bits,
         }
         if (f->folded == w->cout) break;
     }
+    if (table && f->folded == w->cout) {
+        // every channel of the bits search passed, or the table carries the mode-3 constants (wave-uniform in the kernel)
+        f->tab_bits = bits ? 1 : 0;
+        for (int c = 0; bits && c < w->cout; ++c)
+            if (!h_status[3 * w->cout + c]) f->tab_bits = 0;
+        hipError_t he = hipMalloc(&f->d_tab, sizeof(uint4) * kFirstTabVec);
+        if (he == hipSuccess) {
+            hipLaunchKernelGGL(k_first_u8_table, dim3(1), dim3(256), 0, s, pu.e, w->d_wq, pu.wscale, pu.e.scale,
+                               f->tab_bits ? pu.A2 : f->d_a, f->tab_bits ? pu.C2 : f->d_c,
+                               f->tab_bits ? pu.beta2 : (const int32_t*)nullptr, (uint4*)f->d_tab);
+            he = hipGetLastError();
+        }
+        if (he == hipSuccess) he = hipStreamSynchronize(s);
+        if (he == hipSuccess && bits) {
+            // qnn_fold_constants reports the bits form's offsets (+ 0x4B400000, as in mode 2; 0 = nothing found for the
+            // channel) next to the mode-3 A and C
+            he = hipMemcpy(h_status, pu.beta2, sizeof(int32_t) * w->cout, hipMemcpyDeviceToHost);
+            for (int c = 0; c < w->cout; ++c) h_status[c] = h_status[3 * w->cout + c] ? h_status[c] + kFoldMagicBits : 0;
+            if (he == hipSuccess) he = hipMemcpy(f->d_b, h_status, sizeof(int32_t) * w->cout, hipMemcpyHostToDevice);
+        }
+        if (he != hipSuccess) {
+            free(h_status); free(h_points);
+            qnn_set_error("qnn_fold_prepare: %s", hipGetErrorString(he));
+            return fail(QNN_EHIP);
+        }
+    }
     free(h_status); free(h_points);
     (void)hipFree(d_status); (void)hipFree(d_dom); (void)hipFree(d_points);
+    if (d_bits) (void)hipFree(d_bits);
 #undef FOLD_HIP
     *out = f;
     return QNN_OK;
@@ -380,6 +522,7 @@ extern "C" int qnn_fold_free(qnn_fold_t* f) {
     if (f->d_a) (void)hipFree(f->d_a);
     if (f->d_b) (void)hipFree(f->d_b);
     if (f->d_c) (void)hipFree(f->d_c);
+    if (f->d_tab) (void)hipFree(f->d_tab);
     free(f);
     return QNN_OK;
 }
