@@ -198,6 +198,9 @@ typedef struct qnn_epilogue {
  *   QNN_EPI_NO_FIRST_BITS  read by qnn_fold_prepare, not by a launch: the image entry's fold does not search the
  *                        bits form, so the handle's table carries the mode-3 constants (what a handle holds when the
  *                        search fails on some channel; tests)
+ *   QNN_EPI_NO_HALO_TAB  k_conv_mfma_halo with a "bits" fold: every wave derives its lanes' fold constants (and the FP6
+ *                        form's accumulator offset) in the kernel's preamble instead of loading the per-lane table that
+ *                        qnn_fold_prepare built into the handle
  * The restricted-domain first-layer kernels are selected by the TYPED input stores QNN_STORE_F32_IMAGE /
  * QNN_STORE_F32_UNIT of the call (above), never by a switch.
  */
@@ -208,6 +211,7 @@ typedef struct qnn_epilogue {
 #define QNN_EPI_NO_FP6      16u
 #define QNN_EPI_NO_FIRST_TAB   32u
 #define QNN_EPI_NO_FIRST_BITS  64u
+#define QNN_EPI_NO_HALO_TAB    128u
 
 /* ---- library ------------------------------------------------------------ */
 int         qnn_version(void);

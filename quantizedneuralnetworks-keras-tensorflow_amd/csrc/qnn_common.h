@@ -57,7 +57,8 @@ struct qnn_weights {
     uint32_t* h_flag;     // domain flag (pinned, device-visible host word; qnn_weights_check) or nullptr
     uint32_t* d_flag;     // the same word through the device's address space
     float* d_f32act;      // float32-activation kernel (qnn_f32act.hip): filters k-step major [cout/16][K/4][64 lanes], or nullptr
-    uint8_t* d_fp6;       // I4 3x3, cin 64: the FP6 (e2m3) filter image of k_conv_mfma_halo [cout][9][48 B], or nullptr
+    uint8_t* d_fp6;       // I4 3x3, cin 64: the FP6 (e2m3) filter image of k_conv_mfma_halo, per 64-filter slice the 27 648
+                          // bytes of the kernel's two LDS planes in LDS order (k_fp6_weights), or nullptr
     int32_t* d_fp6_wsum;  // [cout] sum of the channel's 576 weight codes (inside the d_fp6 allocation)
 };
 
@@ -139,6 +140,9 @@ struct EpiArgs {
     // in-kernel preamble (QNN_EPI_NO_FIRST_TAB); first_tab_bits: the table carries the bits form of the fold
     const void* first_tab;
     int first_tab_bits;
+    // k_conv_mfma_halo with a mode-2 fold: the handle's per-lane epilogue table (qnn_fold.h, qnn_halo_epi_entry) or nullptr =
+    // the in-kernel preamble (QNN_EPI_NO_HALO_TAB, or a layer the halo kernel does not take)
+    const void* halo_tab;
 };
 
 // One conv call as every route of the dispatch sees it: validated, geometry and epilogue filled in once

@@ -1143,6 +1143,7 @@ int check_epilogue(const qnn_weights* w, const qnn_epilogue_t* epi, int xshift, 
     e->fold_c = nullptr;
     e->first_tab = nullptr;
     e->first_tab_bits = 0;
+    e->halo_tab = nullptr;
     e->dom_flag = epi->domain_flag;
     e->flags = epi->flags;
     e->first_mode = 0;
@@ -1187,6 +1188,7 @@ int check_epilogue(const qnn_weights* w, const qnn_epilogue_t* epi, int xshift, 
             e->first_tab = f->d_tab;
             e->first_tab_bits = f->tab_bits;
         }
+        if (f->folded == f->cout && f->mode == 2 && f->d_halo_tab && !(epi->flags & QNN_EPI_NO_HALO_TAB)) e->halo_tab = f->d_halo_tab;
     }
     QNN_REQUIRE(epi->trick_s == 0.0f || (epi->trick_s > 0.0f && epi->trick_s < 1.0e6f), QNN_EINVAL,
                 "epilogue: trick_s=%g (the layer's kernel_lr_multiplier, or 0)", (double)epi->trick_s);

@@ -140,6 +140,52 @@ __device__ __forceinline__ void qnn_first_u8_tab_store(uint4* __restrict__ tab, 
     reinterpret_cast<float*>(tab + 4 * 64 + lane)[nt] = t.A;
     reinterpret_cast<float*>(tab + 5 * 64 + lane)[nt] = t.B;
 }
+
+// ---- per-lane epilogue constants of k_conv_mfma_halo (qnn_mfma_areg.hip) with a "bits" fold ---------------------------
+// Lane li of a wave owns the channels c = nbase + 32 b + li (b = 0, 1) of its 64-filter slice: slope and FMA constant of
+// the fold, the accumulator offset in its int8 value (fold_b: the MFMA's initial accumulator) and in its FP6 value (added
+// to the pooled bit pattern << 8:  - 2048 sum(w) - (0x4B400000 << 8) on top, modulo 2^32; 0 without wsum), and bit b of
+// `neg` = the channel's BN scale is negative (its 2x2 window is pooled by the minimum).
+// ONE definition: the kernel's own preamble (QNN_EPI_NO_HALO_TAB, or no table in the handle) and the table
+// qnn_fold_prepare builds once per mode-2 handle both call it, so the table holds what a launch without it computes.
+struct HaloEpiEntry {
+    float a[2], c[2];
+    int b8[2], b6[2];
+    uint32_t neg;
+};
+__device__ __forceinline__ HaloEpiEntry qnn_halo_epi_entry(const EpiArgs& e, const int32_t* __restrict__ wsum, int nbase,
+                                                           int li) {
+    HaloEpiEntry t;
+    t.neg = 0u;
+#pragma unroll
+    for (int b = 0; b < 2; ++b) {
+        const int c = nbase + b * 32 + li;
+        t.a[b] = e.fold_a[c]; t.c[b] = e.fold_c[c]; t.b8[b] = e.fold_b[c];
+        t.b6[b] = wsum ? (int)((uint32_t)t.b8[b] - 2048u * (uint32_t)wsum[c] - ((uint32_t)kFoldMagicBits << 8)) : 0;
+        if (e.bn_inv && e.bn_inv[c] < 0.0f) t.neg |= 1u << b;
+    }
+    return t;
+}
+// The table in device memory, in uint4 units: [slice][3][64 lanes] = {a0, a1, c0, c1}, {b8 of b = 0, 1, neg, 0},
+// {b6 of b = 0, 1, neg, 0}: a form loads the first and the one of its matrix pipe, two coalesced 16-byte loads per lane.
+constexpr int kHaloTabVec = 3 * 64;
+__device__ __forceinline__ void qnn_halo_epi_tab_store(uint4* __restrict__ tab, int slice, int lane, const HaloEpiEntry& t) {
+    uint4* o = tab + slice * kHaloTabVec + lane;
+    o[0] = make_uint4(__float_as_uint(t.a[0]), __float_as_uint(t.a[1]), __float_as_uint(t.c[0]), __float_as_uint(t.c[1]));
+    o[64] = make_uint4((uint32_t)t.b8[0], (uint32_t)t.b8[1], t.neg, 0u);
+    o[128] = make_uint4((uint32_t)t.b6[0], (uint32_t)t.b6[1], t.neg, 0u);
+}
+template <bool FP6>
+__device__ __forceinline__ HaloEpiEntry qnn_halo_epi_tab_load(const uint4* __restrict__ tab, int slice, int lane) {
+    const uint4* o = tab + slice * kHaloTabVec + lane;
+    const uint4 v0 = o[0], v1 = o[FP6 ? 128 : 64];
+    HaloEpiEntry t;
+    t.a[0] = __uint_as_float(v0.x); t.a[1] = __uint_as_float(v0.y);
+    t.c[0] = __uint_as_float(v0.z); t.c[1] = __uint_as_float(v0.w);
+    t.b8[0] = t.b6[0] = (int)v1.x; t.b8[1] = t.b6[1] = (int)v1.y;     // (the form reads only its own)
+    t.neg = v1.z;
+    return t;
+}
 #endif
 
 // host side of the handle
@@ -159,6 +205,8 @@ struct qnn_fold {
                                    // found for the table below (beta + 0x4B400000, or 0), reported only
     float* d_c;                    // [cout] mode 2: C = float(-12582912 * A); mode 1: zeros
     void* d_tab;                   // mode 3, usable, 64 filters: the first layer's operand table (kFirstTabVec uint4), or NULL
+    void* d_halo_tab;              // mode 2, usable, 3x3 on 64 input channels, cout % 64 == 0 (the layers k_conv_mfma_halo takes): its
+                                   // per-lane epilogue table (cout / 64 x kHaloTabVec uint4), or NULL
     int tab_bits;                  // the table carries the bits form (A', C', beta in the offset block) -- every channel passed
     int folded;                    // channels whose fold reproduced the chain on the whole domain
     long long points;

@@ -339,6 +339,13 @@ __global__ __launch_bounds__(256) void k_first_u8_table(EpiArgs e, const float* 
     qnn_first_u8_tab_store(tab, nt, lane, qnn_first_u8_entry<true>(e, wq, wscale, D, nt, lane, fa, fc, fbeta));
 }
 
+// the per-lane epilogue table of k_conv_mfma_halo (qnn_fold.h): one wave per 64-filter slice.  Lanes 32-63 hold what lanes
+// 0-31 hold (a lane's channels depend on lane & 31), as in the kernel's registers
+__global__ __launch_bounds__(64) void k_halo_epi_table(EpiArgs e, const int32_t* __restrict__ wsum, uint4* __restrict__ tab) {
+    const int lane = threadIdx.x;
+    qnn_halo_epi_tab_store(tab, blockIdx.x, lane, qnn_halo_epi_entry(e, wsum, blockIdx.x * 64, lane & 31));
+}
+
 __global__ __launch_bounds__(kThreads) void k_fold_eval(const float* __restrict__ A, const int32_t* __restrict__ beta,
                                                         const float* __restrict__ C, int mode, int c,
                                                         int has_res, const int32_t* __restrict__ acc,
@@ -396,6 +403,7 @@ extern "C" int qnn_fold_prepare(const qnn_weights_t* w, int x_store, int x_bits,
         if (f->d_b) (void)hipFree(f->d_b);
         if (f->d_c) (void)hipFree(f->d_c);
         if (f->d_tab) (void)hipFree(f->d_tab);
+        if (f->d_halo_tab) (void)hipFree(f->d_halo_tab);
         if (d_bits) (void)hipFree(d_bits);
         if (d_status) (void)hipFree(d_status);
         if (d_dom) (void)hipFree(d_dom);
@@ -509,6 +517,25 @@ extern "C" int qnn_fold_prepare(const qnn_weights_t* w, int x_store, int x_bits,
             return fail(QNN_EHIP);
         }
     }
+    // the layers k_conv_mfma_halo takes with a bits fold get its per-lane epilogue table (the FP6 value of the offset needs
+    // the per-filter sums kept beside the FP6 filter image)
+    if (!image && f->mode == 2 && f->folded == w->cout && w->kh == 3 && w->kw == 3 && w->cin == 64 && w->cout % 64 == 0 &&
+        w->d_fp6_wsum) {
+        EpiArgs te = p.e;
+        te.fold_a = f->d_a; te.fold_b = f->d_b; te.fold_c = f->d_c;
+        hipError_t he = hipMalloc(&f->d_halo_tab, sizeof(uint4) * kHaloTabVec * (size_t)(w->cout / 64));
+        if (he == hipSuccess) {
+            hipLaunchKernelGGL(k_halo_epi_table, dim3((unsigned)(w->cout / 64)), dim3(64), 0, s, te, w->d_fp6_wsum,
+                               (uint4*)f->d_halo_tab);
+            he = hipGetLastError();
+        }
+        if (he == hipSuccess) he = hipStreamSynchronize(s);
+        if (he != hipSuccess) {
+            free(h_status); free(h_points);
+            qnn_set_error("qnn_fold_prepare: %s", hipGetErrorString(he));
+            return fail(QNN_EHIP);
+        }
+    }
     free(h_status); free(h_points);
     (void)hipFree(d_status); (void)hipFree(d_dom); (void)hipFree(d_points);
     if (d_bits) (void)hipFree(d_bits);
@@ -523,6 +550,7 @@ extern "C" int qnn_fold_free(qnn_fold_t* f) {
     if (f->d_b) (void)hipFree(f->d_b);
     if (f->d_c) (void)hipFree(f->d_c);
     if (f->d_tab) (void)hipFree(f->d_tab);
+    if (f->d_halo_tab) (void)hipFree(f->d_halo_tab);
     free(f);
     return QNN_OK;
 }

@@ -716,8 +716,10 @@ __global__ __launch_bounds__(256) void k_expand_i4_weights(const uint32_t* __res
 
 // FP6 (e2m3) filter image of k_conv_mfma_halo's FP6 form: one thread per (filter, tap, channel half) builds the six
 // dwords a B-operand lane supplies -- field e = 6-bit code of the channel qnn_fp6_channel(e) of that half, w / 8 in
-// sign-magnitude (|w| <= 8 is exact) -- stored as the kernel's LDS image wants them: [filter][tap][dwords 0-3 of half 0,
-// dwords 0-3 of half 1, dwords 4-5 of half 0, dwords 4-5 of half 1]; then the per-filter sum of the 576 codes
+// sign-magnitude (|w| <= 8 is exact) -- and stores them where the kernel's LDS holds them, so that the kernel copies a
+// 64-filter slice's 27 648 bytes as they are: plane A [tap][filter][2 x 16 B = dwords 0-3 of a half, slot = half XOR bit 3
+// of the filter], then plane B [tap][filter][2 x 8 B = dwords 4-5, slot = half XOR bit 4]; then the per-filter sum of the
+// 576 codes
 __global__ __launch_bounds__(256) void k_fp6_weights(const uint32_t* __restrict__ packed, uint32_t* __restrict__ img,
                                                      int32_t* __restrict__ wsum, int cout) {
     const int i = blockIdx.x * 256 + threadIdx.x;          // (c * 9 + tap) * 2 + h
@@ -732,10 +734,13 @@ __global__ __launch_bounds__(256) void k_fp6_weights(const uint32_t* __restrict_
         d[(6 * e) >> 5] |= f << ((6 * e) & 31);
         if (((6 * e) & 31) > 26) d[((6 * e) >> 5) + 1] |= f >> (32 - ((6 * e) & 31));
     }
-    uint32_t* o = img + ct * 12;
-    for (int j = 0; j < 4; ++j) o[4 * h + j] = d[j];
-    o[8 + 2 * h] = d[4];
-    o[9 + 2 * h] = d[5];
+    const int c = ct / 9, tap = ct - c * 9, col = c & 63;
+    uint32_t* o = img + (size_t)(c >> 6) * (kFp6SliceBytes / 4);
+    uint32_t* oa = o + (tap * 2048 + col * 32 + ((h ^ ((col >> 3) & 1)) << 4)) / 4;
+    for (int j = 0; j < 4; ++j) oa[j] = d[j];
+    uint32_t* ob = o + (kFp6PlaneB + tap * 1024 + col * 16 + ((h ^ ((col >> 4) & 1)) << 3)) / 4;
+    ob[0] = d[4];
+    ob[1] = d[5];
     if (h == 0 && ct % 9 == 0) {
         int sum = 0;
         for (int k = 0; k < 9 * 64; ++k) sum += ((int)(p[k >> 3] << (28 - 4 * (k & 7)))) >> 28;

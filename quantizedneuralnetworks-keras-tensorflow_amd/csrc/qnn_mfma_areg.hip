@@ -792,10 +792,13 @@ __global__ __launch_bounds__(256, (OUT == QNN_STORE_F32 ? 2 : 3)) void k_conv_mf
 // their dwords 4-5 ([row][pixel][2 eight-byte slots], slot = lane half XOR (row & 1): a ds_read_b64 group of 32 lanes
 // covers 16 pixels on two rows of different parity (TWP 8) or 4 x 8 pixels on rows whose 16-byte columns pair up with
 // the opposite parity (TWP 4, pitch 192 B), conflict-free).  Filters: plane A [tap][filter][2 x 16 B, half XOR bit 3 of
-// the filter], plane B [tap][filter][2 x 8 B, half XOR bit 4], again one bank per lane of a read group.
-// Only the folded layers without the classifier take it (B0 of the CIFAR VGG: 30.0 -> 25.6 us at batch 4096).  The
-// float-chain epilogue (binary networks) needs more registers than the two waves per SIMD leave and spilled (the bnn
-// step went from 66.6 to 83.8 us); with the classifier (C0) the form measured 11.5 against 11.0 us.
+// the filter], plane B [tap][filter][2 x 8 B, half XOR bit 4], again one bank per lane of a read group; k_fp6_weights
+// writes the slice's image in exactly this order, so it is copied as it is.
+// The folded layers take it, with the classifier or without (CIFAR B0: 30.0 -> 25.6 us at batch 4096; C0 + classifier
+// 10.2 -> 9.0 us, profiles/halo_tab/).  The float-chain epilogue (binary networks) needs more registers than the two
+// waves per SIMD leave and spilled (the bnn step went from 66.6 to 83.8 us).
+// What a FOLD wave needs per lane beside the filters -- slope, FMA constant, offset, pooling sign -- comes from the fold
+// handle's table (qnn_fold.h, qnn_halo_epi_entry; QNN_EPI_NO_HALO_TAB: derived here by the same function).
 template <int TWP, int NW, bool HEAD, bool FOLD = false, bool FP6 = false>
 __global__ __launch_bounds__(NW * 64, 1) void k_conv_mfma_halo(MfmaGeom mg, EpiArgs e, const uint8_t* __restrict__ x,
                                                                const uint8_t* __restrict__ wq8, void* __restrict__ y,
@@ -810,7 +813,7 @@ __global__ __launch_bounds__(NW * 64, 1) void k_conv_mfma_halo(MfmaGeom mg, EpiA
     constexpr int PITCHB = RWP * 16, REGION = FP6 ? PLANE + RH * PITCHB : 2 * PLANE;
     constexpr int B_STEP = 64 * 64, FILT = FP6 ? 9 * 3072 : 9 * B_STEP;
     constexpr int WB6 = 9 * 2048;                          // FP6: filter plane B
-    static_assert(!FP6 || (FOLD && !HEAD), "the FP6 form serves the folded layers without the classifier");
+    static_assert(!FP6 || FOLD, "the FP6 form serves the folded layers");
     constexpr int HTAB = FILT + NW * REGION;
     static_assert(NCH <= 256, "four load rounds per lane");
     const ConvGeom& g = mg.g;
@@ -821,19 +824,23 @@ __global__ __launch_bounds__(NW * 64, 1) void k_conv_mfma_halo(MfmaGeom mg, EpiA
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int nbase = blockIdx.y * 64;
     const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<uint8_t*>(wq8), 0, FP6 ? g.cout * 9 * 48 : (int)mg.w_bytes, 0x00020000);
+        const_cast<uint8_t*>(wq8), 0, FP6 ? (g.cout / 64) * kFp6SliceBytes : (int)mg.w_bytes, 0x00020000);
 
     // ---- the slice's filters -> LDS (first four waves; the areg kernel's image and swizzle) ----
-    if constexpr (FP6) {                               // [filter][tap][3 x 16 B] (k_fp6_weights) -> the two planes
-        for (int i = tid; i < 64 * 27; i += NW * 64) {
-            const int col = i / 27, r = i - col * 27, tap = r / 3, part = r - tap * 3;
-            uint4 v = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, ((nbase + col) * 9 + tap) * 48 + part * 16, 0, 0));
-            if (part < 2) {
-                *reinterpret_cast<uint4*>(smem + tap * 2048 + col * 32 + ((part ^ ((col >> 3) & 1)) << 4)) = v;
-            } else {
-                if ((col >> 4) & 1) v = make_uint4(v.z, v.w, v.x, v.y);
-                *reinterpret_cast<uint4*>(smem + WB6 + tap * 1024 + col * 16) = v;
-            }
+    if constexpr (FP6) {                               // the slice's image is in LDS order (k_fp6_weights): copied as it is
+        static_assert(FILT == kFp6SliceBytes && WB6 == kFp6PlaneB, "k_fp6_weights writes this kernel's LDS planes");
+        constexpr int NV = FILT / 16, TRIPS = (NV + NW * 64 - 1) / (NW * 64);
+        uint4 wv[TRIPS];
+#pragma unroll
+        for (int k = 0; k < TRIPS; ++k) {              // (a lane past the slice's end: out-of-range offset, nothing stored)
+            const int i = tid + k * NW * 64;
+            wv[k] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(
+                                                  wrsrc, i < NV ? i * 16 : (int)0x80000000, (int)blockIdx.y * FILT, 0));
+        }
+#pragma unroll
+        for (int k = 0; k < TRIPS; ++k) {
+            const int i = tid + k * NW * 64;
+            if (i < NV) *reinterpret_cast<uint4*>(smem + i * 16) = wv[k];
         }
     } else if (tid < 256) {
         const int srow = tid >> 2, sch = tid & 3;
@@ -850,35 +857,40 @@ __global__ __launch_bounds__(NW * 64, 1) void k_conv_mfma_halo(MfmaGeom mg, EpiA
     // ---- epilogue constants (as k_conv_mfma_areg) ----
     const bool binary = e.fn == QNN_FN_BINARY_TANH;
     const float mfold = binary ? 1.0f : e.act_m;
-    LaneEpi ke[2];
-    FoldEpi fe[2];
-#pragma unroll
-    for (int b = 0; b < 2; ++b) {
-        lane_epi_init<QNN_STORE_I4>(ke[b], e, nbase + b * 32 + li, li);
-        fe[b].nb = __fdiv_rn(ke[b].bias, e.scale);
-        fe[b].ninv = __fmul_rn(__fmul_rn(ke[b].inv, e.scale), mfold);
-        fe[b].nshift = __fmul_rn(ke[b].shift, mfold);
-    }
-    const bool all_pos = !__any((int)(ke[0].neg || ke[1].neg));
+    LaneEpi ke[2] = {};
+    FoldEpi fe[2] = {};
+    bool neg[2];
     float fda[2] = {0.0f, 0.0f}, fdc[2] = {0.0f, 0.0f};
     int fdb[2] = {0, 0};
     if constexpr (FOLD) {
+        // what the fold leaves per lane: from the handle's table (two 16-byte loads), or derived here by the function that
+        // built the table (QNN_EPI_NO_HALO_TAB; wave-uniform).  The float chain's constants are not formed.
+        lane_epi_sel<QNN_STORE_I4>(ke[0], li);
+        const HaloEpiEntry t = e.halo_tab ? qnn_halo_epi_tab_load<FP6>(reinterpret_cast<const uint4*>(e.halo_tab), blockIdx.y, lane)
+                                          : qnn_halo_epi_entry(e, wsum, nbase, li);
 #pragma unroll
         for (int b = 0; b < 2; ++b) {
-            const int c = nbase + b * 32 + li;
-            fda[b] = e.fold_a[c]; fdc[b] = e.fold_c[c]; fdb[b] = e.fold_b[c];
+            fda[b] = t.a[b]; fdc[b] = t.c[b]; fdb[b] = FP6 ? t.b6[b] : t.b8[b];
+            neg[b] = (t.neg >> b) & 1u;
+        }
+    } else {
+#pragma unroll
+        for (int b = 0; b < 2; ++b) {
+            lane_epi_init<QNN_STORE_I4>(ke[b], e, nbase + b * 32 + li, li);
+            fe[b].nb = __fdiv_rn(ke[b].bias, e.scale);
+            fe[b].ninv = __fmul_rn(__fmul_rn(ke[b].inv, e.scale), mfold);
+            fe[b].nshift = __fmul_rn(ke[b].shift, mfold);
+            neg[b] = ke[b].neg;
         }
     }
+    const bool all_pos = !__any((int)(neg[0] || neg[1]));
     // FP6: the accumulators start from 1.5 * 2^23 and hold the exact integer S + 8 sum(w) on top of it (every partial sum is
     // below 2^17 in magnitude, so the float stays in [2^23, 2^24) where its ulp is 1): the BIT PATTERN is the integer
     // SEED_BITS + S + 8 sum(w), which orders like the value.  256 S + offset = (bits << 8) + (offset - 2048 sum(w) -
-    // (SEED_BITS << 8)), all modulo 2^32
-    constexpr uint32_t SEED_BITS = 0x4B400000u;        // 1.5 * 2^23
+    // (SEED_BITS << 8)), all modulo 2^32: the FP6 value of the fold's offset (qnn_halo_epi_entry)
+    constexpr uint32_t SEED_BITS = (uint32_t)kFoldMagicBits;   // 1.5 * 2^23
     v16f seed6 = {};
     if constexpr (FP6) {
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-            fdb[b] = (int)((uint32_t)fdb[b] - 2048u * (uint32_t)wsum[nbase + b * 32 + li] - (SEED_BITS << 8));
         const float sv = __builtin_bit_cast(float, SEED_BITS);
         seed6 = v16f{sv, sv, sv, sv, sv, sv, sv, sv, sv, sv, sv, sv, sv, sv, sv, sv};
         asm volatile("" : "+v"(seed6));                // sixteen registers kept for the whole kernel, not sixteen moves per tile
@@ -886,7 +898,9 @@ __global__ __launch_bounds__(NW * 64, 1) void k_conv_mfma_halo(MfmaGeom mg, EpiA
     int hu = 0;
     float hbias = 0.0f, hinv = 1.0f, hshift = 0.0f;
     if constexpr (HEAD) {
-        for (int i = tid; i < 16 * 64 * 2; i += NW * 64) reinterpret_cast<uint32_t*>(smem + HTAB)[i] = hd.tab[i];
+        static_assert(HTAB % 16 == 0, "the classifier table is copied in 16-byte pieces");
+        for (int i = tid; i < 16 * 64 * 2 / 4; i += NW * 64)
+            reinterpret_cast<uint4*>(smem + HTAB)[i] = reinterpret_cast<const uint4*>(hd.tab)[i];
         hu = ((lane & 1) ? 8 : 0) + ((lane & 2) ? 4 : 0) + ((lane & 4) ? 2 : 0) + ((lane & 8) ? 1 : 0);
         if (hu < hd.units) {
             hbias = hd.bias ? hd.bias[hu] : 0.0f;
@@ -1041,7 +1055,7 @@ __global__ __launch_bounds__(NW * 64, 1) void k_conv_mfma_halo(MfmaGeom mg, EpiA
                     int pooled = max(max(i0, i1), max(i2, i3));
                     if constexpr (!ALLPOS) {
                         const int mn = min(min(i0, i1), min(i2, i3));
-                        pooled = ke[b].neg ? mn : pooled;
+                        pooled = neg[b] ? mn : pooled;
                     }
                     if constexpr (FP6) {                 // 256 S + the fold's offset: the int8 kernel's pooled accumulator
                         pv[a * 4 + g4] = (int)(((uint32_t)pooled << 8) + (uint32_t)fdb[b]);
@@ -1195,14 +1209,12 @@ void launch_halo_one_f(const MfmaGeom& mg, const EpiArgs& e, const void* x, cons
 }
 
 // a usable fold in the "bits" form (qnn_fold.h mode 2: e.fold_c set) takes the folded epilogue; with an FP6 filter image
-// and no classifier, on the FP6 form
+// on the FP6 form, with the classifier or without
 template <int TWP, int NW, bool HEAD>
 void launch_halo_one(const MfmaGeom& mg, const EpiArgs& e, const void* x, const uint8_t* w, HaloFp6 w6, void* y,
                      const HeadArgs& hd, hipStream_t s) {
     const bool fold = e.fold_a && e.fold_c && e.fn == QNN_FN_QUANTIZED_TANH;
-    if constexpr (!HEAD) {
-        if (fold && w6.w) return launch_halo_one_f<TWP, NW, HEAD, true, true>(mg, e, x, w6.w, w6.wsum, y, hd, s);
-    }
+    if (fold && w6.w) return launch_halo_one_f<TWP, NW, HEAD, true, true>(mg, e, x, w6.w, w6.wsum, y, hd, s);
     if (fold) launch_halo_one_f<TWP, NW, HEAD, true, false>(mg, e, x, w, nullptr, y, hd, s);
     else launch_halo_one_f<TWP, NW, HEAD, false, false>(mg, e, x, w, nullptr, y, hd, s);
 }

@@ -69,12 +69,9 @@ struct LaneEpi {
     uint32_t maskC, rotC;     // nibble stage (int4 only)
 };
 
+// the selectors of the packed outputs' transposes alone (a kernel whose epilogue constants come from elsewhere)
 template <int OUT>
-__device__ __forceinline__ void lane_epi_init(LaneEpi& k, const EpiArgs& e, int c, int li) {
-    k.bias = e.bias ? e.bias[c] : 0.0f;
-    k.inv = e.bn_inv ? e.bn_inv[c] : 1.0f;
-    k.shift = e.bn_inv ? e.bn_shift[c] : 0.0f;
-    k.neg = k.inv < 0.0f;
+__device__ __forceinline__ void lane_epi_sel(LaneEpi& k, int li) {
     if constexpr (OUT == QNN_STORE_I4) {
         k.selA = (li & 4) ? 0x03020706u : 0x05040100u;
         k.selB = (li & 2) ? 0x03070105u : 0x06020400u;
@@ -85,6 +82,14 @@ __device__ __forceinline__ void lane_epi_init(LaneEpi& k, const EpiArgs& e, int 
         k.selB = (li & 1) ? 0x03070105u : 0x06020400u;
         k.maskC = 0; k.rotC = 0;
     }
+}
+template <int OUT>
+__device__ __forceinline__ void lane_epi_init(LaneEpi& k, const EpiArgs& e, int c, int li) {
+    k.bias = e.bias ? e.bias[c] : 0.0f;
+    k.inv = e.bn_inv ? e.bn_inv[c] : 1.0f;
+    k.shift = e.bn_inv ? e.bn_shift[c] : 0.0f;
+    k.neg = k.inv < 0.0f;
+    lane_epi_sel<OUT>(k, li);
 }
 
 // BN on one value, reference op order (two roundings for the BN, one for the bias)
@@ -262,6 +267,8 @@ __host__ __device__ constexpr int qnn_fp6_channel(int e) {
     return 16 * (e >> 4) + (int)((0xEDBA8F5C29764310ull >> (4 * (e & 15))) & 15u);
 }
 
+// bytes of one 64-filter slice of the FP6 filter image (k_fp6_weights: the kernel's LDS planes A and B) and where B starts
+constexpr int kFp6PlaneB = 9 * 2048, kFp6SliceBytes = 9 * 3072;
 // the FP6 filter image k_conv_mfma_halo runs on (null: the int8 form)
 struct HaloFp6 {
     const uint8_t* w;
