@@ -275,6 +275,7 @@ int qnn_prepack_weights(int wkind, int wbits, float H, const float* kernel,
                         int kh, int kw, int cin, int cout, const float* bias,
                         int stride, int same_pad, int store, void* stream,
                         qnn_weights_t** out);
+/* A dilated window (dilation_rate of the conv layers): qnn_prepack_weights_dilated, declared in qnn_abi_dilation.h. */
 int qnn_free_weights(qnn_weights_t* w);
 /* read back the quantized kernel as float32 HWIO into a DEVICE buffer (tests) */
 int qnn_weights_dequant(const qnn_weights_t* w, float* kernel_hwio, void* stream);

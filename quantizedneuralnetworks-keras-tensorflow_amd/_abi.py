@@ -1,4 +1,4 @@
-"""ctypes binding of include/qnn_abi.h (csrc/libqnn_hip.so).
+"""ctypes binding of include/qnn_abi.h and include/qnn_abi_dilation.h (csrc/libqnn_hip.so).
 
 The library is loaded eagerly and loudly: a missing or unloadable .so raises at
 import time of any op that needs it (there is no CPU implementation to fall back
@@ -30,6 +30,10 @@ EXPORTS = [
     "qnn_conv2d_dense_forward", "qnn_avgpool_dense_softmax_forward",
     "qnn_fold_prepare", "qnn_fold_free", "qnn_fold_info", "qnn_fold_constants", "qnn_fold_eval",
 ]
+
+
+# include/qnn_abi_dilation.h: the extension header of ABI 4 (qnn_abi.h and its symbol list are unchanged)
+EXPORTS_DILATION = ["qnn_prepack_weights_dilated"]
 
 
 class Projection(ctypes.Structure):
@@ -109,6 +113,8 @@ def load():
     lib.qnn_softmax_f32.argtypes = [vp, vp, ctypes.c_size_t, ci, vp]
     lib.qnn_prepack_weights.argtypes = [ci, ci, fl, vp, ci, ci, ci, ci, vp, ci, ci, ci, vp,
                                         ctypes.POINTER(vp)]
+    lib.qnn_prepack_weights_dilated.argtypes = [ci, ci, fl, vp, ci, ci, ci, ci, vp, ci, ci, ci, ci, ci, vp,
+                                                ctypes.POINTER(vp)]
     lib.qnn_free_weights.argtypes = [vp]
     lib.qnn_weights_dequant.argtypes = [vp, vp, vp]
     lib.qnn_weights_check.argtypes = [vp, vp]
@@ -127,7 +133,7 @@ def load():
     lib.qnn_conv2d_workspace_bytes.restype = sz
     lib.qnn_conv2d_forward_f32in.argtypes = [vp, vp, ci, ci, ci, ci, ci, ctypes.POINTER(Epilogue), vp,
                                              vp, sz, vp]
-    for name in EXPORTS:   # every symbol the header declares must be exported
+    for name in EXPORTS + EXPORTS_DILATION:   # every symbol the headers declare must be exported
         getattr(lib, name)
     _lib = lib
     return lib
@@ -342,7 +348,9 @@ def release_deferred():
 class Weights:
     """Owner of an opaque qnn_weights_t handle."""
 
-    def __init__(self, wkind, wbits, H, kernel, bias, stride, same_pad, store):
+    def __init__(self, wkind, wbits, H, kernel, bias, stride, same_pad, store, dilation=(1, 1)):
+        """dilation: the layer's dilation_rate as (rows, columns); anything but (1, 1) goes through
+        qnn_prepack_weights_dilated, which refuses it together with stride != 1."""
         kernel = require_cuda(kernel, "prepack kernel")
         if kernel.dim() == 2:
             kh = kw = 1
@@ -355,12 +363,19 @@ class Weights:
         self.store = store
         self.stride = stride
         self.same_pad = same_pad
+        self.dilation = (int(dilation[0]), int(dilation[1]))
         self.handle = ctypes.c_void_p(None)
         release_deferred()
-        check(load().qnn_prepack_weights(wkind, wbits, float(H), ptr(kernel), kh, kw, cin, cout,
-                                         ptr(bias), stride, 1 if same_pad else 0, store,
-                                         stream_ptr(), ctypes.byref(self.handle)),
-              "qnn_prepack_weights")
+        if self.dilation == (1, 1):
+            check(load().qnn_prepack_weights(wkind, wbits, float(H), ptr(kernel), kh, kw, cin, cout,
+                                             ptr(bias), stride, 1 if same_pad else 0, store,
+                                             stream_ptr(), ctypes.byref(self.handle)),
+                  "qnn_prepack_weights")
+        else:
+            check(load().qnn_prepack_weights_dilated(wkind, wbits, float(H), ptr(kernel), kh, kw, cin, cout,
+                                                     ptr(bias), stride, 1 if same_pad else 0, self.dilation[0],
+                                                     self.dilation[1], store, stream_ptr(), ctypes.byref(self.handle)),
+                  "qnn_prepack_weights_dilated")
         self.device = kernel.device
 
     def check(self):
@@ -382,22 +397,25 @@ class Weights:
             pass
 
 
-def out_hw(size, k, stride, same_pad):
-    """Output size of one axis, the rule of csrc/qnn_conv_geom.h: 'valid' with a window larger than the image is 0."""
+def out_hw(size, k, stride, same_pad, dilation=1):
+    """Output size of one axis, the rule of csrc/qnn_conv_geom.h on the effective window dilation * (k - 1) + 1: 'valid'
+    with a window larger than the image is 0."""
     if same_pad:
         return -(-size // stride)
-    return (size - k) // stride + 1 if size >= k else 0
+    ke = dilation * (k - 1) + 1
+    return (size - ke) // stride + 1 if size >= ke else 0
 
 
 def _stored_hw(what, w, H, W, pool):
     """(Hp, Wp) of a conv call's stored output; an empty one (before or after pooling) is refused here, before any
     library call, as conv_describe refuses it ("empty output")."""
     kh, kw = w.shape[0], w.shape[1]
-    Ho, Wo = out_hw(H, kh, w.stride, w.same_pad), out_hw(W, kw, w.stride, w.same_pad)
+    dh, dw = getattr(w, "dilation", (1, 1))
+    Ho, Wo = out_hw(H, kh, w.stride, w.same_pad, dh), out_hw(W, kw, w.stride, w.same_pad, dw)
     if Ho // pool <= 0 or Wo // pool <= 0:
-        raise QnnError("%s: empty output: %dx%d input, %dx%d window, stride %d, %s padding gives %dx%d%s"
-                       % (what, H, W, kh, kw, w.stride, "same" if w.same_pad else "valid", Ho, Wo,
-                          ", pooled by %d" % pool if pool != 1 else ""))
+        raise QnnError("%s: empty output: %dx%d input, %dx%d window%s, stride %d, %s padding gives %dx%d%s"
+                       % (what, H, W, kh, kw, " dilated %dx%d" % (dh, dw) if (dh, dw) != (1, 1) else "", w.stride,
+                          "same" if w.same_pad else "valid", Ho, Wo, ", pooled by %d" % pool if pool != 1 else ""))
     return Ho // pool, Wo // pool
 
 
@@ -439,6 +457,8 @@ class Fold:
         self.rc = rc
         if rc != QNN_OK:
             self.handle = ctypes.c_void_p(None)
+            if rc == QNN_EUNSUPPORTED and w.dilation != (1, 1):       # not a shape the library may fold one day: a refusal
+                raise QnnUnsupported("qnn_fold_prepare: " + load().qnn_last_error().decode(errors="replace"))
             if rc != QNN_EUNSUPPORTED:
                 check(rc, "qnn_fold_prepare")
             return
@@ -529,6 +549,8 @@ def conv2d_dense(wc, wd, x, x_store, x_bits, N, H, W, c_inv, c_shift, c_fn, c_ac
     rc = load().qnn_conv2d_dense_forward(wc.handle, wd.handle, ptr(x), x_store, x_bits, N, H, W, ctypes.byref(ec),
                                          ctypes.byref(ed), ptr(y), stream_ptr())
     if rc == QNN_EUNSUPPORTED:
+        if wc.dilation != (1, 1):                 # refused for its dilation, not for a shape: say so
+            raise QnnUnsupported("qnn_conv2d_dense_forward: " + load().qnn_last_error().decode(errors="replace"))
         return None
     check(rc, "qnn_conv2d_dense_forward")
     return y

@@ -6,6 +6,7 @@
 #include <string>
 
 #include "qnn_abi.h"
+#include "qnn_abi_dilation.h"
 
 #define QNN_WAVE 64
 
@@ -42,6 +43,7 @@ struct qnn_weights {
     float H;
     int kh, kw, cin, cout;
     int stride, same_pad;
+    int dil_h, dil_w; // dilation_rate (qnn_prepack_weights_dilated); 1, 1 from qnn_prepack_weights
     int store;        // QNN_STORE_F32 (float path only) | BIN | I4 | I8
     int cw;           // packed words per tap (ceil(cin / per_word))
     int kwords;       // kh*kw*cw
@@ -103,6 +105,7 @@ struct ConvGeom {
     int N, H, W, Ho, Wo;       // Ho/Wo: conv output (before pooling)
     int cin, cout, kh, kw, stride;
     int pt, pl;                // SAME padding before (top/left)
+    int dil_h, dil_w;          // rows / columns between neighbouring taps (1 = an ordinary window)
     int cw, kwords;
     int pool;                  // 1 or 2
     int Hp, Wp;                // stored output size (Ho/pool, Wo/pool)
@@ -162,6 +165,8 @@ struct ConvCall {
 int qnn_route_first_f32(const ConvCall& c, char* name, size_t name_len);
 int qnn_route_strip(const ConvCall& c, char* name, size_t name_len);
 int qnn_route_gemm(const ConvCall& c, char* name, size_t name_len);
+// the one route for dilated calls besides k_conv_generic (qnn_mfma_strip_dil.hip)
+int qnn_route_strip_dil(const ConvCall& c, char* name, size_t name_len);
 
 #ifdef __HIPCC__
 #define QNN_HD __host__ __device__

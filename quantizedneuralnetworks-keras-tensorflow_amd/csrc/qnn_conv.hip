@@ -165,7 +165,9 @@ __global__ __launch_bounds__(kBlock) void k_dequant_hwio(const float* __restrict
 // ---------------------------------------------------------------------------
 // generic kernel
 // ---------------------------------------------------------------------------
-// conv result (before bias) of output channel c at conv pixel (n, oy, ox)
+// conv result (before bias) of output channel c at conv pixel (n, oy, ox).  Taps are g.dil_h rows / g.dil_w columns
+// apart; a tap outside the image is skipped, for every store (BIN included: no correction table is read here), so
+// the zero padding of a dilated window needs nothing more.
 __device__ float conv_point(const ConvGeom& g, int x_store, const void* __restrict__ x,
                             const uint32_t* __restrict__ wp, const float* __restrict__ wq,
                             float scale, int n, int oy, int ox, int c) {
@@ -173,10 +175,10 @@ __device__ float conv_point(const ConvGeom& g, int x_store, const void* __restri
         const float* xf = (const float*)x;
         float acc = 0.0f;
         for (int dy = 0; dy < g.kh; ++dy) {
-            const int iy = oy * g.stride + dy - g.pt;
+            const int iy = oy * g.stride + dy * g.dil_h - g.pt;
             if ((unsigned)iy >= (unsigned)g.H) continue;
             for (int dx = 0; dx < g.kw; ++dx) {
-                const int ix = ox * g.stride + dx - g.pl;
+                const int ix = ox * g.stride + dx * g.dil_w - g.pl;
                 if ((unsigned)ix >= (unsigned)g.W) continue;
                 const float* a = xf + (((size_t)n * g.H + iy) * g.W + ix) * g.cin;
                 const float* w = wq + ((size_t)c * g.kh * g.kw + dy * g.kw + dx) * g.cin;
@@ -191,10 +193,10 @@ __device__ float conv_point(const ConvGeom& g, int x_store, const void* __restri
         const float wscale = scale * (1.0f / 255.0f);            // 2^wshift, exact
         int acc = 0;
         for (int dy = 0; dy < g.kh; ++dy) {
-            const int iy = oy * g.stride + dy - g.pt;
+            const int iy = oy * g.stride + dy * g.dil_h - g.pt;
             if ((unsigned)iy >= (unsigned)g.H) continue;
             for (int dx = 0; dx < g.kw; ++dx) {
-                const int ix = ox * g.stride + dx - g.pl;
+                const int ix = ox * g.stride + dx * g.dil_w - g.pl;
                 if ((unsigned)ix >= (unsigned)g.W) continue;
                 const uint8_t* a = xb + (((size_t)n * g.H + iy) * g.W + ix) * g.cin;
                 const float* w = wq + ((size_t)c * g.kh * g.kw + dy * g.kw + dx) * g.cin;
@@ -206,10 +208,10 @@ __device__ float conv_point(const ConvGeom& g, int x_store, const void* __restri
     const uint32_t* xa = (const uint32_t*)x;
     int acc = 0;
     for (int dy = 0; dy < g.kh; ++dy) {
-        const int iy = oy * g.stride + dy - g.pt;
+        const int iy = oy * g.stride + dy * g.dil_h - g.pt;
         if ((unsigned)iy >= (unsigned)g.H) continue;
         for (int dx = 0; dx < g.kw; ++dx) {
-            const int ix = ox * g.stride + dx - g.pl;
+            const int ix = ox * g.stride + dx * g.dil_w - g.pl;
             if ((unsigned)ix >= (unsigned)g.W) continue;
             const uint32_t* a = xa + (((size_t)n * g.H + iy) * g.W + ix) * g.cw;
             const uint32_t* w = wp + ((size_t)c * g.kh * g.kw + dy * g.kw + dx) * g.cw;
@@ -1149,6 +1151,11 @@ int check_epilogue(const qnn_weights* w, const qnn_epilogue_t* epi, int xshift, 
     e->first_mode = 0;
     e->proj_x = nullptr; e->proj_w = nullptr; e->proj_bias = nullptr;
     e->proj_scale = 1.0f; e->proj_cin = 0; e->proj_H = 0; e->proj_W = 0;
+    const bool dilated = w->dil_h != 1 || w->dil_w != 1;
+    QNN_REQUIRE(!(dilated && epi->proj), QNN_EUNSUPPORTED,
+                "epilogue: no in-launch projection shortcut behind a dilated layer (dilation %d x %d)", w->dil_h, w->dil_w);
+    QNN_REQUIRE(!(dilated && epi->fold), QNN_EUNSUPPORTED,
+                "epilogue: no folded epilogue for a dilated layer (dilation %d x %d)", w->dil_h, w->dil_w);
     if (epi->proj) {
         // the shortcut as a 1x1 strides-2 convolution of the block input, computed inside the launch (qnn_projection_t)
         const qnn_projection_t* pj = epi->proj;
@@ -1273,8 +1280,11 @@ int conv_describe(ConvCall* c, const qnn_weights* w, const void* x, int x_store,
     ConvGeom& g = c->g;
     g.N = N; g.H = H; g.W = W;
     g.cin = w->cin; g.cout = w->cout; g.kh = w->kh; g.kw = w->kw; g.stride = w->stride;
-    qnn_same_pad(H, w->kh, w->stride, w->same_pad, &g.Ho, &g.pt);
-    qnn_same_pad(W, w->kw, w->stride, w->same_pad, &g.Wo, &g.pl);
+    g.dil_h = w->dil_h; g.dil_w = w->dil_w;
+    QNN_REQUIRE(!dense || (g.dil_h == 1 && g.dil_w == 1), QNN_EUNSUPPORTED,
+                "dense_forward: a dense layer has no dilation (handle prepacked with %d x %d)", g.dil_h, g.dil_w);
+    qnn_same_pad_dilated(H, w->kh, w->stride, g.dil_h, w->same_pad, &g.Ho, &g.pt);
+    qnn_same_pad_dilated(W, w->kw, w->stride, g.dil_w, w->same_pad, &g.Wo, &g.pl);
     QNN_REQUIRE(g.Ho > 0 && g.Wo > 0, QNN_EINVAL, "conv_forward: empty output");
     g.cw = w->cw; g.kwords = w->kwords;
     g.pool = epi->pool;
@@ -1379,6 +1389,7 @@ enum : unsigned {
     CAP_PROJ = 8,       // projection shortcut computed in the launch (qnn_epilogue_t.proj)
     CAP_TRICK = 16,     // the faithful identity trick (qnn_epilogue_t.trick_s)
     CAP_LEAKY = 32,     // QNN_FN_LEAKY_RELU
+    CAP_DIL = 64,       // a dilated window (ConvGeom.dil_h / dil_w != 1): every kernel written for adjacent taps lacks it
 };
 
 struct Route {
@@ -1399,14 +1410,17 @@ const Route kRoutes[] = {
     {route_xnor_pk, CAP_CONV, false},
     {route_ps, CAP_CONV | CAP_DENSE | CAP_RES | CAP_TRICK, false},
     {route_f32act, CAP_CONV | CAP_RES | CAP_LEAKY, true},
-    {route_generic, CAP_CONV | CAP_DENSE | CAP_RES | CAP_TRICK | CAP_LEAKY, false},
+    {qnn_route_strip_dil, CAP_CONV | CAP_RES | CAP_DIL, true},
+    {route_generic, CAP_CONV | CAP_DENSE | CAP_RES | CAP_TRICK | CAP_LEAKY | CAP_DIL, false},
 };
 
-// the one feature check: may route (caps, mfma) take call c?
+// the one feature check: may route (caps, mfma) take call c?  (CAP_DIL is the guard of the dilated calls: the routes
+// test pt / pl unevenly, so none of them is asked; only the two routes that list it ever see such a call)
 bool route_takes(unsigned caps, bool mfma, const ConvCall& c) {
     const EpiArgs& e = c.e;
     const unsigned uses = (c.dense ? CAP_DENSE : CAP_CONV) | (e.res ? CAP_RES : 0u) | (e.proj_x ? CAP_PROJ : 0u) |
-                          (e.trick_s != 0.0f ? CAP_TRICK : 0u) | (e.fn == QNN_FN_LEAKY_RELU ? CAP_LEAKY : 0u);
+                          (e.trick_s != 0.0f ? CAP_TRICK : 0u) | (e.fn == QNN_FN_LEAKY_RELU ? CAP_LEAKY : 0u) |
+                          (c.g.dil_h != 1 || c.g.dil_w != 1 ? CAP_DIL : 0u);
     // a projection call ignores the preference: no VALU kernel computes the shortcut
     return (uses & ~caps) == 0 && !(mfma && !e.proj_x && qnn_conv_impl_pref() == 1);
 }
@@ -1442,7 +1456,21 @@ int conv_forward(const qnn_weights* w, const void* x, int x_store, int x_bits, i
 extern "C" int qnn_prepack_weights(int wkind, int wbits, float H, const float* kernel, int kh,
                                    int kw, int cin, int cout, const float* bias, int stride,
                                    int same_pad, int store, void* stream, qnn_weights_t** out) {
+    return qnn_prepack_weights_dilated(wkind, wbits, H, kernel, kh, kw, cin, cout, bias, stride, same_pad, 1, 1, store,
+                                       stream, out);
+}
+
+extern "C" int qnn_prepack_weights_dilated(int wkind, int wbits, float H, const float* kernel, int kh,
+                                           int kw, int cin, int cout, const float* bias, int stride,
+                                           int same_pad, int dil_h, int dil_w, int store, void* stream,
+                                           qnn_weights_t** out) {
     QNN_REQUIRE(kernel && out, QNN_EINVAL, "qnn_prepack_weights: null pointer");
+    QNN_REQUIRE(dil_h >= 1 && dil_w >= 1, QNN_EINVAL, "qnn_prepack_weights: dilation %d x %d (must be >= 1)", dil_h, dil_w);
+    QNN_REQUIRE(dil_h <= QNN_MAX_DILATION && dil_w <= QNN_MAX_DILATION, QNN_EUNSUPPORTED,
+                "qnn_prepack_weights: dilation %d x %d above QNN_MAX_DILATION = %d", dil_h, dil_w, QNN_MAX_DILATION);
+    QNN_REQUIRE((dil_h == 1 && dil_w == 1) || stride == 1, QNN_EUNSUPPORTED,
+                "qnn_prepack_weights: dilation %d x %d together with stride %d is not supported (dilation != 1 needs "
+                "stride 1)", dil_h, dil_w, stride);
     QNN_REQUIRE(kh > 0 && kw > 0 && cin > 0 && cout > 0, QNN_EINVAL,
                 "qnn_prepack_weights: kernel shape (%d,%d,%d,%d)", kh, kw, cin, cout);
     QNN_REQUIRE(kh <= 3 && kw <= 3, QNN_EUNSUPPORTED,
@@ -1488,6 +1516,7 @@ extern "C" int qnn_prepack_weights(int wkind, int wbits, float H, const float* k
     w->wkind = wkind; w->wbits = wbits; w->H = H;
     w->kh = kh; w->kw = kw; w->cin = cin; w->cout = cout;
     w->stride = stride; w->same_pad = same_pad ? 1 : 0;
+    w->dil_h = dil_h; w->dil_w = dil_w;
     w->store = store; w->wshift = wshift;
     w->cw = store == QNN_STORE_F32 ? cin : qnn_words(store, cin);
     w->kwords = kh * kw * w->cw;
@@ -1538,7 +1567,7 @@ extern "C" int qnn_prepack_weights(int wkind, int wbits, float H, const float* k
         else
             hipLaunchKernelGGL(k_prepack_codes<QNN_STORE_I8>, dim3(grid), dim3(kBlock), 0, s, w->d_wq,
                                w->d_packed, taps, cin, cout, w->cw, m);
-        if (store == QNN_STORE_BIN && w->same_pad && (kh > 1 || kw > 1)) {
+        if (store == QNN_STORE_BIN && w->same_pad && (kh > 1 || kw > 1) && dil_h == 1 && dil_w == 1) {   // (a dilated border is deeper than the table's classes: only k_conv_generic, which skips the taps, runs such a layer)
             PREPACK_HIP(hipMalloc(&w->d_corr, (size_t)64 * cout * sizeof(int32_t)));
             grid = (64 * cout + kBlock - 1) / kBlock;
             hipLaunchKernelGGL(k_corr_table, dim3(grid), dim3(kBlock), 0, s, w->d_wq, w->d_corr, kh,
@@ -1645,6 +1674,8 @@ extern "C" int qnn_conv2d_dense_forward(const qnn_weights_t* wc, const qnn_weigh
     QNN_REQUIRE(wc && wd && x && y && epi_conv && epi_dense, QNN_EINVAL, "qnn_conv2d_dense_forward: null pointer");
     QNN_REQUIRE(N >= 0 && H > 0 && W > 0, QNN_EINVAL, "qnn_conv2d_dense_forward: N=%d H=%d W=%d", N, H, W);
     QNN_REQUIRE(wd->kh == 1 && wd->kw == 1, QNN_EINVAL, "qnn_conv2d_dense_forward: the second handle is not a dense layer");
+    QNN_REQUIRE(wc->dil_h == 1 && wc->dil_w == 1 && wd->dil_h == 1 && wd->dil_w == 1, QNN_EUNSUPPORTED,
+                "qnn_conv2d_dense_forward: no fused kernel for a dilated layer (dilation %d x %d)", wc->dil_h, wc->dil_w);
     if (x_store != QNN_STORE_I4 || wc->store != QNN_STORE_I4 || wd->store != QNN_STORE_I4 || !wc->d_mfma || !wd->d_head ||
         qnn_conv_impl_pref() == 1 || epi_conv->pool != 2 || epi_conv->out_store != QNN_STORE_I4 || epi_conv->res ||
         epi_conv->trick_s != 0.0f || epi_dense->out_store != QNN_STORE_F32 || epi_dense->fn != QNN_FN_NONE ||

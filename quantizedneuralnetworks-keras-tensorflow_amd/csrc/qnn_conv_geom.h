@@ -18,3 +18,9 @@ static inline void qnn_same_pad(int in, int k, int s, int same, int* out, int* b
         *before = 0;
     }
 }
+
+// The same rule for a dilated window: taps d cells apart cover the effective window ke = d * (k - 1) + 1, and SAME / VALID
+// are TensorFlow's rule on ke (tf.nn.conv2d with dilations).  d = 1 is qnn_same_pad itself.  VALID is 0 for in < ke.
+static inline void qnn_same_pad_dilated(int in, int k, int s, int d, int same, int* out, int* before) {
+    qnn_same_pad(in, d * (k - 1) + 1, s, same, out, before);
+}

@@ -766,7 +766,10 @@ int qnn_mfma_prepare_weights(qnn_weights* w, hipStream_t s) {
     // are packed
     const bool small8 = w->store == QNN_STORE_I8 && (w->cin == 16 || w->cin == 32) && (w->cout % 16) == 0 &&
                         w->kh == 3 && w->kw == 3;
-    if (!small && !small8 && !proj && (w->cin % 64 != 0 || w->cout % 64 != 0)) return QNN_OK;
+    // a dilated 3x3 layer of 64 input channels: k_conv_strip_dil (qnn_mfma_strip_dil.hip) takes every multiple of 32 filters
+    const bool dil64 = w->store == QNN_STORE_I4 && (w->dil_h != 1 || w->dil_w != 1) && w->cin == 64 && (w->cout % 32) == 0 &&
+                       w->kh == 3 && w->kw == 3;
+    if (!small && !small8 && !proj && !dil64 && (w->cin % 64 != 0 || w->cout % 64 != 0)) return QNN_OK;
     if (w->store == QNN_STORE_I8) {
         w->d_mfma = (uint8_t*)w->d_packed;      // int8 codes, natural channel order
         return QNN_OK;

@@ -224,6 +224,8 @@ extern "C" int qnn_avgpool_dense_softmax_forward(const qnn_weights_t* wd, const 
     const int Ho = H / size, Wo = W / size;
     QNN_REQUIRE(wd->kh == 1 && wd->kw == 1, QNN_EINVAL,
                 "qnn_avgpool_dense_softmax_forward: weights were prepacked as a %dx%d conv", wd->kh, wd->kw);
+    QNN_REQUIRE(wd->dil_h == 1 && wd->dil_w == 1, QNN_EUNSUPPORTED,
+                "qnn_avgpool_dense_softmax_forward: a dense layer has no dilation (handle prepacked with %d x %d)", wd->dil_h, wd->dil_w);
     QNN_REQUIRE((long)Ho * Wo * C == (long)wd->cin, QNN_EINVAL,
                 "qnn_avgpool_dense_softmax_forward: the dense layer takes %d inputs, the pooled tensor has %d x %d x %d",
                 wd->cin, Ho, Wo, C);

@@ -89,6 +89,12 @@ def _join_store(act_bits, wstore):
     return max(a, w, _abi.STORE_I4)
 
 
+def _dilation(op):
+    """dilation_rate of a conv op as a pair ((1, 1) where the spec says nothing: dense ops, ordinary windows)."""
+    d = op.get("dilation_rate", (1, 1))
+    return (int(d), int(d)) if np.isscalar(d) else (int(d[0]), int(d[1]))
+
+
 def _matrix_pipe_1bit(op):
     """True if a 1-bit x 1-bit conv should take the int8 matrix pipe instead of XNOR+popcount.
 
@@ -101,7 +107,7 @@ def _matrix_pipe_1bit(op):
     if _abi.conv_impl() == _abi.IMPL_VALU or op is None or op["op"] != "conv" or op["kind"] != "binary":
         return False
     kh, kw, cin, cout = op["kernel"].shape
-    return kh == 3 and kw == 3 and cin in (64, 128) and cout == 64
+    return kh == 3 and kw == 3 and cin in (64, 128) and cout == 64 and _dilation(op) == (1, 1)   # (that kernel has adjacent taps)
 
 
 def _prepack(op, store, device, stride=1, same_pad=True):
@@ -109,7 +115,7 @@ def _prepack(op, store, device, stride=1, same_pad=True):
     bias = op.get("bias")
     bias = torch.as_tensor(np.ascontiguousarray(bias, dtype=F32)).to(device) if bias is not None else None
     return _abi.Weights(_wkind(op), int(op.get("nb", 1)), float(op.get("H", 1.0)), kernel, bias,
-                        stride, same_pad, store)
+                        stride, same_pad, store, dilation=_dilation(op))
 
 
 def _images(x, what):
@@ -397,6 +403,7 @@ class FusedModel(_DomainFlag):
                     kh_, kw_, cin_, _ = op["kernel"].shape
                     if out_store == _abi.STORE_BIN and (kh_, kw_, cout) == (3, 3, 64) and cin_ in (64, 128) and \
                             g["pool"] == 2 and g["stride"] == 1 and g["same"] and x_store == _abi.STORE_I4 and \
+                            _dilation(op) == (1, 1) and \
                             nxt["kernel"].shape[0] == 1024 and nxt["kernel"].shape[1] <= 16 and \
                             _abi.conv_impl() != _abi.IMPL_VALU:
                         # +-1 codes as int4 in front of the classifier: lets the last conv group and the dense layer
@@ -467,6 +474,7 @@ class FusedModel(_DomainFlag):
         return (c["kind"] == "conv" and d["kind"] == "dense" and c["pool"] == 2 and c["out_store"] == _abi.STORE_I4
                 and c["x_store"] == _abi.STORE_I4 and d["x_store"] == _abi.STORE_I4 and d["out_store"] == _abi.STORE_F32
                 and d["fn"] == _abi.FN_NONE and not d["softmax"] and not c["softmax"] and c["trick"] is None
+                and c["w"].dilation == (1, 1)
                 and _abi.conv_impl() != _abi.IMPL_VALU)
 
     def run_head(self, cur, N, H, W, out=None):
@@ -508,7 +516,7 @@ class FusedModel(_DomainFlag):
           int4 -> int4 layers with quantized_tanh(4)          -> the matrix-pipe forms (modes 1 / 2)."""
         st = self.steps[si]
         if not self.fold or st["kind"] != "conv" or st["fn"] != _abi.FN_QUANTIZED_TANH or st["act_bits"] != 4 or \
-                st["out_store"] != _abi.STORE_I4 or st["trick"] is not None:
+                st["out_store"] != _abi.STORE_I4 or st["trick"] is not None or st["w"].dilation != (1, 1):
             return None
         if si == 0 and x_store in (_abi.STORE_U8, _abi.STORE_F32_IMAGE):
             key, args = "fold_img", (_abi.STORE_U8, 0)
@@ -855,6 +863,7 @@ class ResidualFusedModel(_DomainFlag):
         ok = (po.get("kind") == "quantized" and po.get("nb") == 4 and mo.get("kind") == "quantized" and mo.get("nb") == 4
               and tuple(pk[:2]) == (1, 1) and tuple(po.get("strides", (1, 1))) == (2, 2)
               and tuple(mk[:2]) == (3, 3) and tuple(mo.get("strides", (1, 1))) == (1, 1) and mo.get("padding", "same") == "same"
+              and _dilation(po) == (1, 1) and _dilation(mo) == (1, 1)
               and mk[2] == mk[3] and mk[3] in (32, 64) and pk[3] == mk[3] and 2 * pk[2] == mk[2]
               and fn == _abi.FN_QUANTIZED_TANH and bits == 4 and out_store == _abi.STORE_I4)
         return pi if ok else None
@@ -974,7 +983,7 @@ class ResidualFusedModel(_DomainFlag):
                 dflag = self._own_flag()
 
         fold = None
-        if self.fold and proj is None and xs == _abi.STORE_I4 and out_store == _abi.STORE_I4 \
+        if self.fold and proj is None and w.dilation == (1, 1) and xs == _abi.STORE_I4 and out_store == _abi.STORE_I4 \
                 and fn == _abi.FN_QUANTIZED_TANH and ab == 4 \
                 and (res is None or (isinstance(res, _Packed) and res.store == _abi.STORE_I4 and res.bits == 4)):
             fkey = (ci, bn_i, xb, None if res is None else float(post_scale))
@@ -1327,7 +1336,7 @@ class LayerModel:
             if op["op"] == "conv":
                 kh, kw_, cin, cout = op["kernel"].shape
                 kw.update(kernel_size=(kh, kw_), strides=tuple(op.get("strides", (1, 1))),
-                          padding=op.get("padding", "same"))
+                          padding=op.get("padding", "same"), dilation_rate=_dilation(op))
                 if op["kind"] == "binary":
                     layer = BinaryConv2D(cout, H=1., **kw)
                 elif op["kind"] == "quantized":

@@ -136,7 +136,7 @@ class LowBitLayer:
             stride = getattr(self, "strides", (1, 1))[0]
             same = getattr(self, "padding", "valid") == "same"
             w = _abi.Weights(self._wkind, self._wbits(), float(self.H), self.kernel, self.bias,
-                             stride, same, store)
+                             stride, same, store, dilation=getattr(self, "dilation_rate", (1, 1)))
             self._packed[store] = w
         return w
 
@@ -257,8 +257,10 @@ class LowBitConv2D(LowBitLayer):
                              + self.padding)
         if self.data_format != "channels_last":
             raise _abi.QnnError("only data_format='channels_last' (NHWC) is supported")
-        if self.dilation_rate != (1, 1):
-            raise _abi.QnnError("dilation_rate != 1 is not supported")
+        if self.dilation_rate != (1, 1) and self.strides != (1, 1):
+            # Keras Conv2D refuses the pair at construction, in these words
+            raise ValueError("`strides > 1` not supported in conjunction with `dilation_rate > 1`. Received: strides=%s "
+                             "and dilation_rate=%s" % (self.strides, self.dilation_rate))
         if self.strides[0] != self.strides[1]:
             raise _abi.QnnError("non-square strides are not supported")
 
@@ -281,8 +283,8 @@ class LowBitConv2D(LowBitLayer):
     def compute_output_shape(self, input_shape):
         n, h, w, _ = input_shape
         same = self.padding == "same"
-        return (n, _abi.out_hw(h, self.kernel_size[0], self.strides[0], same),
-                _abi.out_hw(w, self.kernel_size[1], self.strides[1], same), self.filters)
+        return (n, _abi.out_hw(h, self.kernel_size[0], self.strides[0], same, self.dilation_rate[0]),
+                _abi.out_hw(w, self.kernel_size[1], self.strides[1], same, self.dilation_rate[1]), self.filters)
 
     def call(self, inputs):
         u8 = isinstance(inputs, torch.Tensor) and inputs.dtype == torch.uint8

@@ -510,6 +510,8 @@ def spec_from_keras_npz(path, wbits=None, abits=None):
             op = {"op": "flatten"}
         else:
             raise ValueError("unsupported layer class %r" % cls)
+        if op["op"] == "conv" and tuple(c.get("dilation_rate", (1, 1))) != (1, 1):
+            op["dilation_rate"] = tuple(int(v) for v in c["dilation_rate"])     # (an ordinary window keeps the spec it had)
         if src is not None:
             op["src"] = src
         op["dst"] = name
