@@ -104,6 +104,20 @@ extern "C" {
  * implement it, every other kernel declines a call that carries it.  Added without an ABI version step: callers that
  * never pass it see no change. */
 #define QNN_FN_LEAKY_RELU      5
+/* The two other quantised activations of layers/quantized_ops.py that have a bit-exact contract.  Both produce codes on
+ * the grid k / 2^(act_bits-1) of quantized_tanh, so they are accepted wherever quantized_tanh is -- epi->fn with act_bits
+ * (act_bits <= out_store for a packed output, never QNN_STORE_BIN), qnn_dense_forward, qnn_pack_f32 and the in_fn / in_bits
+ * of qnn_conv2d_forward_f32in -- except: qnn_fold_prepare, qnn_conv2d_dense_forward and a QNN_STORE_U8 input (its
+ * single-FMA contract is written for quantized_tanh) answer QNN_EUNSUPPORTED.  k_conv_generic, the dense and pack kernels
+ * and the un-folded int4 strip kernels ("strip_i4_c<cin>") implement them; every other kernel declines such a call.
+ * With m = 2^(act_bits-1), all float32:
+ *   quantized_relu (quantized_ops.py:69-84):  u = v + 1 (one rounding), code = clamp(rint(u * m) - m, 0, m - 1).  Not
+ *     quantized_tanh clamped at 0: the addition discards low bits of v, and ties are decided on u.
+ *   quantized_leakyrelu at its default alpha = float32(0.1) (quantized_ops.py:102-123):  w = v >= 0 ? v : 0.1f * v (one
+ *     rounding), code = clamp(rint(w * m), -m, m - 1).
+ * Added without an ABI version step: callers that never pass them see no change. */
+#define QNN_FN_QUANTIZED_RELU       6
+#define QNN_FN_QUANTIZED_LEAKYRELU  7
 
 typedef struct qnn_weights qnn_weights_t;   /* opaque prepacked layer weights */
 typedef struct qnn_fold qnn_fold_t;         /* opaque: one layer's epilogue folded over its accumulator domain (below) */

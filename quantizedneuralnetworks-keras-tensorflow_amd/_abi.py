@@ -1,4 +1,4 @@
-"""ctypes binding of include/qnn_abi.h and include/qnn_abi_dilation.h (csrc/libqnn_hip.so).
+"""ctypes binding of include/qnn_abi.h, qnn_abi_dilation.h and qnn_abi_qact.h (csrc/libqnn_hip.so).
 
 The library is loaded eagerly and loudly: a missing or unloadable .so raises at
 import time of any op that needs it (there is no CPU implementation to fall back
@@ -19,6 +19,10 @@ STORE_F32_IMAGE, STORE_F32_UNIT = 17, 18      # float32 input with a declared do
 W_FLOAT, W_BINARY, W_QUANT, W_TERNARY = 0, 1, 2, 3
 FN_NONE, FN_BINARY_TANH, FN_QUANTIZED_TANH, FN_TERNARY_TANH, FN_GRID = 0, 1, 2, 3, 4
 FN_LEAKY_RELU = 5                   # Keras LeakyReLU() at alpha = float32(0.3), float32 output only
+# quantized_ops.py:69-84 / 102-123 (alpha = float32(0.1)): codes on quantized_tanh's grid, accepted wherever it is except
+# by the folds, the fused conv + classifier entry and a QNN_STORE_U8 input (qnn_abi.h)
+FN_QUANTIZED_RELU, FN_QUANTIZED_LEAKYRELU = 6, 7
+QUANT_FNS = (FN_QUANTIZED_TANH, FN_QUANTIZED_RELU, FN_QUANTIZED_LEAKYRELU)      # the activations that carry act_bits
 
 EXPORTS = [
     "qnn_version", "qnn_last_error", "qnn_last_kernel", "qnn_set_conv_impl",
@@ -34,6 +38,9 @@ EXPORTS = [
 
 # include/qnn_abi_dilation.h: the extension header of ABI 4 (qnn_abi.h and its symbol list are unchanged)
 EXPORTS_DILATION = ["qnn_prepack_weights_dilated"]
+
+# include/qnn_abi_qact.h: the quantised activations as an elementwise op, an extension header of the same kind
+EXPORTS_QACT = ["qnn_quantized_act_f32"]
 
 
 class Projection(ctypes.Structure):
@@ -102,6 +109,7 @@ def load():
     lib.qnn_set_conv_impl.argtypes = [ci]
     lib.qnn_binary_tanh_f32.argtypes = [vp, vp, sz, vp]
     lib.qnn_quantized_tanh_f32.argtypes = [vp, vp, sz, ci, vp]
+    lib.qnn_quantized_act_f32.argtypes = [vp, vp, sz, ci, ci, vp]
     lib.qnn_ternary_tanh_f32.argtypes = [vp, vp, sz, vp, vp]
     lib.qnn_ternary_abs_sum_f32.argtypes = [vp, sz, vp, vp]
     lib.qnn_ternary_apply_f32.argtypes = [vp, vp, sz, vp, vp]
@@ -133,7 +141,7 @@ def load():
     lib.qnn_conv2d_workspace_bytes.restype = sz
     lib.qnn_conv2d_forward_f32in.argtypes = [vp, vp, ci, ci, ci, ci, ci, ctypes.POINTER(Epilogue), vp,
                                              vp, sz, vp]
-    for name in EXPORTS + EXPORTS_DILATION:   # every symbol the headers declare must be exported
+    for name in EXPORTS + EXPORTS_DILATION + EXPORTS_QACT:   # every symbol the headers declare must be exported
         getattr(lib, name)
     _lib = lib
     return lib

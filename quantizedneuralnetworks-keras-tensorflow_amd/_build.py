@@ -38,7 +38,7 @@ def _sources():
 
 def _headers():
     hs = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h"))
-    return hs + [os.path.join(ROOT, "include", h) for h in ("qnn_abi.h", "qnn_abi_dilation.h")]
+    return hs + [os.path.join(ROOT, "include", h) for h in ("qnn_abi.h", "qnn_abi_dilation.h", "qnn_abi_qact.h")]
 
 
 def _digest(paths, extra=()):

@@ -7,6 +7,7 @@
 
 #include "qnn_abi.h"
 #include "qnn_abi_dilation.h"
+#include "qnn_abi_qact.h"
 
 #define QNN_WAVE 64
 
@@ -218,6 +219,29 @@ __device__ __forceinline__ float qnn_quantized_tanh(float x, float m) {
     return __fmul_rn(qnn_quant_code_f(x, m), inv_m);
 }
 
+// The quantised activations that share quantized_tanh's grid (QNN_FN_QUANTIZED_TANH / _RELU / _LEAKYRELU, qnn_abi.h), as
+// the one pair every kernel calls: the code as a float, and the value code / m.  `fn` is a constant at most call sites.
+//   quantized_relu, quantized_ops.py:69-84: clip(2 round(clip((x+1)/2, 0, 1) 2^nb) / 2^nb - 1, 0, 1 - 1/m).  Only x + 1
+//     rounds (every later step is a power-of-two scaling, an integer difference or a clip), so the code is
+//     clamp(rint((x + 1) m) - m, 0, m - 1); +-inf clamp like the reference's inner clip.
+//   quantized_leakyrelu, quantized_ops.py:102-123, alpha = float32(0.1): relu(x) - alpha relu(-x) is x for x >= 0 and
+//     -(alpha * -x) = alpha * x (round-to-nearest is sign-symmetric) for x < 0, then quantized_tanh's clip.
+QNN_HD static inline bool qnn_is_qact(int fn) {
+    return fn == QNN_FN_QUANTIZED_TANH || fn == QNN_FN_QUANTIZED_RELU || fn == QNN_FN_QUANTIZED_LEAKYRELU;
+}
+__device__ __forceinline__ float qnn_qact_code_f(int fn, float x, float m) {
+    if (fn == QNN_FN_QUANTIZED_RELU) {
+        const float r = __fsub_rn(rintf(__fmul_rn(__fadd_rn(x, 1.0f), m)), m);
+        return fminf(fmaxf(r, 0.0f), __fsub_rn(m, 1.0f));
+    }
+    if (fn == QNN_FN_QUANTIZED_LEAKYRELU) x = x >= 0.0f ? x : __fmul_rn(0.1f, x);
+    return qnn_quant_code_f(x, m);
+}
+__device__ __forceinline__ float qnn_qact(int fn, float x, float m) {
+    const float inv_m = __uint_as_float(0x7F000000u - __float_as_uint(m));
+    return __fmul_rn(qnn_qact_code_f(fn, x, m), inv_m);
+}
+
 // Keras LeakyReLU() at its default alpha = float32(0.3): one rounding, as torch.where(v >= 0, v, v * 0.3) computes it
 __device__ __forceinline__ float qnn_leaky_relu(float v) {
     return v >= 0.0f ? v : __fmul_rn(v, 0.3f);
@@ -312,6 +336,6 @@ __device__ __forceinline__ int qnn_epi_code(float v, const EpiArgs& e) {
         const int b = (int)qnn_binary_bit(v);
         return e.out_store == QNN_STORE_BIN ? b : 2 * b - 1;   // +-1 as a signed code
     }
-    return (int)qnn_quant_code_f(v, e.act_m);
+    return (int)qnn_qact_code_f(e.fn, v, e.act_m);
 }
 #endif  // __HIPCC__

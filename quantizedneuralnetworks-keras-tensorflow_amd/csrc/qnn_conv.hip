@@ -282,7 +282,7 @@ __global__ __launch_bounds__(kBlock) void k_conv_generic(ConvGeom g, EpiArgs e, 
                 v = qnn_epi_value(v, c, e);
                 v = qnn_epi_residual(v, (long)q, c, e);
                 if (e.fn == QNN_FN_BINARY_TANH) v = qnn_binary_tanh(v);
-                else if (e.fn == QNN_FN_QUANTIZED_TANH) v = qnn_quantized_tanh(v, e.act_m);
+                else if (qnn_is_qact(e.fn)) v = qnn_qact(e.fn, v, e.act_m);
                 else if (e.fn == QNN_FN_LEAKY_RELU) v = qnn_leaky_relu(v);
                 best = (s == 0) ? v : fmaxf(best, v);
             }
@@ -350,7 +350,7 @@ __global__ __launch_bounds__(64) void k_dense_f32in(EpiArgs e, int N, int cin, i
     if (lane == 0) {
         float v = qnn_epi_value(acc, c, e);
         if (e.fn == QNN_FN_BINARY_TANH) v = qnn_binary_tanh(v);
-        else if (e.fn == QNN_FN_QUANTIZED_TANH) v = qnn_quantized_tanh(v, e.act_m);
+        else if (qnn_is_qact(e.fn)) v = qnn_qact(e.fn, v, e.act_m);
         y[t] = v;
     }
 }
@@ -614,7 +614,7 @@ __global__ __launch_bounds__(kBlock) void k_dense_packed(const uint32_t* __restr
     float v = __fmul_rn((float)acc, e.scale);
     v = qnn_epi_value(v, u, e);
     if (e.fn == QNN_FN_BINARY_TANH) v = qnn_binary_tanh(v);
-    else if (e.fn == QNN_FN_QUANTIZED_TANH) v = qnn_quantized_tanh(v, e.act_m);
+    else if (qnn_is_qact(e.fn)) v = qnn_qact(e.fn, v, e.act_m);
     y[(size_t)img * units + u] = v;
 }
 
@@ -654,7 +654,7 @@ __global__ __launch_bounds__(kBlock) void k_dense_packed_split(const uint32_t* _
     float v = __fmul_rn((float)acc, e.scale);
     v = qnn_epi_value(v, u, e);
     if (e.fn == QNN_FN_BINARY_TANH) v = qnn_binary_tanh(v);
-    else if (e.fn == QNN_FN_QUANTIZED_TANH) v = qnn_quantized_tanh(v, e.act_m);
+    else if (qnn_is_qact(e.fn)) v = qnn_qact(e.fn, v, e.act_m);
     y[(size_t)img * units + u] = v;
 }
 
@@ -1122,13 +1122,20 @@ int check_epilogue(const qnn_weights* w, const qnn_epilogue_t* epi, int xshift, 
     e->fn = epi->fn;
     e->out_store = epi->out_store;
     e->act_m = 1.0f;
-    QNN_REQUIRE(epi->fn == QNN_FN_NONE || epi->fn == QNN_FN_BINARY_TANH ||
-                    epi->fn == QNN_FN_QUANTIZED_TANH || epi->fn == QNN_FN_LEAKY_RELU,
+    QNN_REQUIRE(epi->fn == QNN_FN_NONE || epi->fn == QNN_FN_BINARY_TANH || qnn_is_qact(epi->fn) ||
+                    epi->fn == QNN_FN_LEAKY_RELU,
                 QNN_EINVAL, "epilogue: fn=%d cannot be fused", epi->fn);
     QNN_REQUIRE(epi->fn != QNN_FN_LEAKY_RELU ||
                     (epi->out_store == QNN_STORE_F32 && !epi->fold && !epi->proj && x_store != QNN_STORE_U8),
                 QNN_EINVAL, "epilogue: leaky_relu needs a float32 output, no fold, no projection and no QNN_STORE_U8 input");
-    if (epi->fn == QNN_FN_QUANTIZED_TANH) {
+    // quantized_relu / quantized_leakyrelu: the U8 entry's single-FMA contract is written for quantized_tanh (the caller
+    // runs such a first layer on the exact float32 path), and no fold is ever prepared for them (qnn_fold_prepare)
+    const bool qact_new = epi->fn == QNN_FN_QUANTIZED_RELU || epi->fn == QNN_FN_QUANTIZED_LEAKYRELU;
+    QNN_REQUIRE(!(qact_new && x_store == QNN_STORE_U8), QNN_EUNSUPPORTED,
+                "epilogue: fn=%d is not defined on the QNN_STORE_U8 entry (one FMA, then quantized_tanh's clip): pass the "
+                "images as float32", epi->fn);
+    QNN_REQUIRE(!(qact_new && epi->fold), QNN_EUNSUPPORTED, "epilogue: no folded epilogue for fn=%d", epi->fn);
+    if (qnn_is_qact(epi->fn)) {
         QNN_REQUIRE(epi->act_bits >= 2 && epi->act_bits <= 24, QNN_EINVAL,
                     "epilogue: act_bits=%d", epi->act_bits);
         e->act_m = (float)(1u << (epi->act_bits - 1));
@@ -1227,8 +1234,7 @@ int check_epilogue(const qnn_weights* w, const qnn_epilogue_t* epi, int xshift, 
             break;
         case QNN_STORE_I4:
         case QNN_STORE_I8:
-            QNN_REQUIRE(epi->fn == QNN_FN_BINARY_TANH ||
-                            (epi->fn == QNN_FN_QUANTIZED_TANH && epi->act_bits <= epi->out_store),
+            QNN_REQUIRE(epi->fn == QNN_FN_BINARY_TANH || (qnn_is_qact(epi->fn) && epi->act_bits <= epi->out_store),
                         QNN_EINVAL, "epilogue: fn=%d act_bits=%d does not fit %d-bit output",
                         epi->fn, epi->act_bits, epi->out_store);
             e->ocw = qnn_words(epi->out_store, w->cout);
@@ -1390,6 +1396,7 @@ enum : unsigned {
     CAP_TRICK = 16,     // the faithful identity trick (qnn_epilogue_t.trick_s)
     CAP_LEAKY = 32,     // QNN_FN_LEAKY_RELU
     CAP_DIL = 64,       // a dilated window (ConvGeom.dil_h / dil_w != 1): every kernel written for adjacent taps lacks it
+    CAP_QACT = 128,     // QNN_FN_QUANTIZED_RELU / QNN_FN_QUANTIZED_LEAKYRELU: a kernel that only knows quantized_tanh lacks it
 };
 
 struct Route {
@@ -1400,18 +1407,18 @@ struct Route {
 
 // in order of preference; k_conv_generic last takes every call without a projection
 const Route kRoutes[] = {
-    {route_dense, CAP_DENSE, false},
+    {route_dense, CAP_DENSE | CAP_QACT, false},
     {route_pw, CAP_CONV, false},
     {route_first_u8, CAP_CONV, true},
     {route_stem, CAP_CONV, true},
     {qnn_route_first_f32, CAP_CONV, true},
-    {qnn_route_strip, CAP_CONV | CAP_RES | CAP_PROJ, true},
+    {qnn_route_strip, CAP_CONV | CAP_RES | CAP_PROJ | CAP_QACT, true},      // (its un-folded int4 strip kernels; the rest of the family declines)
     {qnn_route_gemm, CAP_CONV | CAP_RES, true},
     {route_xnor_pk, CAP_CONV, false},
     {route_ps, CAP_CONV | CAP_DENSE | CAP_RES | CAP_TRICK, false},
     {route_f32act, CAP_CONV | CAP_RES | CAP_LEAKY, true},
     {qnn_route_strip_dil, CAP_CONV | CAP_RES | CAP_DIL, true},
-    {route_generic, CAP_CONV | CAP_DENSE | CAP_RES | CAP_TRICK | CAP_LEAKY | CAP_DIL, false},
+    {route_generic, CAP_CONV | CAP_DENSE | CAP_RES | CAP_TRICK | CAP_LEAKY | CAP_DIL | CAP_QACT, false},
 };
 
 // the one feature check: may route (caps, mfma) take call c?  (CAP_DIL is the guard of the dilated calls: the routes
@@ -1420,7 +1427,8 @@ bool route_takes(unsigned caps, bool mfma, const ConvCall& c) {
     const EpiArgs& e = c.e;
     const unsigned uses = (c.dense ? CAP_DENSE : CAP_CONV) | (e.res ? CAP_RES : 0u) | (e.proj_x ? CAP_PROJ : 0u) |
                           (e.trick_s != 0.0f ? CAP_TRICK : 0u) | (e.fn == QNN_FN_LEAKY_RELU ? CAP_LEAKY : 0u) |
-                          (c.g.dil_h != 1 || c.g.dil_w != 1 ? CAP_DIL : 0u);
+                          (c.g.dil_h != 1 || c.g.dil_w != 1 ? CAP_DIL : 0u) |
+                          (e.fn == QNN_FN_QUANTIZED_RELU || e.fn == QNN_FN_QUANTIZED_LEAKYRELU ? CAP_QACT : 0u);
     // a projection call ignores the preference: no VALU kernel computes the shortcut
     return (uses & ~caps) == 0 && !(mfma && !e.proj_x && qnn_conv_impl_pref() == 1);
 }
@@ -1646,7 +1654,7 @@ extern "C" int qnn_conv2d_forward_f32in(const qnn_weights_t* w, const float* x, 
     QNN_REQUIRE(w && x && y && epi, QNN_EINVAL, "qnn_conv2d_forward_f32in: null pointer");
     QNN_REQUIRE(w->store != QNN_STORE_F32, QNN_EINVAL,
                 "qnn_conv2d_forward_f32in: weights were prepacked for float32 inputs only");
-    QNN_REQUIRE(in_fn == QNN_FN_BINARY_TANH || in_fn == QNN_FN_QUANTIZED_TANH || in_fn == QNN_FN_GRID,
+    QNN_REQUIRE(in_fn == QNN_FN_BINARY_TANH || qnn_is_qact(in_fn) || in_fn == QNN_FN_GRID,
                 QNN_EINVAL, "qnn_conv2d_forward_f32in: in_fn=%d", in_fn);
     const int x_bits = w->store == QNN_STORE_BIN ? 1 : in_bits;
     ConvCall c;
@@ -1676,6 +1684,8 @@ extern "C" int qnn_conv2d_dense_forward(const qnn_weights_t* wc, const qnn_weigh
     QNN_REQUIRE(wd->kh == 1 && wd->kw == 1, QNN_EINVAL, "qnn_conv2d_dense_forward: the second handle is not a dense layer");
     QNN_REQUIRE(wc->dil_h == 1 && wc->dil_w == 1 && wd->dil_h == 1 && wd->dil_w == 1, QNN_EUNSUPPORTED,
                 "qnn_conv2d_dense_forward: no fused kernel for a dilated layer (dilation %d x %d)", wc->dil_h, wc->dil_w);
+    QNN_REQUIRE(epi_conv->fn != QNN_FN_QUANTIZED_RELU && epi_conv->fn != QNN_FN_QUANTIZED_LEAKYRELU, QNN_EUNSUPPORTED,
+                "qnn_conv2d_dense_forward: no fused kernel for fn=%d (issue the two calls)", epi_conv->fn);
     if (x_store != QNN_STORE_I4 || wc->store != QNN_STORE_I4 || wd->store != QNN_STORE_I4 || !wc->d_mfma || !wd->d_head ||
         qnn_conv_impl_pref() == 1 || epi_conv->pool != 2 || epi_conv->out_store != QNN_STORE_I4 || epi_conv->res ||
         epi_conv->trick_s != 0.0f || epi_dense->out_store != QNN_STORE_F32 || epi_dense->fn != QNN_FN_NONE ||

@@ -1,7 +1,8 @@
 // Elementwise activation clips and pack/unpack kernels (HBM-bound streaming).
 //
 // Reference ops replaced: layers/binary_ops.py:37-51 (binary_tanh),
-// layers/quantized_ops.py:87-100 (quantized_tanh), layers/ternary_ops.py:15-54.
+// layers/quantized_ops.py:87-100 (quantized_tanh), :69-84 (quantized_relu), :102-123 (quantized_leakyrelu),
+// layers/ternary_ops.py:15-54.
 // Each reference op is ~7 separate TF elementwise kernels (7 HBM round trips);
 // here it is one pass, 16 B per lane, one access per thread.
 #include "qnn_common.h"
@@ -39,9 +40,12 @@ __device__ __forceinline__ float4 act4(float4 v, float m) {
     if constexpr (FN == QNN_FN_BINARY_TANH) {
         r.x = qnn_binary_tanh(v.x); r.y = qnn_binary_tanh(v.y);
         r.z = qnn_binary_tanh(v.z); r.w = qnn_binary_tanh(v.w);
-    } else {
+    } else if constexpr (FN == QNN_FN_QUANTIZED_TANH) {
         r.x = qnn_quantized_tanh(v.x, m); r.y = qnn_quantized_tanh(v.y, m);
         r.z = qnn_quantized_tanh(v.z, m); r.w = qnn_quantized_tanh(v.w, m);
+    } else {
+        r.x = qnn_qact(FN, v.x, m); r.y = qnn_qact(FN, v.y, m);
+        r.z = qnn_qact(FN, v.z, m); r.w = qnn_qact(FN, v.w, m);
     }
     return r;
 }
@@ -75,7 +79,7 @@ __global__ __launch_bounds__(kBlock) void k_act_f32(const float* __restrict__ x,
     const size_t t = n4 * 4 + (size_t)blockIdx.x * kBlock + threadIdx.x;
     if (t < n) {
         if constexpr (FN == QNN_FN_BINARY_TANH) y[t] = qnn_binary_tanh(x[t]);
-        else y[t] = qnn_quantized_tanh(x[t], m);
+        else y[t] = qnn_qact(FN, x[t], m);
     }
 }
 
@@ -123,7 +127,7 @@ __device__ __forceinline__ uint32_t encode_one(float v, int fn, float m) {
         float code;
         if (fn == QNN_FN_GRID) code = __fmul_rn(v, m);                 // already k/m
         else if (fn == QNN_FN_BINARY_TANH) code = qnn_binary_tanh(v);  // +-1 as a code
-        else code = qnn_quant_code_f(v, m);
+        else code = qnn_qact_code_f(fn, v, m);
         return (uint32_t)(int)code;
     }
 }
@@ -407,6 +411,23 @@ extern "C" int qnn_quantized_tanh_f32(const float* x, float* y, size_t n, int nb
     return QNN_OK;
 }
 
+// qnn_abi_qact.h
+extern "C" int qnn_quantized_act_f32(const float* x, float* y, size_t n, int fn, int nb, void* stream) {
+    QNN_REQUIRE(x && y, QNN_EINVAL, "qnn_quantized_act_f32: null pointer");
+    QNN_REQUIRE(qnn_is_qact(fn), QNN_EINVAL, "qnn_quantized_act_f32: fn=%d is not a quantised activation", fn);
+    QNN_REQUIRE(nb >= 1 && nb <= 24, QNN_EINVAL, "qnn_quantized_act_f32: nb=%d out of range", nb);
+    if (fn == QNN_FN_QUANTIZED_TANH) return qnn_quantized_tanh_f32(x, y, n, nb, stream);
+    if (n == 0) return QNN_OK;
+    const float m = (float)(1u << (nb - 1));
+    const dim3 grid(act_grid((n + 3) / 4)), block(kBlock);
+    if (fn == QNN_FN_QUANTIZED_RELU)
+        hipLaunchKernelGGL(k_act_f32<QNN_FN_QUANTIZED_RELU>, grid, block, 0, (hipStream_t)stream, x, y, n, m);
+    else
+        hipLaunchKernelGGL(k_act_f32<QNN_FN_QUANTIZED_LEAKYRELU>, grid, block, 0, (hipStream_t)stream, x, y, n, m);
+    QNN_HIP(hipGetLastError());
+    return QNN_OK;
+}
+
 extern "C" int qnn_ternary_abs_sum_f32(const float* x, size_t n, void* workspace16, void* stream) {
     QNN_REQUIRE(x && workspace16, QNN_EINVAL, "qnn_ternary_abs_sum_f32: null pointer");
     hipStream_t s = (hipStream_t)stream;
@@ -448,14 +469,14 @@ extern "C" int qnn_pack_f32(const float* x, void* y, size_t pixels, int channels
                             int store, void* stream) {
     QNN_REQUIRE(x && y, QNN_EINVAL, "qnn_pack_f32: null pointer");
     QNN_REQUIRE(channels > 0, QNN_EINVAL, "qnn_pack_f32: channels=%d", channels);
-    QNN_REQUIRE(fn == QNN_FN_BINARY_TANH || fn == QNN_FN_QUANTIZED_TANH || fn == QNN_FN_GRID,
+    QNN_REQUIRE(fn == QNN_FN_BINARY_TANH || qnn_is_qact(fn) || fn == QNN_FN_GRID,
                 QNN_EINVAL, "qnn_pack_f32: fn=%d cannot be encoded", fn);
     if (pixels == 0) return QNN_OK;
     const int cw = qnn_words(store, channels);
     const size_t words = pixels * (size_t)cw;
     float m = 1.0f;
     if (store == QNN_STORE_BIN) {
-        QNN_REQUIRE(fn != QNN_FN_QUANTIZED_TANH, QNN_EINVAL,
+        QNN_REQUIRE(!qnn_is_qact(fn), QNN_EINVAL,
                     "qnn_pack_f32: BIN storage needs binary_tanh or grid input");
     } else if (store == QNN_STORE_I4 || store == QNN_STORE_I8) {
         if (fn != QNN_FN_BINARY_TANH) {

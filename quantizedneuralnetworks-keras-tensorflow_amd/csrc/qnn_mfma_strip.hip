@@ -77,6 +77,30 @@ __device__ __forceinline__ void strip_block_map(int& xw, int& yblk) {
     }
 }
 
+// FN: the activation of the un-folded epilogue as a template parameter.  0 = quantized_tanh or binary_tanh (told apart at
+// run time, as ever: these instantiations are instruction for instruction what they were), QNN_FN_QUANTIZED_RELU,
+// QNN_FN_QUANTIZED_LEAKYRELU (qnn_common.h: qnn_qact_code_f is what k_conv_generic evaluates; here in code units, u = v * m):
+//   quantized_relu       t = u + m, ONE more packed add per channel pair: m is a power of two, so this is fadd_rn(v, 1) * m
+//                        exactly, the contract's only rounding.  Then the magic add with the offset lowered by m:
+//                        as_int(t + (1.5 * 2^23 + 8 - m)) = 0x4B400008 + rint(t) - m (the offset stays even, so ties still
+//                        go to even), and the integer clamp to [0, m - 1].
+//   quantized_leakyrelu  u = max(u, 0.1f * u): one packed multiply per pair and one v_max_f32 per value.  Equal to the
+//                        contract's select for every u that is not NaN: u >= 0 gives 0.1f * u <= u (both zeros for u = +-0),
+//                        u < 0 gives |0.1f * u| <= |u| hence 0.1f * u >= u; 0.1f * (u = v * m) = (0.1f * v) * m exactly.
+//                        tests/test_qrelu_cpu.py holds this form against the reference's vectors.
+template <int FN>
+__device__ __forceinline__ void strip_qact(v2f (&u2)[2], const v2f& m2, const v2f& alpha2) {
+    static_assert(FN == 0 || FN == QNN_FN_QUANTIZED_RELU || FN == QNN_FN_QUANTIZED_LEAKYRELU, "activation of the strip epilogue");
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        if constexpr (FN == QNN_FN_QUANTIZED_RELU) u2[h] = u2[h] + m2;
+        if constexpr (FN == QNN_FN_QUANTIZED_LEAKYRELU) {
+            const v2f s = u2[h] * alpha2;
+            u2[h] = v2f{fmaxf(u2[h][0], s[0]), fmaxf(u2[h][1], s[1])};
+        }
+    }
+}
+
 // FOLD: the epilogue as integer thresholds (qnn_fold.h; e.fold_a / e.fold_b, proven equal to the float32 chain on the
 // layer's whole accumulator domain by qnn_fold_prepare): the offset is the MFMA's initial accumulator, then per value
 // cvt + mul, per pair one v_cvt_pknorm_i16_f32 (+ two v_pk_add_i16 clamp with a shortcut), and the nibbles of a lane's
@@ -85,7 +109,7 @@ __device__ __forceinline__ void strip_block_map(int& xw, int& yblk) {
 // RES: 0 none, 1 packed int4 shortcut, 2 float32 shortcut, 3 projection shortcut computed here (qnn_projection_t: the
 // 1x1 strides-2 convolution of the block input with CIN / 2 channels, one more MFMA per tile and row on the even pixels of
 // the even input rows -- the float32 tensor RES = 2 reads is never formed); FOLD: 0 chain, 1 / 2 = fold modes (qnn_fold.h)
-template <int CIN, int NT, int RES, bool BIAS, int FOLD>
+template <int CIN, int NT, int RES, bool BIAS, int FOLD, int FN = 0>
 __global__ __launch_bounds__(256, (CIN == 16 ? QNN_STRIP16_WPS : CIN == 32 ? (RES == 2 ? 2 : QNN_STRIP32_WPS) : QNN_STRIP64_WPS)) void k_conv_strip(MfmaGeom mg, EpiArgs e,
                                                                  const uint8_t* __restrict__ x,
                                                                  const uint8_t* __restrict__ wq8,
@@ -153,6 +177,7 @@ __global__ __launch_bounds__(256, (CIN == 16 ? QNN_STRIP16_WPS : CIN == 32 ? (RE
     const v2f rcoef2 = {rcoef, rcoef};
     // folded epilogue: per-channel slope and accumulator offset (the MFMA chain starts from the offset)
     static_assert(!FOLD || RES < 2, "the float32 shortcuts are not folded");
+    static_assert(!FOLD || FN == 0, "only quantized_tanh is folded");
     static_assert(RES != 3 || (NT == 2 && CIN >= 32), "projection shortcut: 32 / 64 channel stages");
     // ---- projection shortcut (RES = 3): 1x1 filters as one more A operand per tile; K-blocks beyond CIN / 2 channels are
     // out of range = zeros, and so are the same lanes' pixel loads ----
@@ -190,9 +215,11 @@ __global__ __launch_bounds__(256, (CIN == 16 ? QNN_STRIP16_WPS : CIN == 32 ? (RE
     // for |u| < 2^22 and is monotone in u everywhere, so a signed integer med3 clamps it; the low nibble is code + 8
     constexpr float kMagic = 12582920.0f;
     constexpr int kMagicBits = 0x4B400008;
-    v2f magic2 = {kMagic, kMagic};
+    const float mgc = FN == QNN_FN_QUANTIZED_RELU ? kMagic - e.act_m : kMagic;     // (an even integer either way: act_bits >= 2)
+    v2f magic2 = {mgc, mgc};
     asm volatile("" : "+v"(magic2));                  // a register pair (v_pk_add_f32 takes no literal): keeps the add packed
-    const int code_lo = kMagicBits - (int)e.act_m, code_hi = kMagicBits + (int)e.act_m - 1;
+    const int code_lo = FN == QNN_FN_QUANTIZED_RELU ? kMagicBits : kMagicBits - (int)e.act_m, code_hi = kMagicBits + (int)e.act_m - 1;
+    const v2f act_m2 = {e.act_m, e.act_m}, alpha2 = {0.1f, 0.1f};      // strip_qact<FN>; unused for FN = 0
     const int rowb = g.W * PIXB;                      // bytes per input row
     const int orowb = g.W * e.ocw * 4;                // bytes per output row
     const int rrowb = RES == 2 ? g.W * g.cout * 4 : RES == 3 ? 2 * e.proj_W * P0B : orowb;   // (RES = 3: every other input row)
@@ -385,7 +412,8 @@ __global__ __launch_bounds__(256, (CIN == 16 ? QNN_STRIP16_WPS : CIN == 32 ? (RE
                     u2[h] = u;
                 }
                 int cb[4];
-                if (binary) {
+                strip_qact<FN>(u2, act_m2, alpha2);
+                if (FN == 0 && binary) {
                     asm volatile("; binary_tanh codes");          // keeps this a real (uniform) branch
 #pragma unroll
                     for (int i = 0; i < 4; ++i) cb[i] = u2[i >> 1][i & 1] > 0x1p-24f ? kMagicBits + 1 : kMagicBits - 1;
@@ -439,7 +467,7 @@ __global__ __launch_bounds__(256, (CIN == 16 ? QNN_STRIP16_WPS : CIN == 32 ? (RE
 // output row, so every output row simply requests its three input rows (one output row ahead) and widens them.
 // B operand of lane (pixel r, k-block): input pixel 2*(xs + r) - pl + dx.
 // ---------------------------------------------------------------------------------------------------------
-template <int CIN, int NT, bool BIAS, int FOLD>
+template <int CIN, int NT, bool BIAS, int FOLD, int FN = 0>
 __global__ __launch_bounds__(256, (CIN == 16 ? 4 : 2)) void k_conv_strip_s2(MfmaGeom mg, EpiArgs e,
                                                                              const uint8_t* __restrict__ x,
                                                                              const uint8_t* __restrict__ wq8,
@@ -479,6 +507,7 @@ __global__ __launch_bounds__(256, (CIN == 16 ? 4 : 2)) void k_conv_strip_s2(Mfma
                 bw[dy][st][nt] = __builtin_bit_cast(v4i, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, woff, 0, 0));
             }
     static_assert(NT == 2, "the stride-2 kernel stores one 32-bit word per lane");
+    static_assert(!FOLD || FN == 0, "only quantized_tanh is folded");
     const bool binary = e.fn == QNN_FN_BINARY_TANH;
     const float cfold = binary ? 1.0f : e.act_m;
     v2f nb[NT][2], ninv[NT][2], nshift[NT][2];
@@ -504,9 +533,11 @@ __global__ __launch_bounds__(256, (CIN == 16 ? 4 : 2)) void k_conv_strip_s2(Mfma
         }
     constexpr float kMagic = 12582920.0f;
     constexpr int kMagicBits = 0x4B400008;
-    v2f magic2 = {kMagic, kMagic};
+    const float mgc = FN == QNN_FN_QUANTIZED_RELU ? kMagic - e.act_m : kMagic;     // (an even integer either way: act_bits >= 2)
+    v2f magic2 = {mgc, mgc};
     asm volatile("" : "+v"(magic2));                  // a register pair (v_pk_add_f32 takes no literal): keeps the add packed
-    const int code_lo = kMagicBits - (int)e.act_m, code_hi = kMagicBits + (int)e.act_m - 1;
+    const int code_lo = FN == QNN_FN_QUANTIZED_RELU ? kMagicBits : kMagicBits - (int)e.act_m, code_hi = kMagicBits + (int)e.act_m - 1;
+    const v2f act_m2 = {e.act_m, e.act_m}, alpha2 = {0.1f, 0.1f};      // strip_qact<FN>; unused for FN = 0
     const int rowb2 = 2 * g.W * PIXB;                  // two input rows per output row
     const int orowb = g.Wo * e.ocw * 4;
     auto widen = [&](const uint2& q) -> v4i {
@@ -588,7 +619,8 @@ __global__ __launch_bounds__(256, (CIN == 16 ? 4 : 2)) void k_conv_strip_s2(Mfma
                     u2[h] = u2[h] + nshift[nt][h];
                 }
                 int cb[4];
-                if (binary) {
+                strip_qact<FN>(u2, act_m2, alpha2);
+                if (FN == 0 && binary) {
                     asm volatile("; binary_tanh codes");
 #pragma unroll
                     for (int i = 0; i < 4; ++i) cb[i] = u2[i >> 1][i & 1] > 0x1p-24f ? kMagicBits + 1 : kMagicBits - 1;
@@ -620,6 +652,11 @@ __global__ __launch_bounds__(256, (CIN == 16 ? 4 : 2)) void k_conv_strip_s2(Mfma
     }
 }
 
+// FN of the kernels for this call's activation (0: quantized_tanh / binary_tanh)
+inline int strip_fn(const EpiArgs& e) {
+    return e.fn == QNN_FN_QUANTIZED_RELU || e.fn == QNN_FN_QUANTIZED_LEAKYRELU ? e.fn : 0;
+}
+
 template <int CIN, int NT>
 int launch_strip_s2(const MfmaGeom& mg, const EpiArgs& e, const void* x, const uint8_t* w, void* y, hipStream_t s) {
     const ConvGeom& g = mg.g;
@@ -634,13 +671,17 @@ int launch_strip_s2(const MfmaGeom& mg, const EpiArgs& e, const void* x, const u
     // a fold contains the bias: "bits" form (2), float form (1), else the plain epilogue with or without a bias
     const int fold = !e.fold_a ? 0 : e.fold_c ? 2 : 1;
     const bool bias = !fold && e.bias;
-#define STRIP_S2_CASE(BIAS_, FOLD_)                                                                                       \
-    if (bias == BIAS_ && fold == FOLD_) {                                                                                 \
-        hipLaunchKernelGGL((k_conv_strip_s2<CIN, NT, BIAS_, FOLD_>), grid, block, 0, s, mg, e, (const uint8_t*)x, w, y,   \
+    const int qfn = strip_fn(e);
+    if (fold && qfn) return 1;  // (not reached: no fold is prepared for these activations)
+#define STRIP_S2_CASE(BIAS_, FOLD_, FN_)                                                                                  \
+    if (bias == BIAS_ && fold == FOLD_ && qfn == FN_) {                                                                   \
+        hipLaunchKernelGGL((k_conv_strip_s2<CIN, NT, BIAS_, FOLD_, FN_>), grid, block, 0, s, mg, e, (const uint8_t*)x, w, y, \
                            QNN_STRIP_PLAN_ARGS(p), (uint32_t)img_x, (uint32_t)img_y);                                     \
         return 0;                                                                                                         \
     }
-    STRIP_S2_CASE(false, 2) STRIP_S2_CASE(false, 1) STRIP_S2_CASE(true, 0) STRIP_S2_CASE(false, 0)
+    STRIP_S2_CASE(false, 2, 0) STRIP_S2_CASE(false, 1, 0) STRIP_S2_CASE(true, 0, 0) STRIP_S2_CASE(false, 0, 0)
+    STRIP_S2_CASE(true, 0, QNN_FN_QUANTIZED_RELU) STRIP_S2_CASE(false, 0, QNN_FN_QUANTIZED_RELU)
+    STRIP_S2_CASE(true, 0, QNN_FN_QUANTIZED_LEAKYRELU) STRIP_S2_CASE(false, 0, QNN_FN_QUANTIZED_LEAKYRELU)
 #undef STRIP_S2_CASE
     return 1;                   // not reached: (bias, fold) takes exactly the four values above
 }
@@ -664,19 +705,28 @@ int launch_strip(const MfmaGeom& mg, const EpiArgs& e, const void* x, const uint
     if (!qnn_strip_plan(&p, g.N, spr, g.H, 256 * wps / ny > 0 ? 256 * wps / ny : 1, 3, 1)) return 1;
     const dim3 grid(p.blocks, (unsigned)ny), block(256);
     const bool bias = e.bias != nullptr && !(e.fold_a != nullptr && res < 2);   // a fold contains the bias
-#define STRIP_CASE(RES_, BIAS_, FOLD_)                                                                        \
-    if (res == RES_ && bias == BIAS_ && fold == FOLD_) {                                                      \
-        hipLaunchKernelGGL((k_conv_strip<CIN, NT, RES_, BIAS_, FOLD_>), grid, block, 0, s, mg, e, (const uint8_t*)x, w, y, \
+#define STRIP_CASE_FN(RES_, BIAS_, FOLD_, FN_)                                                                \
+    if (res == RES_ && bias == BIAS_ && fold == FOLD_ && qfn == FN_) {                                        \
+        hipLaunchKernelGGL((k_conv_strip<CIN, NT, RES_, BIAS_, FOLD_, FN_>), grid, block, 0, s, mg, e, (const uint8_t*)x, w, y, \
                            QNN_STRIP_PLAN_ARGS(p), (uint32_t)img_x, (uint32_t)img_y, (uint32_t)img_r);       \
         return 0;                                                                                             \
     }
+#define STRIP_CASE(RES_, BIAS_, FOLD_) STRIP_CASE_FN(RES_, BIAS_, FOLD_, 0)
+    // the un-folded chain with each activation (a fold exists for quantized_tanh only)
+#define STRIP_CASE3(RES_, BIAS_)                                                                              \
+    STRIP_CASE_FN(RES_, BIAS_, 0, 0) STRIP_CASE_FN(RES_, BIAS_, 0, QNN_FN_QUANTIZED_RELU)                     \
+    STRIP_CASE_FN(RES_, BIAS_, 0, QNN_FN_QUANTIZED_LEAKYRELU)
+    const int qfn = strip_fn(e);
     // folded epilogue: everything behind the accumulator (bias included) is inside the fold's two constants
     const int fold = (e.fold_a == nullptr || res >= 2) ? 0 : e.fold_c ? 2 : 1;
     STRIP_CASE(0, false, 2) STRIP_CASE(1, false, 2) STRIP_CASE(0, false, 1) STRIP_CASE(1, false, 1)
-    STRIP_CASE(0, false, 0) STRIP_CASE(0, true, 0) STRIP_CASE(1, false, 0) STRIP_CASE(1, true, 0)
-    STRIP_CASE(2, false, 0) STRIP_CASE(2, true, 0)
-    if constexpr (NT == 2 && CIN >= 32) { STRIP_CASE(3, false, 0) STRIP_CASE(3, true, 0) }
+    if (fold && qfn) return 1;  // (not reached: no fold is prepared for these activations)
+    STRIP_CASE3(0, false) STRIP_CASE3(0, true) STRIP_CASE3(1, false) STRIP_CASE3(1, true)
+    STRIP_CASE3(2, false) STRIP_CASE3(2, true)
+    if constexpr (NT == 2 && CIN >= 32) { STRIP_CASE3(3, false) STRIP_CASE3(3, true) }
+#undef STRIP_CASE3
 #undef STRIP_CASE
+#undef STRIP_CASE_FN
     return 1;
 }
 

@@ -1,6 +1,8 @@
 // Route of the row-walking strip family: 3x3 layers with 16 / 32 / 64 input channels and an un-pooled packed output of
 // the input's own width (int4 -> int4: qnn_mfma_strip.hip, qnn_mfma_strip16.hip; int8 -> int8: qnn_mfma_strip_i8.hip),
 // then the small-channel tile kernel (qnn_mfma_small.hip).  Host code only: this file holds no kernel.
+// quantized_relu / quantized_leakyrelu (the route's CAP_QACT): the un-folded int4 strip kernels of qnn_mfma_strip.hip
+// implement them; the int8 strips, the LDS-staged 16-channel form and the tile kernel decline such a call.
 #include <math.h>
 #include <stdio.h>
 
@@ -8,6 +10,10 @@
 
 // The layer shapes the strip kernels of either width run; `store` = QNN_STORE_I4 or QNN_STORE_I8, of input, output and a
 // packed residual alike.
+static bool strip_qact(const EpiArgs& e) {
+    return e.fn == QNN_FN_QUANTIZED_RELU || e.fn == QNN_FN_QUANTIZED_LEAKYRELU;
+}
+
 static bool strip_shape(const ConvGeom& g, const EpiArgs& e, int store) {
     int pexp = 0;
     // the residual's post-scale (models/resnet.py:128: 0.5) folds into the activation's code scale: a power of two
@@ -40,7 +46,7 @@ static int route_strip_i8(const ConvCall& c, char* name, size_t name_len) {
     const ConvGeom& g = c.g;
     const EpiArgs& e = c.e;
     // no folded epilogue and no in-launch projection in the int8 kernels
-    if (c.w->store != QNN_STORE_I8 || (e.flags & QNN_EPI_NO_STRIP) || e.fold_a || e.proj_x) return 1;
+    if (c.w->store != QNN_STORE_I8 || (e.flags & QNN_EPI_NO_STRIP) || e.fold_a || e.proj_x || strip_qact(e)) return 1;
     // Accumulator bound: K = 9 * Cin <= 576 products of two codes in [-128, 127]: |acc| <= 576 * 128 * 128 = 9 437 184
     // < 2^24, so the kernels' int -> float32 conversion is exact (as the reference's float32 sum of the same products).
     static_assert(576L * 128 * 128 < (1L << 24), "int8 strip kernels: accumulators must convert to float32 exactly");
@@ -67,6 +73,7 @@ int qnn_route_strip(const ConvCall& c, char* name, size_t name_len) {
     // channels, instead of a residual and without a fold
     const bool proj_ok = !e.proj_x || (g.stride == 1 && (g.cin == 32 || g.cin == 64) && g.cout == g.cin && e.proj_cin * 2 == g.cin &&
                                        !e.res && !e.fold_a && (e.proj_H + 1) / 2 == g.H && (e.proj_W + 1) / 2 == g.W);
+    const bool qact = strip_qact(e);                         // never with a fold (check_epilogue)
     // Cin 64 (auto): every un-pooled layer.  Measured, 64 x 56^2 / 4096 x 16^2 pixels, round 3 (one 32-bit store and one
     // shortcut load per row): with the merge 13.9 us here against 36.4 us on the LDS-weight kernel, without it
     // 13.1 / 43.5 against 14.0 / 46.5 (round 2, two 16-bit accesses per row: 16.3 / 54.6 against 14.1 / 47.3).
@@ -77,7 +84,7 @@ int qnn_route_strip(const ConvCall& c, char* name, size_t name_len) {
         ep.proj_scale = e.proj_scale * (1.0f / 256.0f);      // the projection's operands too
         // 16 -> 16 channels with a usable fold and an even width: the LDS-staged form (qnn_mfma_strip16.hip: a sixth
         // of the load and a quarter of the store instructions)
-        if (g.cin == 16 && !(e.flags & QNN_EPI_NO_LDS16) && qnn_launch_strip16_lds(ms, ep, c.x, w->d_mfma, c.y, c.s) == 0) {
+        if (g.cin == 16 && !qact && !(e.flags & QNN_EPI_NO_LDS16) && qnn_launch_strip16_lds(ms, ep, c.x, w->d_mfma, c.y, c.s) == 0) {
             snprintf(name, name_len, "strip_i4_c16_lds");
             return 0;
         }
@@ -86,7 +93,7 @@ int qnn_route_strip(const ConvCall& c, char* name, size_t name_len) {
     }
     // small-channel 3x3 int4 layers on the tile kernel (both operands in registers).  Its own shape test: whole 16-pixel
     // tiles, any post-scale, and no in-launch projection shortcut, which exists in the strip kernel only
-    const bool small = !e.proj_x && (g.cin == 16 || g.cin == 32) && g.kh == 3 && g.kw == 3 && g.stride == 1 && g.pt == 1 &&
+    const bool small = !e.proj_x && !qact && (g.cin == 16 || g.cin == 32) && g.kh == 3 && g.kw == 3 && g.stride == 1 && g.pt == 1 &&
                        g.pl == 1 && g.pool == 1 && (g.W % 16) == 0 && e.out_store == QNN_STORE_I4 &&
                        (g.cout % (g.cin == 16 ? 16 : 32)) == 0 &&
                        (!e.res || (e.res_store == QNN_STORE_I4 && e.res_cw == e.ocw) ||

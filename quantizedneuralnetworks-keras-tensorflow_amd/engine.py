@@ -72,9 +72,26 @@ def _act_code(act):
         return None
     if act["fn"] == "binary_tanh":
         return _abi.FN_BINARY_TANH, 1
-    if act["fn"] == "quantized_tanh" and act["nb"] <= 8:
-        return _abi.FN_QUANTIZED_TANH, int(act["nb"])
+    if act["fn"] in _QUANT_ACTS and act["nb"] <= 8:
+        if act["fn"] == "quantized_leakyrelu":
+            quantized_ops.check_leaky_alpha(act.get("alpha", quantized_ops.LEAKY_ALPHA))
+        return _QUANT_ACTS[act["fn"]], int(act["nb"])
     return None
+
+
+# the quantised activations of layers/quantized_ops.py: spec name -> QNN_FN_* (all three leave codes on the grid k / 2^(nb-1))
+_QUANT_ACTS = {"quantized_tanh": _abi.FN_QUANTIZED_TANH, "quantized_relu": _abi.FN_QUANTIZED_RELU,
+               "quantized_leakyrelu": _abi.FN_QUANTIZED_LEAKYRELU}
+_NEW_QUANT_FNS = (_abi.FN_QUANTIZED_RELU, _abi.FN_QUANTIZED_LEAKYRELU)
+
+
+def _float_images(x, fn):
+    """uint8 images in front of a layer whose epilogue is quantized_relu / quantized_leakyrelu: the QNN_STORE_U8 entry's
+    single-FMA contract is written for quantized_tanh (the library answers QNN_EUNSUPPORTED), so the layer runs on the
+    exact float32 path on bytes / 255, formed as the reference forms them (utils/load_data.py:40)."""
+    if x.dtype == torch.uint8 and fn in _NEW_QUANT_FNS:
+        return x.to(torch.float32) / F32(255)
+    return x
 
 
 def _join_store(act_bits, wstore):
@@ -247,6 +264,10 @@ def _act(t, op):
         return binary_ops.binary_tanh(t)
     if fn == "quantized_tanh":
         return quantized_ops.quantized_tanh(t, op["nb"])
+    if fn == "quantized_relu":
+        return quantized_ops.quantized_relu(t, op["nb"])
+    if fn == "quantized_leakyrelu":
+        return quantized_ops.quantized_leakyrelu(t, op["nb"], op.get("alpha", quantized_ops.LEAKY_ALPHA))
     if fn == "ternary_tanh":
         return ternary_ops.ternary_tanh(t)
     if fn == "leaky_relu":
@@ -422,7 +443,7 @@ class FusedModel(_DomainFlag):
                     klm = np.float32(1.0 / np.sqrt(1.5 / (int(ci_ * kh_ * kw_) + int(co_ * kh_ * kw_))))
                 tk = _abi.faithful_trick(klm, trick)
             self.steps.append(dict(kind=g["kind"], w=w, x_store=x_store, x_bits=x_bits, inv=inv,
-                                   shift=shift, fn=fn, act_bits=bits if fn == _abi.FN_QUANTIZED_TANH else 0,
+                                   shift=shift, fn=fn, act_bits=bits if fn in _abi.QUANT_FNS else 0,
                                    pool=g["pool"], out_store=out_store, softmax=g.get("softmax", False), trick=tk))
             x_store, x_bits = out_store, bits
 
@@ -474,6 +495,7 @@ class FusedModel(_DomainFlag):
         return (c["kind"] == "conv" and d["kind"] == "dense" and c["pool"] == 2 and c["out_store"] == _abi.STORE_I4
                 and c["x_store"] == _abi.STORE_I4 and d["x_store"] == _abi.STORE_I4 and d["out_store"] == _abi.STORE_F32
                 and d["fn"] == _abi.FN_NONE and not d["softmax"] and not c["softmax"] and c["trick"] is None
+                and c["fn"] not in _NEW_QUANT_FNS
                 and c["w"].dilation == (1, 1)
                 and _abi.conv_impl() != _abi.IMPL_VALU)
 
@@ -497,6 +519,8 @@ class FusedModel(_DomainFlag):
         if st["kind"] != "conv":
             return _abi.dense(st["w"], cur, st["x_store"], st["x_bits"], N, st["inv"], st["shift"],
                               st["fn"], st["act_bits"], st["out_store"], out=out), H, W
+        if si == 0:
+            cur = _float_images(cur, st["fn"])
         u8 = si == 0 and cur.dtype == torch.uint8
         if u8 and st["trick"] is not None:
             #  never drop the faithful trick silently: the uint8 entry has no output-side trick
@@ -544,6 +568,8 @@ class FusedModel(_DomainFlag):
         x_ptr, y_ptr) enqueues one forward.  None if a step needs a torch op (softmax)."""
         if any(st["softmax"] for st in self.steps):
             return None
+        if example.dtype == torch.uint8 and self.steps[0]["fn"] in _NEW_QUANT_FNS:
+            return None                      # the bytes are divided by 255 in a torch op first (_float_images)
         N, H, W, _ = example.shape
         u8 = example.dtype == torch.uint8
         cur, bound = example, []
@@ -645,7 +671,7 @@ class GraphModel:
         """The classifier tail that starts at avgpool op `i`, fused: (its op indices, result) or None.  The clip in front
         of it is packed as its other consumers pack it on load."""
         t = self.graph.tail_from(i) if self.fuse_tail and isinstance(src, _Virtual) else None
-        if t is None or src.fn not in (_abi.FN_BINARY_TANH, _abi.FN_QUANTIZED_TANH):
+        if t is None or src.fn not in (_abi.FN_BINARY_TANH,) + _abi.QUANT_FNS:
             return None
         end = t[2] if t[3] is None else t[3]
         if end in self.graph.tail_no:
@@ -674,7 +700,7 @@ class GraphModel:
             pre = src.pre
             C = pre.shape[-1]
             w = g.weights(i, store)
-            nb_in = src.nb if src.fn == _abi.FN_QUANTIZED_TANH else 1
+            nb_in = src.nb if src.fn in _abi.QUANT_FNS else 1
             if kind == "conv" and src.fn == _abi.FN_GRID:
                 N, H, W, _ = pre.shape
                 xp = _abi.pack(pre, C, _abi.FN_GRID, 1, store)
@@ -966,7 +992,9 @@ class ResidualFusedModel(_DomainFlag):
                 rkw = dict(res=res.t, res_store=res.store, res_bits=res.bits, post_scale=post_scale)
             else:
                 rkw = dict(res=res.contiguous(), res_store=_abi.STORE_F32, res_bits=0, post_scale=post_scale)
-        ab = bits if fn == _abi.FN_QUANTIZED_TANH else 0
+        ab = bits if fn in _abi.QUANT_FNS else 0
+        if not isinstance(src, _Packed):
+            src = _float_images(src, fn)
         if isinstance(src, _Packed) and _wstore(op) is None:
             src = src.to_f32()               # stock float conv: float32 route
         N, H, W, C = src.shape
@@ -1035,7 +1063,7 @@ class ResidualFusedModel(_DomainFlag):
             pre = self._f32(memo, pre_name)          # no fusable producer: clip (+pack) the float32 tensor
             if store is None:
                 return _act(pre, op)
-            nb_in = bits if fn == _abi.FN_QUANTIZED_TANH else 1
+            nb_in = bits if fn in _abi.QUANT_FNS else 1
             return _Packed(_abi.pack(pre, pre.shape[-1], fn, nb_in, store), store, bits, pre.shape)
         if op["fn"] == "leaky_relu":
             # LeakyReLU(alpha = 0.3) inside the launch of the conv behind it, with the float32 shortcut in the epilogue
@@ -1366,7 +1394,7 @@ class LayerModel:
     @staticmethod
     def _grid(op):
         """What a layer may assume about the values activation `op` hands it (layers/_base.py, input_domain)."""
-        if op["fn"] == "quantized_tanh":
+        if op["fn"] in _QUANT_ACTS:          # all three leave values k / 2^(nb-1)
             return ("quantized", op["nb"]) if op["nb"] <= 8 else None
         return {"binary_tanh": "binary", "ternary_tanh": ("quantized", 1)}.get(op["fn"])      # grid {-1,0,1}: value = code
 

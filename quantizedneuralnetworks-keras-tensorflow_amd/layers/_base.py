@@ -75,7 +75,8 @@ class LowBitLayer:
         #   ("quantized", nb)         values are k/2**(nb-1)        -> packed int path
         #   "ternary"                 values are exactly {-1,0,+1}  -> sign/mask planes (ternary layers) or int4
         #   ("binary_tanh",)          apply binary_tanh on load (fuses the Activation layer)
-        #   ("quantized_tanh", nb)    apply quantized_tanh(nb) on load
+        #   ("quantized_tanh", nb)    apply quantized_tanh(nb) on load; likewise ("quantized_relu", nb) and
+        #                             ("quantized_leakyrelu", nb) (alpha = 0.1)
         self.input_domain = kwargs.pop("input_domain", None)
         return kwargs
 
@@ -163,7 +164,8 @@ class LowBitLayer:
             return store, 1, fn, 1
         kind, nb = dom
         nb = int(nb)
-        fn = _abi.FN_GRID if kind == "quantized" else _abi.FN_QUANTIZED_TANH
+        fn = {"quantized": _abi.FN_GRID, "quantized_tanh": _abi.FN_QUANTIZED_TANH,
+              "quantized_relu": _abi.FN_QUANTIZED_RELU, "quantized_leakyrelu": _abi.FN_QUANTIZED_LEAKYRELU}[kind]
         astore = _abi.store_for_bits(nb)
         store = max(astore, wbits_store) if wbits_store != _abi.STORE_BIN else astore
         return store, nb, fn, nb

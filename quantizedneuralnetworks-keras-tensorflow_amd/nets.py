@@ -59,24 +59,31 @@ def baseline_config(index):
     raise ValueError(index)
 
 
-def _layer_kinds(cf):
+QUANTIZED_ACTIVATIONS = ("quantized_tanh", "quantized_relu", "quantized_leakyrelu")
+
+
+def _layer_kinds(cf, quantized_activation="quantized_tanh"):
     """model_factory.py:24-61 -> (conv kind, conv nb, dense kind, dense nb, act op).
 
     Quirk kept from the reference: the Dense layer of a (full-)qnn gets
-    nb=cf.abits, not cf.wbits (model_factory.py:31)."""
+    nb=cf.abits, not cf.wbits (model_factory.py:31).
+    quantized_activation: the function the reference imports as `quantize_op` (model_factory.py:9; its default is
+    quantized_tanh): the activation of the full-qnn, qbnn and qtnn networks."""
+    if quantized_activation not in QUANTIZED_ACTIVATIONS:
+        raise ValueError("quantized_activation must be one of %s, got %r" % (QUANTIZED_ACTIVATIONS, quantized_activation))
     nt = cf.network_type
     if nt == "float":
         conv, fc, act = ("float", None), ("float", None), {"op": "act", "fn": "leaky_relu", "alpha": 0.3}
     elif nt in ("qnn", "full-qnn"):
         conv, fc = ("quantized", cf.wbits), ("quantized", cf.abits)
         act = ({"op": "act", "fn": "leaky_relu", "alpha": 0.3} if nt == "qnn"
-               else {"op": "act", "fn": "quantized_tanh", "nb": cf.abits})
+               else {"op": "act", "fn": quantized_activation, "nb": cf.abits})
     elif nt in ("bnn", "qbnn", "full-bnn"):
         conv, fc = ("binary", None), ("binary", None)
         if nt == "bnn":
             act = {"op": "act", "fn": "leaky_relu", "alpha": 0.3}
         elif nt == "qbnn":
-            act = {"op": "act", "fn": "quantized_tanh", "nb": cf.abits}
+            act = {"op": "act", "fn": quantized_activation, "nb": cf.abits}
         else:
             act = {"op": "act", "fn": "binary_tanh"}
     elif nt in ("tnn", "qtnn", "full-tnn"):      # model_factory.py:49-58
@@ -84,7 +91,7 @@ def _layer_kinds(cf):
         if nt == "tnn":
             act = {"op": "act", "fn": "leaky_relu", "alpha": 0.3}
         elif nt == "qtnn":
-            act = {"op": "act", "fn": "quantized_tanh", "nb": cf.abits}
+            act = {"op": "act", "fn": quantized_activation, "nb": cf.abits}
         else:
             act = {"op": "act", "fn": "ternary_tanh"}
     else:
@@ -138,6 +145,10 @@ def _act_second_moment(act):
         return 1.0
     if act["fn"] == "quantized_tanh":
         return 0.45                 # ~N(0,1) clipped to [-1,1)
+    if act["fn"] == "quantized_relu":
+        return 0.2                  # ~N(0,1) clipped to [0,1)
+    if act["fn"] == "quantized_leakyrelu":
+        return 0.23                 # [0,1) above zero, a tenth of [-1,0) below
     if act["fn"] == "ternary_tanh":
         return 0.6
     return 0.6
@@ -153,9 +164,9 @@ def _conv_op(gen, kind, nb, kh, cin, cout, strides, use_bias, prev_act):
     return op, var
 
 
-def vgg_spec(cf, seed=0):
-    """models/vgg.py:5-44."""
-    (ck, cnb), (fk, fnb), act = _layer_kinds(cf)
+def vgg_spec(cf, seed=0, quantized_activation="quantized_tanh"):
+    """models/vgg.py:5-44.  quantized_activation: see _layer_kinds."""
+    (ck, cnb), (fk, fnb), act = _layer_kinds(cf, quantized_activation)
     gen = _ParamGen(seed)
     spec = []
     cin, prev_act = cf.channels, None
@@ -189,9 +200,9 @@ def vgg_spec(cf, seed=0):
     return spec
 
 
-def resnet_spec(cf, seed=0):
-    """models/resnet.py:72-144 (ResNet v1, depth 6n+2, use_bias=False, 0.5*(x+y))."""
-    (ck, cnb), (fk, fnb), act = _layer_kinds(cf)
+def resnet_spec(cf, seed=0, quantized_activation="quantized_tanh"):
+    """models/resnet.py:72-144 (ResNet v1, depth 6n+2, use_bias=False, 0.5*(x+y)).  quantized_activation: see _layer_kinds."""
+    (ck, cnb), (fk, fnb), act = _layer_kinds(cf, quantized_activation)
     gen = _ParamGen(seed)
     spec = []
     uid = [0]
@@ -258,12 +269,14 @@ def resnet_spec(cf, seed=0):
     return spec
 
 
-def build_spec(cf, seed=0):
-    """model_factory.py:63-68."""
+def build_spec(cf, seed=0, quantized_activation="quantized_tanh"):
+    """model_factory.py:63-68.  quantized_activation: "quantized_tanh" (default), "quantized_relu" or
+    "quantized_leakyrelu" -- what a network was trained with after model_factory.py:9 was changed to import that
+    function as `quantize_op`."""
     if cf.architecture == "VGG":
-        return vgg_spec(cf, seed)
+        return vgg_spec(cf, seed, quantized_activation)
     if cf.architecture == "RESNET":
-        return resnet_spec(cf, seed)
+        return resnet_spec(cf, seed, quantized_activation)
     raise ValueError("Error: type " + str(cf.architecture) + " is not supported")
 
 
@@ -371,10 +384,10 @@ class Model:
         print_fn("Total params: %d   engine: %s" % (self.count_params(), type(self.engine).__name__))
 
 
-def build_model(cf, seed=0, device="cuda", first_layer="auto", lanes=None):
+def build_model(cf, seed=0, device="cuda", first_layer="auto", lanes=None, quantized_activation="quantized_tanh"):
     """model_factory.py:18-72: config -> model (synthetic weights; use spec_from_keras_npz +
-    Model(cf, spec) to run an imported checkpoint)."""
-    return Model(cf, build_spec(cf, seed), device, first_layer=first_layer, lanes=lanes)
+    Model(cf, spec) to run an imported checkpoint).  quantized_activation: see build_spec."""
+    return Model(cf, build_spec(cf, seed, quantized_activation), device, first_layer=first_layer, lanes=lanes)
 
 
 def activation_range_probe(model, x, number, limit=63.0, batch_size=256):
@@ -487,7 +500,11 @@ def spec_from_keras_npz(path, wbits=None, abits=None):
                   "var": d[name + "/moving_variance"]}
         elif cls == "Activation":
             fn = c["activation"]
-            if fn == "quantized_relu":         # local name of quantize_op, model_factory.py:19-20
+            if fn == "quantized_relu":
+                # NOT quantized_ops.quantized_relu: a checkpoint's Activation('quantized_relu') names the reference's
+                # local lambda `quantized_relu = lambda x: quantize_op(x, nb=cf.abits)` (model_factory.py:19-20), which
+                # shadows the op of that name and is quantized_tanh unless the import line 9 was changed.  A network
+                # trained with another quantize_op is rebuilt with build_spec(..., quantized_activation=...).
                 op = {"op": "act", "fn": "quantized_tanh", "nb": int(abits)}
             elif fn in ("binary_tanh", "ternary_tanh"):
                 op = {"op": "act", "fn": fn}
