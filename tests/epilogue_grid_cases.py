@@ -16,6 +16,8 @@ import zlib
 import numpy as np
 
 from oracle import qnn_oracle as O
+import conv_dilation_cases as D
+import qrelu_cases as Q
 
 F32 = np.float32
 STORE_F32, STORE_BIN, STORE_I4, STORE_I8 = 0, 1, 4, 8                        # include/qnn_abi.h
@@ -23,7 +25,9 @@ EPI_NO_STRIP, EPI_NO_STRIP64, EPI_NO_HALO = 1, 2, 4                         # qn
 STORE_NAME = {STORE_F32: "f32", STORE_BIN: "bin", STORE_I4: "i4", STORE_I8: "i8"}
 MIN_TIES, MIN_ZEROS, MIN_EDGE, MIN_DIFF = 32, 32, 8, 8
 # Values of the residual merge planted through the shortcut (see shortcut()), per activation of the case: exact zeros for
-# binary outputs, the ties nearest to zero for Q(2), Q(4) and Q(8); (target, positions)
+# binary outputs, the ties nearest to zero for Q(2), Q(4) and Q(8); (target, positions).  A third element "f32" marks a
+# target that is no dyadic number (the float32 neighbour of one): only a float32 shortcut can carry it, on positions where
+# r = T / post_scale - v is a float32 and r + v is exact.  A case may carry a table of its own as c["plant"] (qact_grid_cases.py: its two functions).
 PLANT = {("binary_tanh", 0): ((0.0, 64),), ("quantized_tanh", 2): ((0.25, 32), (-0.25, 32), (-0.75, 32)),
          ("quantized_tanh", 4): ((1 / 16, 32), (-1 / 16, 32), (3 / 16, 32), (-3 / 16, 32)),
          ("quantized_tanh", 8): ((1 / 256, 32), (-1 / 256, 32), (3 / 256, 32), (-3 / 256, 32))}
@@ -42,15 +46,17 @@ _BASES = {}
 BIAS8 = (0, 0, 1, -1, 0, 2, -2, 0, -16, 16, 0, 1, -1, 0, 0, 14)
 
 
-def base(x_store, N, H, W, cin, cout, k=3, stride=1, bias=True):
+def base(x_store, N, H, W, cin, cout, k=3, stride=1, bias=True, d=1):
     """Inputs, layer and plain convolution (bias included) of one (input store, geometry): built once and shared.
+    d: a square dilation rate; the op carries it as dilation_rate, the oracle convolves with the zero-stuffed kernel
+    (conv_dilation_cases.stuff, proven by test_conv_dilation_cpu.py).
 
     4-bit operands: activation codes rint(normal * 2) (values of about 0.25 sigma), weight codes -2 .. 2, so the conv value is
     acc / 64.  8-bit operands: activation codes 8 * rint(normal * 2), weight codes 8 * (-1 .. 1): the conv value is S / 256,
     which puts Q(8) ties at odd S and Q(4) ties at S = 16 mod 32; such small sums reach the clip edges of Q(8) only through
     the bias, hence BIAS8.  BIN: +-1 against +-1.  The bias is a multiple of 2^-4 (BIN: an even integer, as the sum of an
     even number of +-1 is even)."""
-    key = (x_store, N, H, W, cin, cout, k, stride, bias)
+    key = (x_store, N, H, W, cin, cout, k, stride, bias) + ((d,) if d != 1 else ())
     if key in _BASES:
         return _BASES[key]
     rng = np.random.default_rng(_seed("base", *key))
@@ -62,7 +68,7 @@ def base(x_store, N, H, W, cin, cout, k=3, stride=1, bias=True):
         b = (rng.integers(-1, 2, cout) * 2).astype(F32)
         wq = O.binarize(kernel)
     else:
-        xb = x_store
+        xb = x_store or 4                            # (a float32 input carries values of the 4-bit grid)
         m = 2.0 ** (xb - 1)
         if xb == 4:
             a = np.rint(rng.standard_normal((N, H, W, cin)) * 2)
@@ -79,10 +85,13 @@ def base(x_store, N, H, W, cin, cout, k=3, stride=1, bias=True):
         assert np.array_equal(O.quantized_tanh(x, xb), x)
     assert np.array_equal(wq, kernel if x_store != STORE_BIN else np.sign(kernel))        # the latent kernel is on the grid
     op.update(bias=b if bias else None, strides=(stride, stride), padding="same")
+    if d != 1:
+        assert x_store != STORE_BIN                   # (a stuffed kernel never goes through binarize)
+        op["dilation_rate"] = (d, d)
     if x_store == STORE_BIN:
         conv = O.binary_conv2d_call(x, kernel, op["bias"], strides=op["strides"])
     else:
-        conv = O.quantized_conv2d_call(x, kernel, op["bias"], nb=xb, strides=op["strides"])
+        conv = O.quantized_conv2d_call(x, D.stuff(kernel, d, d), op["bias"], nb=xb, strides=op["strides"])
     _BASES[key] = dict(key=key, x=x, x_bits=xb, op=op, conv=conv)
     return _BASES[key]
 
@@ -94,16 +103,19 @@ def dyadic_bn(cout, sign):
     """BN parameters from which bn_constants (tf.nn.batch_normalization's inv = rsqrt(var + eps) * gamma, shift = beta -
     mean * inv) forms a power-of-two inv in {1/8, 1/4, 1/2, 1} and a shift that is a multiple of 2^-4, exactly: var + eps is
     1 or 4.  sign: "pos", "neg" (every scale negative) or "mixed" (channels 1 mod 3 negative: both signs inside every 16-,
-    32- and 64-filter slice)."""
+    32- and 64-filter slice).  "wide": the mixed pattern with four times the scale, {1/2, 1, 2, 4}: pre-residual values of
+    several units, for a shortcut merge scaled by 1/4 that must still reach a point away from zero."""
     if (cout, sign) not in _BNS:
         c = np.arange(cout)
-        s = {"pos": np.ones(cout), "neg": -np.ones(cout), "mixed": np.where(c % 3 == 1, -1.0, 1.0)}[sign]
+        s = {"pos": np.ones(cout), "neg": -np.ones(cout), "mixed": np.where(c % 3 == 1, -1.0, 1.0),
+             "wide": np.where(c % 3 == 1, -4.0, 4.0)}[sign]
         bn = dict(op="bn", eps=0.25, gamma=(s * np.array([0.25, 0.5, 1.0, 0.25])[c % 4]).astype(F32),
                   var=np.array([0.75, 3.75])[(c // 4) % 2].astype(F32), mean=(((c % 3) - 1) * 0.5).astype(F32),
                   beta=(((c % 5) - 2) / 16.0).astype(F32))
         inv, shift = O.bn_constants(bn["gamma"], bn["beta"], bn["mean"], bn["var"], bn["eps"])
-        assert np.all(np.abs(np.frexp(inv)[0]) == 0.5) and np.all(np.abs(inv) >= 0.125) and np.all(np.abs(inv) <= 1)
-        assert np.array_equal(shift * 16, np.rint(shift * 16)) and np.array_equal(np.sign(inv), s)
+        assert np.all(np.abs(np.frexp(inv)[0]) == 0.5) and np.all(np.abs(inv) >= (0.5 if sign == "wide" else 0.125)) and \
+            np.all(np.abs(inv) <= (4 if sign == "wide" else 1))
+        assert np.array_equal(shift * 16, np.rint(shift * 16)) and np.array_equal(np.sign(inv), np.sign(s))
         _BNS[cout, sign] = bn
     return _BNS[cout, sign]
 
@@ -125,10 +137,12 @@ def shortcut(c):
     float32 multiples of 2^-4.  Then the special points of the case's activations are planted: for every (target T, count)
     of PLANT, on positions spread over the tensor where r = T / post_scale - v (v = pre_residual) is itself a shortcut
     value, the shortcut is that r, so that the merge (r + v) * post_scale is exactly T.  A target takes at most a third
-    of the positions still open to it, so that the later ones find some too."""
+    of the positions still open to it, so that the later ones find some too.  An "f32" target (see PLANT) is skipped by
+    a packed shortcut; a float32 one takes the positions where r is a float32 and the float32 sum r + v is T / post_scale."""
     if c["res"] is None:
         return None
-    targets = tuple(t for k in sorted({(a["fn"], a["nb"]) for a in c["acts"]}) for t in PLANT[k])
+    table = c.get("plant") or PLANT
+    targets = tuple(t for k in sorted({(a["fn"], a["nb"]) for a in c["acts"]}) for t in table[k])
     key = (c["base"], c["sign"], c["res"], c["res_bits"], c["post_scale"], targets)
     if key not in _SHORTCUTS:
         v = pre_residual(c).astype(np.float64)
@@ -141,9 +155,16 @@ def shortcut(c):
             lo, hi = -1.0, (m - 1) / m
             r = np.clip(np.rint(rng.standard_normal(v.shape) * 0.25 * m), -m, m - 1) / m
         free = np.ones(v.size, bool)
-        for T, count in targets:
+        for T, count, *exact in targets:
             want = (T / c["post_scale"] - v).reshape(-1)
-            idx = np.flatnonzero((want * m == np.rint(want * m)) & (want >= lo) & (want <= hi) & free)
+            if exact:
+                if c["res"] != STORE_F32:
+                    continue
+                w32 = want.astype(F32)
+                ok = (w32.astype(np.float64) == want) & ((w32 + v.reshape(-1).astype(F32)).astype(np.float64) == T / c["post_scale"])
+            else:
+                ok = want * m == np.rint(want * m)
+            idx = np.flatnonzero(ok & (want >= lo) & (want <= hi) & free)
             n = min(count, (idx.size + 2) // 3)
             idx = idx[np.unique(np.linspace(0, idx.size - 1, n).astype(np.int64))] if n else idx[:0]
             r.reshape(-1)[idx] = want[idx]
@@ -166,10 +187,15 @@ def _pool(c, y):
     return O.maxpool2d(y) if c["pool"] == 2 else y
 
 
+# the activations by name: the oracle's two, and the restatements of qrelu_cases.py (held to golden/ref_qrelu.npz)
+ACT = {"binary_tanh": lambda p, nb: O.binary_tanh(p), "quantized_tanh": O.quantized_tanh,
+       "quantized_relu": Q.quantized_relu, "quantized_leakyrelu": Q.quantized_leakyrelu}
+
+
 def expected(c, a, p=None):
     """The oracle's output of activation `a` of case `c`: float32 values (a packed output holds their codes)."""
     p = preactivation(c) if p is None else p
-    return _pool(c, O.binary_tanh(p) if a["fn"] == "binary_tanh" else O.quantized_tanh(p, a["nb"]))
+    return _pool(c, ACT[a["fn"]](p, a["nb"]))
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -221,7 +247,8 @@ def A(fn, nb, store, named=True):
     """One activation / output store of a case.  named: the call must run on the case's kernel (False: the store selects
     another kernel; the output is compared all the same)."""
     return dict(fn=fn, nb=nb, store=store, named=named,
-                id="%s%s" % ("b" if fn == "binary_tanh" else "q%d" % nb, STORE_NAME[store]))
+                id="%s%s" % ({"binary_tanh": "b", "quantized_tanh": "q%d", "quantized_relu": "relu%d",
+                              "quantized_leakyrelu": "leaky%d"}[fn].replace("%d", str(nb)), STORE_NAME[store]))
 
 
 QT, BT = "quantized_tanh", "binary_tanh"
@@ -236,15 +263,17 @@ ACTS_BIN = [A(BT, 0, STORE_BIN), A(BT, 0, STORE_F32, False)]
 
 
 def _case(kernel, valu, x_store, shape, cout, acts, epi="nobn", sign=None, res=None, res_bits=0, post_scale=1.0, k=3,
-          stride=1, pool=1, flags=0, bias=True, head=False):
+          stride=1, pool=1, flags=0, bias=True, head=False, d=1):
     """kernel / valu: the names qnn_last_kernel reports in auto mode and under IMPL_VALU.  epi: "nobn", "dyadic" (sign:
-    "pos" / "neg" / "mixed") or "residual" (res: STORE_I4 / STORE_I8 / STORE_F32, behind a dyadic BN when sign is set)."""
+    "pos" / "neg" / "mixed") or "residual" (res: STORE_I4 / STORE_I8 / STORE_F32, behind a dyadic BN when sign is set).
+    d: a square dilation rate (see base)."""
     N, H, W, cin = shape
     assert (epi == "nobn") == (sign is None and res is None) and (epi == "residual") == (res is not None)
-    c = dict(kernel=kernel, valu=valu, x_store=x_store, base=(x_store, N, H, W, cin, cout, k, stride, bias), acts=acts,
+    c = dict(kernel=kernel, valu=valu, x_store=x_store,
+             base=(x_store, N, H, W, cin, cout, k, stride, bias) + ((d,) if d != 1 else ()), acts=acts, d=d,
              epi=epi, sign=sign, res=res, res_bits=res_bits, post_scale=post_scale, pool=pool, flags=flags, head=head)
     tags = [kernel + ("+dense" if head else ""), "%dx%dx%dx%d" % shape + ("" if cout == cin else "-%d" % cout),
-            "pool2" if pool == 2 else None, epi if epi != "dyadic" else sign, (sign or "nobn") if res is not None else None,
+            "d%d" % d if d != 1 else None, "pool2" if pool == 2 else None, epi if epi != "dyadic" else sign, (sign or "nobn") if res is not None else None,
             None if res is None else "r%s%s" % (STORE_NAME[res], res_bits or ""), None if res is None else "x%g" % post_scale,
             None if bias else "nobias"]
     c["id"] = "-".join(t for t in tags if t)
@@ -273,6 +302,17 @@ def _table():
         name, shape = "strip_i4_c%d_s2" % C, (2, 19, 21, C)
         t.append(_case(name, _ps(4, C), I4, shape, 2 * C, ACTS_I4_MORE, stride=2))
         t.append(_case(name, _ps(4, C), I4, shape, 2 * C, ACTS_I4, "dyadic", "mixed", stride=2))
+    # ---- the dilated strip kernel (its own copy of the chain epilogue); under IMPL_VALU a dilated call runs on generic
+    for C in (16, 32, 64):
+        for d in (2, 3):
+            name, shape = "strip_i4_c%d_dil" % C, (2, 10, 20, C)
+            # (16 channels without BN: four images, as two hold 6 and 7 points on the lower clip edge of Q(2))
+            t.append(_case(name, "generic", I4, (4, 10, 20, C) if C == 16 else shape, C, ACTS_I4, d=d))
+            t.append(_case(name, "generic", I4, shape, C, ACTS_I4, "dyadic", "mixed", d=d))
+            t.append(_case(name, "generic", I4, shape, C, ACTS_I4, "dyadic", "neg", bias=False, d=d))
+            for post in (0.5, 1.0):
+                t.append(_case(name, "generic", I4, shape, C, ACTS_I4, "residual", "mixed", I4, 4, post, d=d))
+            t.append(_case(name, "generic", I4, shape, C, ACTS_I4, "residual", None, STORE_F32, 0, 0.5, d=d))
     # ---- the small-channel tile kernel
     for C in (16, 32):
         # (16 channels: four images, as two do not hold 32 exact zeros behind the dyadic BN)

@@ -69,7 +69,7 @@ def test_table_covers_the_kernels_and_classes():
     by = {}
     for c in CASES:
         by.setdefault(c["kernel"], []).append(c)
-    want = (["strip_i4_c%d" % n for n in (16, 32, 64)] + ["strip_i4_c16_s2", "strip_i4_c32_s2", "mfma_i4_small_c16",
+    want = (["strip_i4_c%d" % n for n in (16, 32, 64)] + ["strip_i4_c%d_dil" % n for n in (16, 32, 64)] + ["strip_i4_c16_s2", "strip_i4_c32_s2", "mfma_i4_small_c16",
             "mfma_i4_small_c32", "mfma_i4_areg64x64", "mfma_i4_halo64x64", "mfma_i4_wres256x64", "mfma_i4_256x64",
             "mfma_i4_256x128", "mfma_i4_256x256", "mfma_i8_256x128", "mfma_i8_256x256", "mfma_i8_areg64x64"] +
             ["strip_i8_c%d" % n for n in (16, 32, 64)] + ["xnor_pk_cw2", "generic"])

@@ -4,7 +4,8 @@ The cases (epilogue_grid_cases.py; their content is proven by test_epilogue_grid
 on the points where an epilogue can be subtly wrong and random BN constants never land: half-integers of quantized_tanh,
 the threshold of binary_tanh, the clip edges.  Each case names the kernel it is for; the call is made with the QNN_EPI_*
 flag that selects it, qnn_last_kernel is asserted, and the output is compared bit for bit with the oracle and with the same
-call under IMPL_VALU (k_conv_ps / xnor / k_conv_generic: independent kernels).  Every int4 -> int4 Q(4) call is repeated
+call under IMPL_VALU (k_conv_ps / xnor / k_conv_generic: independent kernels; a dilated case -- strip_i4_c<cin>_dil, with its own copy of
+the chain epilogue -- has k_conv_generic as its twin).  Every int4 -> int4 Q(4) call is repeated
 with the folded epilogue: whatever qnn_fold_prepare decided, the bits are the same, and every channel it did fold is swept
 over its whole accumulator domain (x 16 shortcut codes) against the oracle's chain.
 
@@ -155,11 +156,17 @@ def test_epilogue_on_the_grid(c):
         assert np.array_equal(raw, rawv), (c["id"], a["id"], kern, kv)
         # the folded epilogue of the int4 -> int4 Q(4) calls
         if c["x_store"] == _abi.STORE_I4 and (a["fn"], a["nb"], a["store"]) == (G.QT, 4, _abi.STORE_I4):
-            f = _abi.Fold.try_prepare(w, _abi.STORE_I4, 4, inv, shift, _abi.FN_QUANTIZED_TANH, 4, _abi.STORE_I4, **rkw)
+            if c["d"] != 1:     # a dilated handle: qnn_fold_prepare refuses it with a reason, whatever the epilogue
+                assert c["kernel"].endswith("_dil") and w.dilation == (c["d"], c["d"]), c["id"]
+                with pytest.raises(_abi.QnnUnsupported, match="dilated"):
+                    _abi.Fold(w, _abi.STORE_I4, 4, inv, shift, _abi.FN_QUANTIZED_TANH, 4, _abi.STORE_I4, **rkw)
+                f = None
+            else:
+                f = _abi.Fold.try_prepare(w, _abi.STORE_I4, 4, inv, shift, _abi.FN_QUANTIZED_TANH, 4, _abi.STORE_I4, **rkw)
             if f is None:       # a shortcut form qnn_fold_prepare does not take (float32, 2 bit, post_scale other than 0.5),
-                #                 or a layer without a matrix-pipe weight image
-                assert c["kernel"] == "generic" or (c["res"] is not None and
-                                                    (c["res"], c["res_bits"], c["post_scale"]) != (_abi.STORE_I4, 4, 0.5)), c["id"]
+                #                 a layer without a matrix-pipe weight image, or a dilated one (refused above)
+                assert c["kernel"] == "generic" or c["d"] != 1 or (
+                    c["res"] is not None and (c["res"], c["res_bits"], c["post_scale"]) != (_abi.STORE_I4, 4, 0.5)), c["id"]
                 ran.append("fold: not offered")
                 continue
             kf, rawf, gotf = _run(c, a, _abi.IMPL_AUTO, w, xp, inv, shift, rkw, fold=f)
