@@ -14,7 +14,8 @@ through the ``qnn_amd`` alias module at the repository root.
 from . import _abi  # noqa: F401
 from . import nets, engine, shard  # noqa: F401
 from .layers.binary_ops import binary_tanh, binarize, binary_sigmoid  # noqa: F401
-from .layers.quantized_ops import quantize, quantized_tanh, quantized_relu, quantized_leakyrelu  # noqa: F401
+from .layers.quantized_ops import (quantize, quantized_tanh, quantized_relu, quantized_leakyrelu,  # noqa: F401
+                                   quantized_maxrelu, quantized_leakymaxrelu)
 from .layers.ternary_ops import ternary_tanh, ternarize  # noqa: F401
 from .layers.binary_layers import BinaryConv2D, BinaryDense, BinaryConvolution2D  # noqa: F401
 from .layers.quantized_layers import (QuantizedConv2D, QuantizedDense,  # noqa: F401
@@ -23,6 +24,7 @@ from .layers.ternary_layers import TernaryConv2D, TernaryDense, TernaryConvoluti
 
 __all__ = [
     "binary_tanh", "binarize", "binary_sigmoid", "quantize", "quantized_tanh", "quantized_relu", "quantized_leakyrelu",
+    "quantized_maxrelu", "quantized_leakymaxrelu",
     "ternary_tanh", "ternarize", "BinaryConv2D", "BinaryDense", "BinaryConvolution2D",
     "QuantizedConv2D", "QuantizedDense", "QuantizedConvolution2D",
     "TernaryConv2D", "TernaryDense", "TernaryConvolution2D",

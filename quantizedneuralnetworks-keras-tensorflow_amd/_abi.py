@@ -1,4 +1,4 @@
-"""ctypes binding of include/qnn_abi.h, qnn_abi_dilation.h and qnn_abi_qact.h (csrc/libqnn_hip.so).
+"""ctypes binding of include/qnn_abi.h, qnn_abi_dilation.h, qnn_abi_qact.h and qnn_abi_maxact.h (csrc/libqnn_hip.so).
 
 The library is loaded eagerly and loudly: a missing or unloadable .so raises at
 import time of any op that needs it (there is no CPU implementation to fall back
@@ -23,6 +23,10 @@ FN_LEAKY_RELU = 5                   # Keras LeakyReLU() at alpha = float32(0.3),
 # by the folds, the fused conv + classifier entry and a QNN_STORE_U8 input (qnn_abi.h)
 FN_QUANTIZED_RELU, FN_QUANTIZED_LEAKYRELU = 6, 7
 QUANT_FNS = (FN_QUANTIZED_TANH, FN_QUANTIZED_RELU, FN_QUANTIZED_LEAKYRELU)      # the activations that carry act_bits
+# quantized_ops.py:125-171 (include/qnn_abi_maxact.h): scaled by the batch tensor's maximum, so NOT in QUANT_FNS -- only the
+# elementwise entry qnn_quantized_maxact_f32 takes them, every conv / dense / pack / fold entry answers QNN_EUNSUPPORTED
+FN_QUANTIZED_MAXRELU, FN_QUANTIZED_LEAKYMAXRELU = 8, 9
+MAXACT_FNS = (FN_QUANTIZED_MAXRELU, FN_QUANTIZED_LEAKYMAXRELU)
 
 EXPORTS = [
     "qnn_version", "qnn_last_error", "qnn_last_kernel", "qnn_set_conv_impl",
@@ -41,6 +45,9 @@ EXPORTS_DILATION = ["qnn_prepack_weights_dilated"]
 
 # include/qnn_abi_qact.h: the quantised activations as an elementwise op, an extension header of the same kind
 EXPORTS_QACT = ["qnn_quantized_act_f32"]
+
+# include/qnn_abi_maxact.h: quantized_maxrelu / quantized_leakymaxrelu as a reduction, an apply pass and the two in sequence
+EXPORTS_MAXACT = ["qnn_maxact_max_f32", "qnn_maxact_apply_f32", "qnn_quantized_maxact_f32"]
 
 
 class Projection(ctypes.Structure):
@@ -110,6 +117,9 @@ def load():
     lib.qnn_binary_tanh_f32.argtypes = [vp, vp, sz, vp]
     lib.qnn_quantized_tanh_f32.argtypes = [vp, vp, sz, ci, vp]
     lib.qnn_quantized_act_f32.argtypes = [vp, vp, sz, ci, ci, vp]
+    lib.qnn_maxact_max_f32.argtypes = [vp, sz, vp, vp]
+    lib.qnn_maxact_apply_f32.argtypes = [vp, vp, sz, ci, ci, vp, vp]
+    lib.qnn_quantized_maxact_f32.argtypes = [vp, vp, sz, ci, ci, vp, vp]
     lib.qnn_ternary_tanh_f32.argtypes = [vp, vp, sz, vp, vp]
     lib.qnn_ternary_abs_sum_f32.argtypes = [vp, sz, vp, vp]
     lib.qnn_ternary_apply_f32.argtypes = [vp, vp, sz, vp, vp]
@@ -141,7 +151,7 @@ def load():
     lib.qnn_conv2d_workspace_bytes.restype = sz
     lib.qnn_conv2d_forward_f32in.argtypes = [vp, vp, ci, ci, ci, ci, ci, ctypes.POINTER(Epilogue), vp,
                                              vp, sz, vp]
-    for name in EXPORTS + EXPORTS_DILATION + EXPORTS_QACT:   # every symbol the headers declare must be exported
+    for name in EXPORTS + EXPORTS_DILATION + EXPORTS_QACT + EXPORTS_MAXACT:   # every symbol the headers declare must be exported
         getattr(lib, name)
     _lib = lib
     return lib
@@ -150,6 +160,8 @@ def load():
 def check(rc, what):
     if rc != QNN_OK:
         msg = load().qnn_last_error().decode(errors="replace")
+        if rc == QNN_EUNSUPPORTED and "qnn_quantized_maxact_f32" in msg:     # a refusal with a reason (qnn_abi_maxact.h)
+            raise QnnUnsupported("%s: %s" % (what, msg))
         raise QnnError("%s failed (%d): %s" % (what, rc, msg))
 
 
@@ -465,7 +477,7 @@ class Fold:
         self.rc = rc
         if rc != QNN_OK:
             self.handle = ctypes.c_void_p(None)
-            if rc == QNN_EUNSUPPORTED and w.dilation != (1, 1):       # not a shape the library may fold one day: a refusal
+            if rc == QNN_EUNSUPPORTED and (w.dilation != (1, 1) or fn in MAXACT_FNS):   # not a shape the library may fold one day: a refusal
                 raise QnnUnsupported("qnn_fold_prepare: " + load().qnn_last_error().decode(errors="replace"))
             if rc != QNN_EUNSUPPORTED:
                 check(rc, "qnn_fold_prepare")

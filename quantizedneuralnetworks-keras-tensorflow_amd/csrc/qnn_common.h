@@ -8,6 +8,7 @@
 #include "qnn_abi.h"
 #include "qnn_abi_dilation.h"
 #include "qnn_abi_qact.h"
+#include "qnn_abi_maxact.h"
 
 #define QNN_WAVE 64
 
@@ -240,6 +241,37 @@ __device__ __forceinline__ float qnn_qact_code_f(int fn, float x, float m) {
 __device__ __forceinline__ float qnn_qact(int fn, float x, float m) {
     const float inv_m = __uint_as_float(0x7F000000u - __float_as_uint(m));
     return __fmul_rn(qnn_qact_code_f(fn, x, m), inv_m);
+}
+
+// quantized_maxrelu / quantized_leakymaxrelu (QNN_FN_QUANTIZED_MAXRELU / _LEAKYMAXRELU, qnn_abi_maxact.h): the scale is
+// P = the smallest power of two >= M, M = the maximum of the whole batch tensor, so they are NOT among qnn_is_qact's
+// per-value functions: every entry but the elementwise one refuses them (QNN_REFUSE_MAXACT).
+QNN_HD static inline bool qnn_is_maxact(int fn) {
+    return fn == QNN_FN_QUANTIZED_MAXRELU || fn == QNN_FN_QUANTIZED_LEAKYMAXRELU;
+}
+#define QNN_REFUSE_MAXACT(fn, who)                                                                                      \
+    QNN_REQUIRE(!qnn_is_maxact(fn), QNN_EUNSUPPORTED,                                                                   \
+                "%s: fn=%d (quantized_maxrelu / quantized_leakymaxrelu) scales by the maximum of the whole batch tensor " \
+                "and is no per-value function: run qnn_quantized_maxact_f32 on the float32 tensor (qnn_abi_maxact.h)",  \
+                who, (int)(fn))
+// The two scales from the bits of M, by integer exponent arithmetic: P = 2^e, e = M's exponent plus one when its mantissa
+// is not zero; s_in = m / P = 2^(nb-1-e), s_out = P / m.  False unless -64 <= e <= 64, i.e. outside 2^-65 < M <= 2^64 (zero, subnormal, inf and NaN
+// patterns included): the caller writes NaN.
+__device__ __forceinline__ bool qnn_maxact_scales(uint32_t mbits, int nb, float* s_in, float* s_out) {
+    const int e = (int)(mbits >> 23) - 127 + ((mbits & 0x7FFFFFu) != 0u ? 1 : 0);
+    if (mbits == 0u || mbits >= 0x7F800000u || e < -64 || e > 64) return false;
+    *s_in = __uint_as_float((uint32_t)(127 + (nb - 1) - e) << 23);
+    *s_out = __uint_as_float((uint32_t)(127 + e - (nb - 1)) << 23);
+    return true;
+}
+// The per-value arithmetic: clip(rint(x s_in), lo, m - 1) s_out, on L(x) = (x >= 0 ? x : 0.1f x) with lo = -m for the
+// leaky form, lo = 0 otherwise.  Both multiplications are exponent shifts; `+ 0` turns a -0 code into the +0 of the
+// reference's round_through.
+__device__ __forceinline__ float qnn_maxact(int fn, float x, float m, float s_in, float s_out) {
+    if (fn == QNN_FN_QUANTIZED_LEAKYMAXRELU) x = x >= 0.0f ? x : __fmul_rn(0.1f, x);
+    const float lo = fn == QNN_FN_QUANTIZED_LEAKYMAXRELU ? -m : 0.0f;
+    const float code = fminf(fmaxf(rintf(__fmul_rn(x, s_in)), lo), __fsub_rn(m, 1.0f));
+    return __fmul_rn(__fadd_rn(code, 0.0f), s_out);
 }
 
 // Keras LeakyReLU() at its default alpha = float32(0.3): one rounding, as torch.where(v >= 0, v, v * 0.3) computes it

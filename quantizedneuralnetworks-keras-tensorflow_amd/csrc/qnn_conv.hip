@@ -1122,6 +1122,7 @@ int check_epilogue(const qnn_weights* w, const qnn_epilogue_t* epi, int xshift, 
     e->fn = epi->fn;
     e->out_store = epi->out_store;
     e->act_m = 1.0f;
+    QNN_REFUSE_MAXACT(epi->fn, "epilogue");
     QNN_REQUIRE(epi->fn == QNN_FN_NONE || epi->fn == QNN_FN_BINARY_TANH || qnn_is_qact(epi->fn) ||
                     epi->fn == QNN_FN_LEAKY_RELU,
                 QNN_EINVAL, "epilogue: fn=%d cannot be fused", epi->fn);
@@ -1397,6 +1398,10 @@ enum : unsigned {
     CAP_LEAKY = 32,     // QNN_FN_LEAKY_RELU
     CAP_DIL = 64,       // a dilated window (ConvGeom.dil_h / dil_w != 1): every kernel written for adjacent taps lacks it
     CAP_QACT = 128,     // QNN_FN_QUANTIZED_RELU / QNN_FN_QUANTIZED_LEAKYRELU: a kernel that only knows quantized_tanh lacks it
+    CAP_MAXACT = 256,   // QNN_FN_QUANTIZED_MAXRELU / _LEAKYMAXRELU (qnn_abi_maxact.h): NO route lists it.  Defence in depth
+                        // only: check_epilogue refuses such a call first, so today nothing reaches the dispatch with it
+                        // (nor the QNN_REFUSE_MAXACT in conv_run); a later entry that forgot the check finds no kernel
+                        // instead of quantized_tanh's
 };
 
 struct Route {
@@ -1428,7 +1433,8 @@ bool route_takes(unsigned caps, bool mfma, const ConvCall& c) {
     const unsigned uses = (c.dense ? CAP_DENSE : CAP_CONV) | (e.res ? CAP_RES : 0u) | (e.proj_x ? CAP_PROJ : 0u) |
                           (e.trick_s != 0.0f ? CAP_TRICK : 0u) | (e.fn == QNN_FN_LEAKY_RELU ? CAP_LEAKY : 0u) |
                           (c.g.dil_h != 1 || c.g.dil_w != 1 ? CAP_DIL : 0u) |
-                          (e.fn == QNN_FN_QUANTIZED_RELU || e.fn == QNN_FN_QUANTIZED_LEAKYRELU ? CAP_QACT : 0u);
+                          (e.fn == QNN_FN_QUANTIZED_RELU || e.fn == QNN_FN_QUANTIZED_LEAKYRELU ? CAP_QACT : 0u) |
+                          (qnn_is_maxact(e.fn) ? CAP_MAXACT : 0u);
     // a projection call ignores the preference: no VALU kernel computes the shortcut
     return (uses & ~caps) == 0 && !(mfma && !e.proj_x && qnn_conv_impl_pref() == 1);
 }
@@ -1445,6 +1451,7 @@ int conv_run(const ConvCall& c) {
     char name[64];
     for (const Route& r : kRoutes)
         if (route_takes(r.caps, r.mfma, c) && r.launch(c, name, sizeof(name)) == 0) return conv_launched(name);
+    QNN_REFUSE_MAXACT(c.e.fn, "conv_forward");
     // only a projection call gets here (k_conv_generic takes every other one); the caller keeps two launches
     qnn_set_error("conv_forward: no kernel computes a projection shortcut for this layer (3x3 stride-1 int4, cin = cout in "
                   "{32, 64}, proj cin = cin / 2, output ceil(H/2) x ceil(W/2) of the block input)");
@@ -1654,6 +1661,7 @@ extern "C" int qnn_conv2d_forward_f32in(const qnn_weights_t* w, const float* x, 
     QNN_REQUIRE(w && x && y && epi, QNN_EINVAL, "qnn_conv2d_forward_f32in: null pointer");
     QNN_REQUIRE(w->store != QNN_STORE_F32, QNN_EINVAL,
                 "qnn_conv2d_forward_f32in: weights were prepacked for float32 inputs only");
+    QNN_REFUSE_MAXACT(in_fn, "qnn_conv2d_forward_f32in (in_fn)");
     QNN_REQUIRE(in_fn == QNN_FN_BINARY_TANH || qnn_is_qact(in_fn) || in_fn == QNN_FN_GRID,
                 QNN_EINVAL, "qnn_conv2d_forward_f32in: in_fn=%d", in_fn);
     const int x_bits = w->store == QNN_STORE_BIN ? 1 : in_bits;
@@ -1684,6 +1692,8 @@ extern "C" int qnn_conv2d_dense_forward(const qnn_weights_t* wc, const qnn_weigh
     QNN_REQUIRE(wd->kh == 1 && wd->kw == 1, QNN_EINVAL, "qnn_conv2d_dense_forward: the second handle is not a dense layer");
     QNN_REQUIRE(wc->dil_h == 1 && wc->dil_w == 1 && wd->dil_h == 1 && wd->dil_w == 1, QNN_EUNSUPPORTED,
                 "qnn_conv2d_dense_forward: no fused kernel for a dilated layer (dilation %d x %d)", wc->dil_h, wc->dil_w);
+    QNN_REFUSE_MAXACT(epi_conv->fn, "qnn_conv2d_dense_forward");
+    QNN_REFUSE_MAXACT(epi_dense->fn, "qnn_conv2d_dense_forward (dense)");
     QNN_REQUIRE(epi_conv->fn != QNN_FN_QUANTIZED_RELU && epi_conv->fn != QNN_FN_QUANTIZED_LEAKYRELU, QNN_EUNSUPPORTED,
                 "qnn_conv2d_dense_forward: no fused kernel for fn=%d (issue the two calls)", epi_conv->fn);
     if (x_store != QNN_STORE_I4 || wc->store != QNN_STORE_I4 || wd->store != QNN_STORE_I4 || !wc->d_mfma || !wd->d_head ||

@@ -414,6 +414,7 @@ extern "C" int qnn_quantized_tanh_f32(const float* x, float* y, size_t n, int nb
 // qnn_abi_qact.h
 extern "C" int qnn_quantized_act_f32(const float* x, float* y, size_t n, int fn, int nb, void* stream) {
     QNN_REQUIRE(x && y, QNN_EINVAL, "qnn_quantized_act_f32: null pointer");
+    QNN_REFUSE_MAXACT(fn, "qnn_quantized_act_f32");
     QNN_REQUIRE(qnn_is_qact(fn), QNN_EINVAL, "qnn_quantized_act_f32: fn=%d is not a quantised activation", fn);
     QNN_REQUIRE(nb >= 1 && nb <= 24, QNN_EINVAL, "qnn_quantized_act_f32: nb=%d out of range", nb);
     if (fn == QNN_FN_QUANTIZED_TANH) return qnn_quantized_tanh_f32(x, y, n, nb, stream);
@@ -469,6 +470,7 @@ extern "C" int qnn_pack_f32(const float* x, void* y, size_t pixels, int channels
                             int store, void* stream) {
     QNN_REQUIRE(x && y, QNN_EINVAL, "qnn_pack_f32: null pointer");
     QNN_REQUIRE(channels > 0, QNN_EINVAL, "qnn_pack_f32: channels=%d", channels);
+    QNN_REFUSE_MAXACT(fn, "qnn_pack_f32");
     QNN_REQUIRE(fn == QNN_FN_BINARY_TANH || qnn_is_qact(fn) || fn == QNN_FN_GRID,
                 QNN_EINVAL, "qnn_pack_f32: fn=%d cannot be encoded", fn);
     if (pixels == 0) return QNN_OK;

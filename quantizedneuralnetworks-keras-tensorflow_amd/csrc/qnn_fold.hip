@@ -362,6 +362,7 @@ extern "C" int qnn_fold_prepare(const qnn_weights_t* w, int x_store, int x_bits,
                                 qnn_fold_t** out) {
     QNN_REQUIRE(w && epi && out, QNN_EINVAL, "qnn_fold_prepare: null pointer");
     *out = nullptr;
+    QNN_REFUSE_MAXACT(epi->fn, "qnn_fold_prepare");
     QNN_REQUIRE(w->dil_h == 1 && w->dil_w == 1, QNN_EUNSUPPORTED,
                 "qnn_fold_prepare: no folded epilogue for a dilated layer (dilation %d x %d)", w->dil_h, w->dil_w);
     const bool image = x_store == QNN_STORE_U8 || x_store == QNN_STORE_F32_IMAGE;

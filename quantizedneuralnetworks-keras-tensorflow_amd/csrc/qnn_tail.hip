@@ -236,6 +236,7 @@ extern "C" int qnn_avgpool_dense_softmax_forward(const qnn_weights_t* wd, const 
                       wd->store);
         return QNN_EUNSUPPORTED;
     }
+    QNN_REFUSE_MAXACT(epi_dense->fn, "qnn_avgpool_dense_softmax_forward");
     if (epi_dense->fn != QNN_FN_NONE || epi_dense->pool != 1 || epi_dense->res || epi_dense->proj || epi_dense->trick_s != 0.0f ||
         epi_dense->out_store != QNN_STORE_F32) {
         qnn_set_error("qnn_avgpool_dense_softmax_forward: no fused kernel for a dense epilogue with an activation, pooling, a "

@@ -67,9 +67,13 @@ def _wstore(op):
 
 
 def _act_code(act):
-    """(fn, bits) of an activation op, or None if it is not a low-bit clip."""
+    """(fn, bits) of an activation op, or None if it is not a low-bit clip.  None for quantized_maxrelu /
+    quantized_leakymaxrelu too: their values P k / m follow the batch maximum and are not on the fixed grid k / m, so
+    the activation is materialised as float32 and its consumers take the float-input kernels."""
     if act is None:
         return None
+    if act["fn"] == "quantized_leakymaxrelu":
+        quantized_ops.check_leaky_alpha(act.get("alpha", quantized_ops.LEAKY_ALPHA), "quantized_leakymaxrelu")
     if act["fn"] == "binary_tanh":
         return _abi.FN_BINARY_TANH, 1
     if act["fn"] in _QUANT_ACTS and act["nb"] <= 8:
@@ -83,6 +87,18 @@ def _act_code(act):
 _QUANT_ACTS = {"quantized_tanh": _abi.FN_QUANTIZED_TANH, "quantized_relu": _abi.FN_QUANTIZED_RELU,
                "quantized_leakyrelu": _abi.FN_QUANTIZED_LEAKYRELU}
 _NEW_QUANT_FNS = (_abi.FN_QUANTIZED_RELU, _abi.FN_QUANTIZED_LEAKYRELU)
+# scaled by the maximum of the whole batch tensor (include/qnn_abi_maxact.h): elementwise ops on float32 only
+_MAX_ACTS = ("quantized_maxrelu", "quantized_leakymaxrelu")
+
+
+def _refuse_max_acts(spec, who):
+    """The packed engines carry codes on the fixed grid k / 2^(nb-1); an activation whose scale is the batch maximum has
+    no such codes (packed codes plus a device-resident scale are not built): GraphModel runs such a spec."""
+    for op in spec:
+        if op["op"] == "act" and op["fn"] in _MAX_ACTS:
+            raise _abi.NotFusable("%s: activation %r scales by the maximum of the whole batch tensor; its values are not on "
+                                  "the fixed grid k / 2^(nb-1) the packed kernels carry, so it cannot be fused into an "
+                                  "epilogue or packed on load; use GraphModel" % (who, op["fn"]))
 
 
 def _float_images(x, fn):
@@ -258,7 +274,8 @@ def _bn_apply(t, inv, shift):
 
 def _act(t, op):
     """An activation op: the clips of layers/*_ops.py (ternary_tanh thresholds at the mean of the whole batch tensor,
-    ternary_ops.py:23) and LeakyReLU."""
+    ternary_ops.py:23; quantized_maxrelu / quantized_leakymaxrelu scale by its maximum, quantized_ops.py:134: each batch
+    a model is called on is quantised with its own maximum, as the reference's predict(batch_size) does) and LeakyReLU."""
     fn = op["fn"]
     if fn == "binary_tanh":
         return binary_ops.binary_tanh(t)
@@ -268,6 +285,10 @@ def _act(t, op):
         return quantized_ops.quantized_relu(t, op["nb"])
     if fn == "quantized_leakyrelu":
         return quantized_ops.quantized_leakyrelu(t, op["nb"], op.get("alpha", quantized_ops.LEAKY_ALPHA))
+    if fn == "quantized_maxrelu":
+        return quantized_ops.quantized_maxrelu(t, op["nb"])
+    if fn == "quantized_leakymaxrelu":
+        return quantized_ops.quantized_leakymaxrelu(t, op["nb"], op.get("alpha", quantized_ops.LEAKY_ALPHA))
     if fn == "ternary_tanh":
         return ternary_ops.ternary_tanh(t)
     if fn == "leaky_relu":
@@ -385,6 +406,7 @@ class FusedModel(_DomainFlag):
         self._head_no = {}                   # (H, W) of inputs the library has no fused head kernel for
         self.steps = []
         self._keep = []
+        _refuse_max_acts(spec, "FusedModel")
         groups = self._group(spec)
         if groups is None:
             raise _abi.NotFusable("FusedModel: spec is not a fusable chain; use GraphModel")
@@ -832,6 +854,7 @@ class ResidualFusedModel(_DomainFlag):
         library cannot fold exactly keep the chain); False = always the float32 chain.  Same bits either way."""
         if first_layer not in ("auto", "exact", "image"):
             raise ValueError("first_layer must be 'auto', 'exact' or 'image', got %r" % (first_layer,))
+        _refuse_max_acts(spec, "ResidualFusedModel")
         self.first_layer = first_layer
         self.fold = bool(fold)
         self._folds = {}                     # (conv, bn, shortcut kind, ...) -> _abi.Fold or None

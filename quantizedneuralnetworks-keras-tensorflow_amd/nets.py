@@ -59,18 +59,29 @@ def baseline_config(index):
     raise ValueError(index)
 
 
-QUANTIZED_ACTIVATIONS = ("quantized_tanh", "quantized_relu", "quantized_leakyrelu")
+QUANTIZED_ACTIVATIONS = ("quantized_tanh", "quantized_relu", "quantized_leakyrelu", "quantized_maxrelu",
+                         "quantized_leakymaxrelu")
+# the two that scale by the maximum of the whole batch tensor: a network built with them gives logits that depend on
+# which images share a batch, and runs with float32 between its layers.  The builders take them only with batch_scaled=True
+BATCH_SCALED_ACTIVATIONS = ("quantized_maxrelu", "quantized_leakymaxrelu")
 
 
-def _layer_kinds(cf, quantized_activation="quantized_tanh"):
+def _layer_kinds(cf, quantized_activation="quantized_tanh", batch_scaled=False):
     """model_factory.py:24-61 -> (conv kind, conv nb, dense kind, dense nb, act op).
 
     Quirk kept from the reference: the Dense layer of a (full-)qnn gets
     nb=cf.abits, not cf.wbits (model_factory.py:31).
     quantized_activation: the function the reference imports as `quantize_op` (model_factory.py:9; its default is
-    quantized_tanh): the activation of the full-qnn, qbnn and qtnn networks."""
+    quantized_tanh): the activation of the full-qnn, qbnn and qtnn networks.
+    batch_scaled: must be True for the BATCH_SCALED_ACTIVATIONS and False for every other one -- the caller's statement
+    that each batch is quantised with its own maximum (predict(batch_size=b) depends on b, as the reference's does)."""
     if quantized_activation not in QUANTIZED_ACTIVATIONS:
         raise ValueError("quantized_activation must be one of %s, got %r" % (QUANTIZED_ACTIVATIONS, quantized_activation))
+    if (quantized_activation in BATCH_SCALED_ACTIVATIONS) != bool(batch_scaled):
+        raise ValueError("quantized_activation=%r %s: %s scale every batch tensor by its own maximum, so the network's "
+                         "output depends on which images share a batch" %
+                         (quantized_activation, "needs batch_scaled=True" if not batch_scaled else "does not go with batch_scaled=True",
+                          " and ".join(BATCH_SCALED_ACTIVATIONS)))
     nt = cf.network_type
     if nt == "float":
         conv, fc, act = ("float", None), ("float", None), {"op": "act", "fn": "leaky_relu", "alpha": 0.3}
@@ -149,6 +160,10 @@ def _act_second_moment(act):
         return 0.2                  # ~N(0,1) clipped to [0,1)
     if act["fn"] == "quantized_leakyrelu":
         return 0.23                 # [0,1) above zero, a tenth of [-1,0) below
+    if act["fn"] == "quantized_maxrelu":
+        return 0.5                  # ~N(0,1) clipped below at 0; the scale follows the batch maximum: nothing clips above
+    if act["fn"] == "quantized_leakymaxrelu":
+        return 0.505                # the same, plus a hundredth of the negative half
     if act["fn"] == "ternary_tanh":
         return 0.6
     return 0.6
@@ -164,9 +179,9 @@ def _conv_op(gen, kind, nb, kh, cin, cout, strides, use_bias, prev_act):
     return op, var
 
 
-def vgg_spec(cf, seed=0, quantized_activation="quantized_tanh"):
-    """models/vgg.py:5-44.  quantized_activation: see _layer_kinds."""
-    (ck, cnb), (fk, fnb), act = _layer_kinds(cf, quantized_activation)
+def vgg_spec(cf, seed=0, quantized_activation="quantized_tanh", batch_scaled=False):
+    """models/vgg.py:5-44.  quantized_activation, batch_scaled: see _layer_kinds."""
+    (ck, cnb), (fk, fnb), act = _layer_kinds(cf, quantized_activation, batch_scaled)
     gen = _ParamGen(seed)
     spec = []
     cin, prev_act = cf.channels, None
@@ -200,9 +215,10 @@ def vgg_spec(cf, seed=0, quantized_activation="quantized_tanh"):
     return spec
 
 
-def resnet_spec(cf, seed=0, quantized_activation="quantized_tanh"):
-    """models/resnet.py:72-144 (ResNet v1, depth 6n+2, use_bias=False, 0.5*(x+y)).  quantized_activation: see _layer_kinds."""
-    (ck, cnb), (fk, fnb), act = _layer_kinds(cf, quantized_activation)
+def resnet_spec(cf, seed=0, quantized_activation="quantized_tanh", batch_scaled=False):
+    """models/resnet.py:72-144 (ResNet v1, depth 6n+2, use_bias=False, 0.5*(x+y)).  quantized_activation, batch_scaled: see
+    _layer_kinds."""
+    (ck, cnb), (fk, fnb), act = _layer_kinds(cf, quantized_activation, batch_scaled)
     gen = _ParamGen(seed)
     spec = []
     uid = [0]
@@ -269,14 +285,16 @@ def resnet_spec(cf, seed=0, quantized_activation="quantized_tanh"):
     return spec
 
 
-def build_spec(cf, seed=0, quantized_activation="quantized_tanh"):
-    """model_factory.py:63-68.  quantized_activation: "quantized_tanh" (default), "quantized_relu" or
-    "quantized_leakyrelu" -- what a network was trained with after model_factory.py:9 was changed to import that
-    function as `quantize_op`."""
+def build_spec(cf, seed=0, quantized_activation="quantized_tanh", batch_scaled=False):
+    """model_factory.py:63-68.  quantized_activation: "quantized_tanh" (default), "quantized_relu",
+    "quantized_leakyrelu", "quantized_maxrelu" or "quantized_leakymaxrelu" -- what a network was trained with after
+    model_factory.py:9 was changed to import that function as `quantize_op`.  The last two scale by the maximum of the
+    batch tensor (layers/quantized_ops.py here) and are taken only together with batch_scaled=True (ValueError
+    otherwise, see _layer_kinds): such a spec runs on engine.GraphModel, float32 between the layers."""
     if cf.architecture == "VGG":
-        return vgg_spec(cf, seed, quantized_activation)
+        return vgg_spec(cf, seed, quantized_activation, batch_scaled)
     if cf.architecture == "RESNET":
-        return resnet_spec(cf, seed, quantized_activation)
+        return resnet_spec(cf, seed, quantized_activation, batch_scaled)
     raise ValueError("Error: type " + str(cf.architecture) + " is not supported")
 
 
@@ -296,8 +314,15 @@ class Model:
         try:
             self.engine = engine.FusedModel(spec, device, first_layer=first_layer)     # chains (VGG)
         except _abi.NotFusable:                                     # residual / non-fusable topologies
-            self.engine = engine.ResidualFusedModel(spec, device,
-                                                    first_layer=first_layer if first_layer in ("auto", "image") else "exact")
+            try:
+                self.engine = engine.ResidualFusedModel(spec, device,
+                                                        first_layer=first_layer if first_layer in ("auto", "image") else "exact")
+            except _abi.NotFusable:
+                # only the batch-scaled activations (float32 between the layers) are handed on; anything else the
+                # residual engine refuses stays an error
+                if not any(op["op"] == "act" and op["fn"] in BATCH_SCALED_ACTIVATIONS for op in spec):
+                    raise
+                self.engine = engine.GraphModel(spec, device)
         self.layers = [op for op in spec if op["op"] in ("conv", "dense")]
         self.lanes = int(lanes) if lanes is not None else (2 if isinstance(self.engine, engine.FusedModel) else 3)
         self.upload_batches = 8              # predict() on a host array: batches uploaded (and resident) at a time
@@ -384,10 +409,11 @@ class Model:
         print_fn("Total params: %d   engine: %s" % (self.count_params(), type(self.engine).__name__))
 
 
-def build_model(cf, seed=0, device="cuda", first_layer="auto", lanes=None, quantized_activation="quantized_tanh"):
+def build_model(cf, seed=0, device="cuda", first_layer="auto", lanes=None, quantized_activation="quantized_tanh",
+                batch_scaled=False):
     """model_factory.py:18-72: config -> model (synthetic weights; use spec_from_keras_npz +
-    Model(cf, spec) to run an imported checkpoint).  quantized_activation: see build_spec."""
-    return Model(cf, build_spec(cf, seed, quantized_activation), device, first_layer=first_layer, lanes=lanes)
+    Model(cf, spec) to run an imported checkpoint).  quantized_activation, batch_scaled: see build_spec."""
+    return Model(cf, build_spec(cf, seed, quantized_activation, batch_scaled), device, first_layer=first_layer, lanes=lanes)
 
 
 def activation_range_probe(model, x, number, limit=63.0, batch_size=256):
@@ -506,6 +532,9 @@ def spec_from_keras_npz(path, wbits=None, abits=None):
                 # shadows the op of that name and is quantized_tanh unless the import line 9 was changed.  A network
                 # trained with another quantize_op is rebuilt with build_spec(..., quantized_activation=...).
                 op = {"op": "act", "fn": "quantized_tanh", "nb": int(abits)}
+            elif fn in ("quantized_maxrelu", "quantized_leakymaxrelu"):
+                # no lambda of the reference shadows these names: the ops of layers/quantized_ops.py:125-171 themselves
+                op = {"op": "act", "fn": fn, "nb": int(abits)}
             elif fn in ("binary_tanh", "ternary_tanh"):
                 op = {"op": "act", "fn": fn}
             else:

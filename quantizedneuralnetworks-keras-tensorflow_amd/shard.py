@@ -8,7 +8,8 @@ CPU tests).  40 bytes per image: latency-bound, no bucketing needed.
 
 Not shardable this way: ternary_tanh (global mean|x| over the batch tensor,
 ternary_ops.py:23) -- it needs all-reduced (sum, count) first; see
-`allreduce_mean_abs`.
+`allreduce_mean_abs` -- and quantized_maxrelu / quantized_leakymaxrelu (the maximum
+of the batch tensor, quantized_ops.py:134): `allreduce_max`.
 """
 import torch
 import torch.distributed as dist
@@ -96,9 +97,34 @@ def allreduce_mean_abs(x, group=None):
     return (s[0] / s[1]).float()
 
 
+def allreduce_max(ws, group=None):
+    """Maximum over the shards of the workspace word of quantized_maxrelu / quantized_leakymaxrelu (in place): the first
+    32-bit word of `ws` holds the bits of a NON-NEGATIVE float32, for which bit order equals value order, so it is reduced
+    with ReduceOp.MAX on a float32 view.  No-op outside a sharded context / for a single process."""
+    if group is None and _ACTIVE:
+        group = _ACTIVE[-1][0]
+    elif group is None:
+        return ws
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:
+        dist.all_reduce(ws.view(torch.float32)[:1], op=dist.ReduceOp.MAX, group=group)
+    return ws
+
+
+def allreduce_max_relu(x, group=None, valid_rows=None):
+    """Global max(x, 0) of a batch-sharded tensor over its first `valid_rows` batch rows (None: all): the statistic
+    quantized_maxrelu scales by, computed with torch ops (used by the CPU tests; the GPU path is
+    quantized_ops.quantized_maxrelu).  0 where no shard holds a positive value."""
+    part = x if valid_rows is None else x[:valid_rows]
+    m = part.clamp(min=0).amax().float().reshape(1) if part.numel() else torch.zeros(1, dtype=torch.float32, device=x.device)
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:
+        dist.all_reduce(m, op=dist.ReduceOp.MAX, group=group)
+    return m[0]
+
+
 def sharded_forward(model, x_global, rank, world, group=None):
     """forward(shard) on every rank + all-gather of the logits.  Runs inside `sharded(group)`, so a
-    full-tnn network thresholds its ternary activations at the global batch mean."""
+    full-tnn network thresholds its ternary activations at the global batch mean and a quantized_maxrelu network scales
+    by the global batch maximum: the logits equal the unsharded forward's."""
     total = x_global.shape[0]
     lo, hi, per = shard_bounds(total, rank, world)
     with sharded(group, valid_rows=hi - lo):      # a ragged last shard is zero-padded: keep the padding out of the statistics
