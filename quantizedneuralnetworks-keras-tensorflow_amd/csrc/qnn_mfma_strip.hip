@@ -37,6 +37,7 @@
 #include "qnn_mfma_common.h"
 #include "qnn_fold.h"
 #include "qnn_strip_plan.h"
+#include "qnn_strip_device.h"
 
 #ifndef QNN_STRIP16_WPS
 #define QNN_STRIP16_WPS 6        // waves per SIMD (= persistent workgroups per CU): Cin 16 needs 51-67 VGPRs
@@ -61,21 +62,6 @@
 #endif
 
 namespace {
-
-// Workgroup -> (task stream, channel block) when a layer's channel blocks are separate workgroups (gridDim.y > 1): the
-// blocks of one task stream are placed on ONE XCD (workgroups are dealt to the eight XCDs round robin in dispatch order)
-// and start together, so the pieces of a stored pixel written by different blocks meet in the same L2 instead of leaving
-// partial sectors in several (measured on the un-pooled int8 first layer, qnn_first_u8.hip: 0.49 -> 0.39 ms).
-__device__ __forceinline__ void strip_block_map(int& xw, int& yblk) {
-    xw = blockIdx.x; yblk = blockIdx.y;
-    const int nsl = gridDim.y, bxw = gridDim.x;
-    if (nsl > 1 && (bxw & 7) == 0) {
-        const int bid = blockIdx.y * bxw + blockIdx.x;
-        const int xcd = bid & 7, j = bid >> 3;
-        yblk = j % nsl;
-        xw = (j / nsl) * 8 + xcd;
-    }
-}
 
 // FN: the activation of the un-folded epilogue as a template parameter.  0 = quantized_tanh or binary_tanh (told apart at
 // run time, as ever: these instantiations are instruction for instruction what they were), QNN_FN_QUANTIZED_RELU,
@@ -128,6 +114,8 @@ __global__ __launch_bounds__(256, (CIN == 16 ? QNN_STRIP16_WPS : CIN == 32 ? (RE
     const int wid = xw_ * 4 + wave, nw = gridDim.x * 4;
     const int nbase = yb_ * (16 * NT);                // first output channel of this wave
 
+    // (deliberately NOT strip_kblocks / strip_load_filters of qnn_strip_device.h, which state the same table and load: through
+    // them this kernel compiles differently, profiles/strip_chain/README.md.  Keep the two texts equal.)
     // ---- k-block of this lane in every K-step ----
     int dxs[ST], hbs[ST];
     bool kok[ST];
@@ -224,28 +212,12 @@ __global__ __launch_bounds__(256, (CIN == 16 ? QNN_STRIP16_WPS : CIN == 32 ? (RE
     const int orowb = g.W * e.ocw * 4;                // bytes per output row
     const int rrowb = RES == 2 ? g.W * g.cout * 4 : RES == 3 ? 2 * e.proj_W * P0B : orowb;   // (RES = 3: every other input row)
 
-    auto widen = [&](const uint2& q) -> v4i {
-        const uint4 v = make_uint4((q.x << 4) & 0xF0F0F0F0u, q.x & 0xF0F0F0F0u,
-                                   (q.y << 4) & 0xF0F0F0F0u, q.y & 0xF0F0F0F0u);
-        return __builtin_bit_cast(v4i, v);
-    };
-
     for (int task = wid; task < ntasks; task += nw) {
-        // ---- task = (image, strip, row chunk): scalar decode, once per ~rc rows ----
-        const uint32_t rest = qnn_div((uint32_t)task, fd_nch);
-        const int chunk = task - (int)rest * nch;
-        const int n = (int)qnn_div(rest, fd_spr);
-        const int xs = ((int)rest - n * spr) * 16;
-        const int y0 = chunk * rc;
-        const int y1 = min(y0 + rc, g.H);
-        const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<uint8_t*>(x) + (size_t)n * img_x, 0, (int)img_x, 0x00020000);
-        const __amdgpu_buffer_rsrc_t yr = __builtin_amdgcn_make_buffer_rsrc(
-            (uint8_t*)y + (size_t)n * img_y, 0, (int)img_y, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc(
-            RES == 3 ? const_cast<uint8_t*>(e.proj_x) + (size_t)n * img_r
-                     : RES != 0 ? (uint8_t*)const_cast<void*>(e.res) + (size_t)n * img_r : (uint8_t*)y, 0,
-            RES != 0 ? (int)img_r : 0, 0x00020000);
+        const StripTask tk = strip_task(task, fd_nch, nch, fd_spr, spr, rc, g.H);
+        const int n = tk.n, xs = tk.xs, y0 = tk.y0, y1 = tk.y1;
+        const __amdgpu_buffer_rsrc_t xr = strip_image_rsrc(x, n, img_x), yr = strip_image_rsrc(y, n, img_y);
+        const __amdgpu_buffer_rsrc_t rr = RES == 0 ? strip_image_rsrc(y, 0, 0)           // (never read)
+                                                   : strip_image_rsrc(RES == 3 ? (const void*)e.proj_x : e.res, n, img_r);
         // byte offset (inside the image) of this lane's k-block in input row y0 - 1; lanes whose pixel lies left or right of
         // the image start out of range and stay there (0x80000000 + row increments < 2^32)
         int voff[ST];
@@ -305,9 +277,9 @@ __global__ __launch_bounds__(256, (CIN == 16 ? QNN_STRIP16_WPS : CIN == 32 ? (RE
                 for (int d = 0; d < D; ++d) load_res(rs[d], rf[d]);             // rows y0 .. y0 + D - 1
             }
 #pragma unroll
-            for (int st = 0; st < ST; ++st) X[0][st] = widen(t0[st]);
+            for (int st = 0; st < ST; ++st) X[0][st] = strip_widen(t0[st]);
 #pragma unroll
-            for (int st = 0; st < ST; ++st) X[1][st] = widen(t1[st]);
+            for (int st = 0; st < ST; ++st) X[1][st] = strip_widen(t1[st]);
         }
 
         // one output row yy = y0 + j: X slots a / b / c = j, j+1, j+2 (mod 3) hold input rows yy-1 / yy / yy+1; ring slot
@@ -316,7 +288,7 @@ __global__ __launch_bounds__(256, (CIN == 16 ? QNN_STRIP16_WPS : CIN == 32 ? (RE
         auto body = [&](v4i (&Xa)[ST], v4i (&Xb)[ST], v4i (&Xc)[ST], uint2 (&rw)[ST], uint32_t (&rsc)[NT],
                         float4 (&rfc)[NT]) {
 #pragma unroll
-            for (int st = 0; st < ST; ++st) Xc[st] = widen(rw[st]);
+            for (int st = 0; st < ST; ++st) Xc[st] = strip_widen(rw[st]);
             load_row(rw);                              // row yy + 1 + D
             uint32_t rcur[NT];
             float4 fcur[NT];
@@ -325,7 +297,7 @@ __global__ __launch_bounds__(256, (CIN == 16 ? QNN_STRIP16_WPS : CIN == 32 ? (RE
             if constexpr (RES != 0) load_res(rsc, rfc);   // shortcut of row yy + D
             v4i accp[NT];
             if constexpr (RES == 3) {
-                const v4i Xp = widen(make_uint2(rcur[0], rcur[NT - 1]));
+                const v4i Xp = strip_widen(make_uint2(rcur[0], rcur[NT - 1]));
                 const v4i z0 = {0, 0, 0, 0};
 #pragma unroll
                 for (int nt = 0; nt < NT; ++nt) accp[nt] = __builtin_amdgcn_mfma_i32_16x16x64_i8(bwp[nt], Xp, z0, 0, 0, 0);
@@ -487,25 +459,9 @@ __global__ __launch_bounds__(256, (CIN == 16 ? 4 : 2)) void k_conv_strip_s2(Mfma
     const int nbase = yb_ * (16 * NT);
     int dxs[ST], hbs[ST];
     bool kok[ST];
-#pragma unroll
-    for (int st = 0; st < ST; ++st) {
-        kok[st] = kq < 3;
-        dxs[st] = kok[st] ? kq : 1;
-        hbs[st] = st;
-    }
-    const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<uint8_t*>(wq8), 0, (int)mg.w_bytes, 0x00020000);
-    v4i bw[3][ST][NT];
-#pragma unroll
-    for (int dy = 0; dy < 3; ++dy)
-#pragma unroll
-        for (int st = 0; st < ST; ++st)
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) {
-                const int ch = nbase + 4 * NT * (r >> 2) + 4 * nt + (r & 3);       // as in k_conv_strip: consecutive channels per lane
-                const int woff = kok[st] ? (ch * 9 + dy * 3 + dxs[st]) * CIN + hbs[st] * 16 : (int)0x80000000;
-                bw[dy][st][nt] = __builtin_bit_cast(v4i, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, woff, 0, 0));
-            }
+    strip_kblocks_s2(kq, dxs, hbs, kok);
+    v4i bw[3][ST][NT];                                 // as in k_conv_strip: consecutive channels per lane
+    strip_load_filters<CIN>(bw, wq8, mg.w_bytes, nbase, r, kok, dxs, hbs);
     static_assert(NT == 2, "the stride-2 kernel stores one 32-bit word per lane");
     static_assert(!FOLD || FN == 0, "only quantized_tanh is folded");
     const bool binary = e.fn == QNN_FN_BINARY_TANH;
@@ -540,22 +496,10 @@ __global__ __launch_bounds__(256, (CIN == 16 ? 4 : 2)) void k_conv_strip_s2(Mfma
     const v2f act_m2 = {e.act_m, e.act_m}, alpha2 = {0.1f, 0.1f};      // strip_qact<FN>; unused for FN = 0
     const int rowb2 = 2 * g.W * PIXB;                  // two input rows per output row
     const int orowb = g.Wo * e.ocw * 4;
-    auto widen = [&](const uint2& q) -> v4i {
-        const uint4 v = make_uint4((q.x << 4) & 0xF0F0F0F0u, q.x & 0xF0F0F0F0u,
-                                   (q.y << 4) & 0xF0F0F0F0u, q.y & 0xF0F0F0F0u);
-        return __builtin_bit_cast(v4i, v);
-    };
     for (int task = wid; task < ntasks; task += nw) {
-        const uint32_t rest = qnn_div((uint32_t)task, fd_nch);
-        const int chunk = task - (int)rest * nch;
-        const int n = (int)qnn_div(rest, fd_spr);
-        const int xs = ((int)rest - n * spr) * 16;
-        const int y0 = chunk * rc;
-        const int y1 = min(y0 + rc, g.Ho);
-        const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<uint8_t*>(x) + (size_t)n * img_x, 0, (int)img_x, 0x00020000);
-        const __amdgpu_buffer_rsrc_t yr = __builtin_amdgcn_make_buffer_rsrc(
-            (uint8_t*)y + (size_t)n * img_y, 0, (int)img_y, 0x00020000);
+        const StripTask tk = strip_task(task, fd_nch, nch, fd_spr, spr, rc, g.Ho);
+        const int n = tk.n, xs = tk.xs, y0 = tk.y0, y1 = tk.y1;
+        const __amdgpu_buffer_rsrc_t xr = strip_image_rsrc(x, n, img_x), yr = strip_image_rsrc(y, n, img_y);
         int voff[3];
         const int px = 2 * (xs + r) - g.pl + kq;
 #pragma unroll
@@ -591,7 +535,7 @@ __global__ __launch_bounds__(256, (CIN == 16 ? 4 : 2)) void k_conv_strip_s2(Mfma
             for (int dy = 0; dy < 3; ++dy)
 #pragma unroll
                 for (int st = 0; st < ST; ++st) {
-                    const v4i xo = widen(cur[dy][st]);
+                    const v4i xo = strip_widen(cur[dy][st]);
 #pragma unroll
                     for (int nt = 0; nt < NT; ++nt)
                         acc[nt] = __builtin_amdgcn_mfma_i32_16x16x64_i8(bw[dy][st][nt], xo, acc[nt], 0, 0, 0);

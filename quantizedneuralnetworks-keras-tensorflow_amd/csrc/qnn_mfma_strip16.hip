@@ -31,6 +31,7 @@
 #include "qnn_mfma_common.h"
 #include "qnn_fold.h"
 #include "qnn_strip_plan.h"
+#include "qnn_strip_device.h"
 
 namespace {
 
@@ -84,22 +85,11 @@ __global__ __launch_bounds__(256, QNN_S16_BOUNDS) void k_conv_strip16_lds(MfmaGe
     const int xl_row = lane / 10, xl_c = lane - 10 * xl_row;
     const int sl_row = lane >> 3, sl_c = lane & 7;
 
-    auto widen = [&](const uint2& q) -> v4i {
-        const uint4 v = make_uint4((q.x << 4) & 0xF0F0F0F0u, q.x & 0xF0F0F0F0u, (q.y << 4) & 0xF0F0F0F0u, q.y & 0xF0F0F0F0u);
-        return __builtin_bit_cast(v4i, v);
-    };
-
     for (int task = wid; task < ntasks; task += nw) {
-        const uint32_t rest = qnn_div((uint32_t)task, fd_nch);
-        const int chunk = task - (int)rest * nch;
-        const int n = (int)qnn_div(rest, fd_spr);
-        const int xs = ((int)rest - n * spr) * 16;
-        const int y0 = chunk * rc;
-        const int y1 = min(y0 + rc, g.H);
-        const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(x) + (size_t)n * img_x, 0, (int)img_x, 0x00020000);
-        const __amdgpu_buffer_rsrc_t yr = __builtin_amdgcn_make_buffer_rsrc((uint8_t*)y + (size_t)n * img_y, 0, (int)img_y, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc(
-            RES ? (uint8_t*)const_cast<void*>(e.res) + (size_t)n * img_y : (uint8_t*)y, 0, RES ? (int)img_y : 0, 0x00020000);
+        const StripTask tk = strip_task(task, fd_nch, nch, fd_spr, spr, rc, g.H);
+        const int n = tk.n, xs = tk.xs, y0 = tk.y0, y1 = tk.y1;
+        const __amdgpu_buffer_rsrc_t xr = strip_image_rsrc(x, n, img_x), yr = strip_image_rsrc(y, n, img_y);
+        const __amdgpu_buffer_rsrc_t rr = RES ? strip_image_rsrc(e.res, n, img_y) : strip_image_rsrc(y, 0, 0);
         // byte offsets (inside the image) of this lane's 16 bytes in the first six-row group; rows above / below the image
         // and pixel pairs left / right of it are out of range = zeros (the width is even: a pair never straddles the edge)
         const int xpx = xs - 2 + 2 * xl_c;
@@ -122,8 +112,8 @@ __global__ __launch_bounds__(256, QNN_S16_BOUNDS) void k_conv_strip16_lds(MfmaGe
         // of 6 per row): a row's operand is then one ds_read_b128 and no arithmetic
         auto xput_v = [&](int slot, const uint4& v) {
             v4i* dst = reinterpret_cast<v4i*>(xs_lds + slot * kXSlot + lane * 32);
-            dst[0] = widen(make_uint2(v.x, v.y));
-            dst[1] = widen(make_uint2(v.z, v.w));
+            dst[0] = strip_widen(make_uint2(v.x, v.y));
+            dst[1] = strip_widen(make_uint2(v.z, v.w));
         };
         auto xput = [&](int slot) { xput_v(slot, xg); };
         auto sput = [&](int slot) { if constexpr (RES) *reinterpret_cast<uint4*>(ss_lds + slot * kSSlot + lane * 16) = sg; };

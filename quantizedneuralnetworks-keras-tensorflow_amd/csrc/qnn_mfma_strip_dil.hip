@@ -28,6 +28,7 @@
 
 #include "qnn_mfma_common.h"
 #include "qnn_strip_plan.h"
+#include "qnn_strip_device.h"
 
 namespace {
 
@@ -61,6 +62,8 @@ __global__ __launch_bounds__(256, dil_wps(CIN)) void k_conv_strip_dil(MfmaGeom m
     const int wid = blockIdx.x * 4 + wave, nw = gridDim.x * 4;
     const int nbase = blockIdx.y * (16 * NT);         // first output channel of this wave
 
+    // (deliberately NOT strip_kblocks / strip_load_filters of qnn_strip_device.h, which state the same table and load: through
+    // them this kernel compiles differently, profiles/strip_chain/README.md.  Keep the two texts equal.)
     // ---- k-block of this lane in every K-step ----
     int dxs[ST], hbs[ST];
     bool kok[ST];
@@ -113,27 +116,11 @@ __global__ __launch_bounds__(256, dil_wps(CIN)) void k_conv_strip_dil(MfmaGeom m
     const int orowb = g.W * e.ocw * 4;                // bytes per output row
     const int rrowb = RES == 2 ? g.W * g.cout * 4 : orowb;
 
-    auto widen = [&](const uint2& q) -> v4i {
-        const uint4 v = make_uint4((q.x << 4) & 0xF0F0F0F0u, q.x & 0xF0F0F0F0u,
-                                   (q.y << 4) & 0xF0F0F0F0u, q.y & 0xF0F0F0F0u);
-        return __builtin_bit_cast(v4i, v);
-    };
-
     for (int task = wid; task < ntasks; task += nw) {
-        // ---- task = (image, strip, row chunk): scalar decode, once per ~rc rows ----
-        const uint32_t rest = qnn_div((uint32_t)task, fd_nch);
-        const int chunk = task - (int)rest * nch;
-        const int n = (int)qnn_div(rest, fd_spr);
-        const int xs = ((int)rest - n * spr) * 16;
-        const int y0 = chunk * rc;
-        const int y1 = min(y0 + rc, g.H);
-        const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<uint8_t*>(x) + (size_t)n * img_x, 0, (int)img_x, 0x00020000);
-        const __amdgpu_buffer_rsrc_t yr = __builtin_amdgcn_make_buffer_rsrc(
-            (uint8_t*)y + (size_t)n * img_y, 0, (int)img_y, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc(
-            RES != 0 ? (uint8_t*)const_cast<void*>(e.res) + (size_t)n * img_r : (uint8_t*)y, 0,
-            RES != 0 ? (int)img_r : 0, 0x00020000);
+        const StripTask tk = strip_task(task, fd_nch, nch, fd_spr, spr, rc, g.H);
+        const int n = tk.n, xs = tk.xs, y0 = tk.y0, y1 = tk.y1;
+        const __amdgpu_buffer_rsrc_t xr = strip_image_rsrc(x, n, img_x), yr = strip_image_rsrc(y, n, img_y);
+        const __amdgpu_buffer_rsrc_t rr = RES == 0 ? strip_image_rsrc(y, 0, 0) : strip_image_rsrc(e.res, n, img_r);
         // byte offset (inside the image) of this lane's k-block in input row y0 - d: negative above the image (out of
         // range as an unsigned offset, in range again from row 0 on); a tap column left or right of the image starts
         // out of range and stays there (0x80000000 + row increments < 2^32, images are < 10^9 bytes)
@@ -165,7 +152,7 @@ __global__ __launch_bounds__(256, dil_wps(CIN)) void k_conv_strip_dil(MfmaGeom m
 #pragma unroll
             for (int i = 0; i < 2 * DIL; ++i)
 #pragma unroll
-                for (int st = 0; st < ST; ++st) X[i][st] = widen(t[i][st]);
+                for (int st = 0; st < ST; ++st) X[i][st] = strip_widen(t[i][st]);
         }
 
         // one output row yy = y0 + j: X slots j, j + d, j + 2d (mod R) hold input rows yy - d / yy / yy + d; ring slot
@@ -184,7 +171,7 @@ __global__ __launch_bounds__(256, dil_wps(CIN)) void k_conv_strip_dil(MfmaGeom m
             }
             if constexpr (RES != 0) rvoff += rrowb;
 #pragma unroll
-            for (int st = 0; st < ST; ++st) Xc[st] = widen(rw[st]);
+            for (int st = 0; st < ST; ++st) Xc[st] = strip_widen(rw[st]);
             load_row(rw);                              // row yy + d + R
             v4i acc[NT];
 #pragma unroll

@@ -30,6 +30,7 @@
 // Register counts and waves per SIMD: the table below.
 #include "qnn_mfma_common.h"
 #include "qnn_strip_plan.h"
+#include "qnn_strip_device.h"
 
 // Waves per SIMD and ring slots, from the register counts of the ISA (unified 512-entry file per SIMD lane: 512 / waves,
 // in steps of 8).  The ring costs 4 * ST registers per slot (twice the int4 kernel's raw ring), the filters 12 * ST * NT.
@@ -57,18 +58,6 @@ constexpr int strip8_wps(int cin, int res) {
 #define QNN_STRIP8_S2_WPS(CIN) ((CIN) == 16 ? 4 : 2)   // stride 2: filters 24 / 48 + two row triples 24 / 48 + constants
 
 namespace {
-
-// (qnn_mfma_strip.hip: the channel blocks of one task stream on one XCD)
-__device__ __forceinline__ void strip8_block_map(int& xw, int& yblk) {
-    xw = blockIdx.x; yblk = blockIdx.y;
-    const int nsl = gridDim.y, bxw = gridDim.x;
-    if (nsl > 1 && (bxw & 7) == 0) {
-        const int bid = blockIdx.y * bxw + blockIdx.x;
-        const int xcd = bid & 7, j = bid >> 3;
-        yblk = j % nsl;
-        xw = (j / nsl) * 8 + xcd;
-    }
-}
 
 constexpr float kMagic8 = 12582912.0f;               // 1.5 * 2^23
 constexpr int kMagic8Bits = 0x4B400000;
@@ -178,10 +167,12 @@ void k_conv_strip_i8(MfmaGeom mg, EpiArgs e, const uint8_t* __restrict__ x, cons
     const int r = lane & 15, kq = lane >> 4;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     int xw_, yb_;
-    strip8_block_map(xw_, yb_);
+    strip_block_map(xw_, yb_);
     const int wid = xw_ * 4 + wave, nw = gridDim.x * 4;
     const int nbase = yb_ * (16 * NT);                // first output channel of this wave
 
+    // (deliberately NOT strip_kblocks / strip_load_filters of qnn_strip_device.h, which state the same table and load: through
+    // them this kernel compiles differently, profiles/strip_chain/README.md.  Keep the two texts equal.)
     // ---- k-block of this lane in every K-step ----
     int dxs[ST], hbs[ST];
     bool kok[ST];
@@ -213,20 +204,10 @@ void k_conv_strip_i8(MfmaGeom mg, EpiArgs e, const uint8_t* __restrict__ x, cons
     const int rrowb = RES == 2 ? g.W * g.cout * 4 : orowb;
 
     for (int task = wid; task < ntasks; task += nw) {
-        // ---- task = (image, strip, row chunk): scalar decode, once per ~rc rows ----
-        const uint32_t rest = qnn_div((uint32_t)task, fd_nch);
-        const int chunk = task - (int)rest * nch;
-        const int n = (int)qnn_div(rest, fd_spr);
-        const int xs = ((int)rest - n * spr) * 16;
-        const int y0 = chunk * rc;
-        const int y1 = min(y0 + rc, g.H);
-        const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<uint8_t*>(x) + (size_t)n * img_x, 0, (int)img_x, 0x00020000);
-        const __amdgpu_buffer_rsrc_t yr = __builtin_amdgcn_make_buffer_rsrc(
-            (uint8_t*)y + (size_t)n * img_y, 0, (int)img_y, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc(
-            RES != 0 ? (uint8_t*)const_cast<void*>(e.res) + (size_t)n * img_r : (uint8_t*)y, 0,
-            RES != 0 ? (int)img_r : 0, 0x00020000);
+        const StripTask tk = strip_task(task, fd_nch, nch, fd_spr, spr, rc, g.H);
+        const int n = tk.n, xs = tk.xs, y0 = tk.y0, y1 = tk.y1;
+        const __amdgpu_buffer_rsrc_t xr = strip_image_rsrc(x, n, img_x), yr = strip_image_rsrc(y, n, img_y);
+        const __amdgpu_buffer_rsrc_t rr = RES == 0 ? strip_image_rsrc(y, 0, 0) : strip_image_rsrc(e.res, n, img_r);
         // byte offset (inside the image) of this lane's k-block in input row y0 - 1; lanes whose pixel lies left or right of
         // the image start out of range and stay there (0x80000000 + row increments < 2^32); row -1 is a negative = huge
         // unsigned offset, the rows below the image end beyond the descriptor's size: both read as zeros
@@ -340,37 +321,22 @@ void k_conv_strip_i8_s2(MfmaGeom mg, EpiArgs e, const uint8_t* __restrict__ x, c
     const int r = lane & 15, kq = lane >> 4;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     int xw_, yb_;
-    strip8_block_map(xw_, yb_);
+    strip_block_map(xw_, yb_);
     const int wid = xw_ * 4 + wave, nw = gridDim.x * 4;
     const int nbase = yb_ * (16 * NT);
-    const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<uint8_t*>(wq8), 0, (int)mg.w_bytes, 0x00020000);
-    v4i bw[3][ST][NT];
-#pragma unroll
-    for (int dy = 0; dy < 3; ++dy)
-#pragma unroll
-        for (int st = 0; st < ST; ++st)
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) {
-                const int ch = nbase + 4 * NT * (r >> 2) + 4 * nt + (r & 3);       // as in k_conv_strip_i8
-                const int woff = kq < 3 ? (ch * 9 + dy * 3 + kq) * CIN + st * 16 : (int)0x80000000;
-                bw[dy][st][nt] = __builtin_bit_cast(v4i, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, woff, 0, 0));
-            }
+    int dxs[ST], hbs[ST];
+    bool kok[ST];
+    strip_kblocks_s2(kq, dxs, hbs, kok);
+    v4i bw[3][ST][NT];                                 // as in k_conv_strip_i8
+    strip_load_filters<CIN>(bw, wq8, mg.w_bytes, nbase, r, kok, dxs, hbs);
     Strip8Epi<NT, BIAS> ep;
     ep.init(e, nbase + 4 * NT * kq, false, false);
     const int rowb2 = 2 * g.W * PIXB;                  // two input rows per output row
     const int orowb = g.Wo * g.cout;
     for (int task = wid; task < ntasks; task += nw) {
-        const uint32_t rest = qnn_div((uint32_t)task, fd_nch);
-        const int chunk = task - (int)rest * nch;
-        const int n = (int)qnn_div(rest, fd_spr);
-        const int xs = ((int)rest - n * spr) * 16;
-        const int y0 = chunk * rc;
-        const int y1 = min(y0 + rc, g.Ho);
-        const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<uint8_t*>(x) + (size_t)n * img_x, 0, (int)img_x, 0x00020000);
-        const __amdgpu_buffer_rsrc_t yr = __builtin_amdgcn_make_buffer_rsrc(
-            (uint8_t*)y + (size_t)n * img_y, 0, (int)img_y, 0x00020000);
+        const StripTask tk = strip_task(task, fd_nch, nch, fd_spr, spr, rc, g.Ho);
+        const int n = tk.n, xs = tk.xs, y0 = tk.y0, y1 = tk.y1;
+        const __amdgpu_buffer_rsrc_t xr = strip_image_rsrc(x, n, img_x), yr = strip_image_rsrc(y, n, img_y);
         int voff[3];
         const int px = 2 * (xs + r) - g.pl + kq;
         const bool pvalid = xs + r < g.Wo;
