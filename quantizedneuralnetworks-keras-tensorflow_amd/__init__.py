@@ -21,6 +21,8 @@ from .layers.binary_layers import BinaryConv2D, BinaryDense, BinaryConvolution2D
 from .layers.quantized_layers import (QuantizedConv2D, QuantizedDense,  # noqa: F401
                                       QuantizedConvolution2D)
 from .layers.ternary_layers import TernaryConv2D, TernaryDense, TernaryConvolution2D  # noqa: F401
+from .layers.pooling import (MaxPooling2D, AveragePooling2D, GlobalAveragePooling2D,  # noqa: F401
+                             GlobalMaxPooling2D)
 
 __all__ = [
     "binary_tanh", "binarize", "binary_sigmoid", "quantize", "quantized_tanh", "quantized_relu", "quantized_leakyrelu",
@@ -28,4 +30,5 @@ __all__ = [
     "ternary_tanh", "ternarize", "BinaryConv2D", "BinaryDense", "BinaryConvolution2D",
     "QuantizedConv2D", "QuantizedDense", "QuantizedConvolution2D",
     "TernaryConv2D", "TernaryDense", "TernaryConvolution2D",
+    "MaxPooling2D", "AveragePooling2D", "GlobalAveragePooling2D", "GlobalMaxPooling2D",
 ]

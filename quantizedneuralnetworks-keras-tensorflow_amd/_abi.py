@@ -1,4 +1,5 @@
-"""ctypes binding of include/qnn_abi.h, qnn_abi_dilation.h, qnn_abi_qact.h and qnn_abi_maxact.h (csrc/libqnn_hip.so).
+"""ctypes binding of include/qnn_abi.h, qnn_abi_dilation.h, qnn_abi_qact.h, qnn_abi_maxact.h and qnn_abi_pool.h
+(csrc/libqnn_hip.so).
 
 The library is loaded eagerly and loudly: a missing or unloadable .so raises at
 import time of any op that needs it (there is no CPU implementation to fall back
@@ -48,6 +49,16 @@ EXPORTS_QACT = ["qnn_quantized_act_f32"]
 
 # include/qnn_abi_maxact.h: quantized_maxrelu / quantized_leakymaxrelu as a reduction, an apply pass and the two in sequence
 EXPORTS_MAXACT = ["qnn_maxact_max_f32", "qnn_maxact_apply_f32", "qnn_quantized_maxact_f32"]
+
+# include/qnn_abi_pool.h: MaxPooling2D / AveragePooling2D with pool_size, strides and padding, on float32 and on packed codes
+EXPORTS_POOL = ["qnn_pool2d_out_hw", "qnn_pool2d_forward"]
+POOL_MAX, POOL_AVG = 0, 1
+
+
+class Pool2D(ctypes.Structure):
+    """qnn_pool2d_t"""
+    _fields_ = [("mode", ctypes.c_int32), ("ph", ctypes.c_int32), ("pw", ctypes.c_int32), ("sh", ctypes.c_int32),
+                ("sw", ctypes.c_int32), ("same_pad", ctypes.c_int32)]
 
 
 class Projection(ctypes.Structure):
@@ -151,7 +162,9 @@ def load():
     lib.qnn_conv2d_workspace_bytes.restype = sz
     lib.qnn_conv2d_forward_f32in.argtypes = [vp, vp, ci, ci, ci, ci, ci, ctypes.POINTER(Epilogue), vp,
                                              vp, sz, vp]
-    for name in EXPORTS + EXPORTS_DILATION + EXPORTS_QACT + EXPORTS_MAXACT:   # every symbol the headers declare must be exported
+    lib.qnn_pool2d_out_hw.argtypes = [ci, ci, ctypes.POINTER(Pool2D), ctypes.POINTER(ci), ctypes.POINTER(ci)]
+    lib.qnn_pool2d_forward.argtypes = [vp, ci, ci, ci, ci, ci, ci, ctypes.POINTER(Pool2D), vp, ci, vp]
+    for name in EXPORTS + EXPORTS_DILATION + EXPORTS_QACT + EXPORTS_MAXACT + EXPORTS_POOL:   # every symbol the headers declare must be exported
         getattr(lib, name)
     _lib = lib
     return lib
@@ -298,6 +311,43 @@ def avgpool_packed(p, store, bits, N, H, W, C, size):
     check(load().qnn_avgpool_packed_f32(ptr(p), store, bits, N, H, W, C, size, ptr(out), stream_ptr()),
           "qnn_avgpool_packed_f32")
     return out
+
+
+def _pair(v, what):
+    """An int or a pair of ints as Keras takes pool_size / strides: (rows, columns)."""
+    if isinstance(v, (tuple, list)):
+        if len(v) != 2:
+            raise ValueError("%s must be an integer or a pair of integers, got %r" % (what, v))
+        return int(v[0]), int(v[1])
+    return int(v), int(v)
+
+
+def pool2d(x, store, bits, N, H, W, C, mode, size, strides=None, same=False):
+    """qnn_pool2d_forward: MaxPooling2D / AveragePooling2D(size, strides, 'same' if same else 'valid') of an NHWC tensor:
+    float32 (store = STORE_F32) or int32 packed words (STORE_BIN / _I4 / _I8 at `bits`).  mode: POOL_MAX -> a tensor
+    stored like x (packed: (N * Ho * Wo, words) codes at the same bits), POOL_AVG -> float32 (N, Ho, Wo, C).  strides None =
+    the window.  Returns (y, Ho, Wo).  The output size comes from the library (qnn_pool2d_out_hw), which refuses a
+    'valid' window larger than the image; STORE_T2 raises QnnUnsupported."""
+    ph, pw = _pair(size, "size")
+    sh, sw = (ph, pw) if strides is None else _pair(strides, "strides")
+    desc = Pool2D(int(mode), ph, pw, sh, sw, 1 if same else 0)
+    if store == STORE_T2:
+        raise QnnUnsupported("pool2d: no pooling on the ternary bit planes (QNN_STORE_T2): unpack, pool, pack")
+    Ho, Wo = ctypes.c_int(0), ctypes.c_int(0)
+    check(load().qnn_pool2d_out_hw(H, W, ctypes.byref(desc), ctypes.byref(Ho), ctypes.byref(Wo)), "qnn_pool2d_out_hw")
+    Ho, Wo = Ho.value, Wo.value
+    if store == STORE_F32:
+        x = require_cuda(x, "pool2d")
+    elif not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.int32 and x.is_contiguous()):
+        raise QnnError("pool2d: a packed input must be a contiguous int32 CUDA tensor")
+    y_store = store if mode == POOL_MAX else STORE_F32
+    if y_store == STORE_F32:
+        y = torch.empty((N, Ho, Wo, C), dtype=torch.float32, device=x.device)
+    else:
+        y = torch.empty((N * Ho * Wo, words(store, C)), dtype=torch.int32, device=x.device)
+    check(load().qnn_pool2d_forward(ptr(x), store, bits, N, H, W, C, ctypes.byref(desc), ptr(y), y_store, stream_ptr()),
+          "qnn_pool2d_forward")
+    return y, Ho, Wo
 
 
 def softmax(x, out=None):

@@ -195,7 +195,7 @@ class _SpecGraph:
                 i if spec[i]["op"] == "dense" and i == len(spec) - 1 else None
             fl = self._behind(self.srcs[de][0], "flatten") if de is not None else None
             ap = self._behind(self.srcs[fl][0], "avgpool") if fl is not None else None
-            if ap is not None:
+            if ap is not None and not _new_pool(spec[ap]):      # the fused tail is the size-only average
                 t = (ap, fl, de, sm)
             self.tails[i] = t
         return self.tails[i]
@@ -237,13 +237,52 @@ class _SpecGraph:
 
 # ---- the stock Keras layers around the contractions, on float32 tensors.  Every interpreter below calls these, so their
 # results cannot drift apart; oracle/qnn_oracle.py restates them independently.
+# Pooling ops.  An op that carries only an integer `size` is the OLD FORM (a square window, strides equal to it,
+# 'valid'): what every spec builder and reference checkpoint produces, run by the torch code below and fused as before.
+# Anything else -- `size` as a pair, `strides`, `padding`, the two global ops -- is the NEW FORM: Keras' pooling with
+# TensorFlow's padding (include/qnn_abi_pool.h), run by qnn_pool2d_forward on float32 here and on packed codes by the engines.
+_POOLS = ("maxpool", "avgpool", "globalmaxpool", "globalavgpool")
+
+
+def _new_pool(op):
+    if op["op"] in ("globalmaxpool", "globalavgpool"):
+        return True
+    return op["op"] in ("maxpool", "avgpool") and ("strides" in op or "padding" in op or
+                                                   not isinstance(op.get("size", 2), (int, np.integer)))
+
+
+def _pool_run(x, store, bits, shape, op):
+    """A new-form pooling op on an NHWC tensor `x` (float32, or packed words at (store, bits)) through
+    qnn_pool2d_forward: (y, output shape); y is float32 for the averages, stored like x for the maxima.  The global ops
+    are the whole image as the window and give (N, C)."""
+    N, H, W, C = shape
+    mode = _abi.POOL_MAX if op["op"] in ("maxpool", "globalmaxpool") else _abi.POOL_AVG
+    if op["op"].startswith("global"):
+        y, _, _ = _abi.pool2d(x, store, bits, N, H, W, C, mode, (H, W))
+        return (y.reshape(N, C) if y.dtype == torch.float32 else y), (N, C)
+    padding = str(op.get("padding", "valid")).lower()
+    if padding not in ("valid", "same"):
+        raise ValueError("%s: padding must be 'valid' or 'same', got %r" % (op["op"], op.get("padding")))
+    y, Ho, Wo = _abi.pool2d(x, store, bits, N, H, W, C, mode, op.get("size", 2 if mode == _abi.POOL_MAX else 8),
+                            op.get("strides"), padding == "same")
+    return y, (N, Ho, Wo, C)
+
+
+def _pool_f32(t, op):
+    return _pool_run(t.contiguous(), _abi.STORE_F32, 0, t.shape, op)[0]
+
+
 def _maxpool(t, op):
+    if _new_pool(op):
+        return _pool_f32(t, op)
     s = op.get("size", 2)
     N, H, W, C = t.shape
     return t[:, :H // s * s, :W // s * s, :].reshape(N, H // s, s, W // s, s, C).amax(dim=(2, 4))
 
 
 def _avgpool(t, op):
+    if _new_pool(op):
+        return _pool_f32(t, op)
     s = op.get("size", 8)
     N, H, W, C = t.shape
     win = t[:, :H // s * s, :W // s * s, :].reshape(N, H // s, s, W // s, s, C)
@@ -296,7 +335,7 @@ def _act(t, op):
     raise ValueError(fn)
 
 
-_GLUE = {"maxpool": _maxpool, "avgpool": _avgpool, "zeropad": _zeropad, "flatten": _flatten, "scale": _scale, "act": _act,
+_GLUE = {"maxpool": _maxpool, "avgpool": _avgpool, "globalmaxpool": _pool_f32, "globalavgpool": _pool_f32, "zeropad": _zeropad, "flatten": _flatten, "scale": _scale, "act": _act,
          "softmax": lambda t, op: _abi.softmax(t)}
 
 
@@ -500,8 +539,8 @@ class FusedModel(_DomainFlag):
             if i < n and spec[i]["op"] == "act":
                 g["act"] = spec[i]; i += 1
             if i < n and spec[i]["op"] == "maxpool":
-                if spec[i].get("size", 2) != 2 or g["kind"] != "conv":
-                    return None
+                if _new_pool(spec[i]) or spec[i].get("size", 2) != 2 or g["kind"] != "conv":
+                    return None                  # (a new-form pool is never the 2x2 / 2 epilogue pool, whatever its size)
                 g["pool"] = 2; i += 1
             if i < n and spec[i]["op"] == "softmax":
                 g["softmax"] = True; i += 1
@@ -688,6 +727,21 @@ class GraphModel:
         self.spec = spec
         self.graph = _SpecGraph(spec, device)
         self.fuse_tail = True                # avg-pool + Flatten + Dense [+ softmax] in one launch (_SpecGraph.run_tail)
+        self.kernel_log = None               # tests: set to a list to record the kernel of every new-form pooling op
+
+    def _pool(self, src, op):
+        """A new-form pooling op.  Behind a low-bit clip the activation is packed as its consumers would pack it on load
+        and pooled on the codes (the maximum stays packed for the next contraction); everything else is pooled in float32."""
+        if isinstance(src, _Virtual) and src.fn in (_abi.FN_BINARY_TANH,) + _abi.QUANT_FNS and src.pre.dim() == 4:
+            bits = 1 if src.fn == _abi.FN_BINARY_TANH else src.nb
+            store = _abi.STORE_BIN if bits == 1 else _abi.store_for_bits(bits)
+            src = _Packed(_abi.pack(src.pre, src.pre.shape[-1], src.fn, bits, store), store, bits, src.pre.shape)
+        if isinstance(src, _Packed) and len(src.shape) == 4:
+            return _pool_packed(src, op, self.kernel_log)
+        y = _GLUE[op["op"]](self._plain(src), op)
+        if self.kernel_log is not None:
+            self.kernel_log.append(_abi.last_kernel())
+        return y
 
     def _tail(self, i, src):
         """The classifier tail that starts at avgpool op `i`, fused: (its op indices, result) or None.  The clip in front
@@ -706,11 +760,27 @@ class GraphModel:
 
     @staticmethod
     def _plain(t):
+        if isinstance(t, _Packed):
+            return t.to_f32()
         return t.materialize() if isinstance(t, _Virtual) else t
 
     def _contract(self, i, op, src, inv, shift):
         """Conv / dense op `i` on `src` with BN (inv, shift) in its epilogue."""
         kind, wstore, g = op["op"], _wstore(op), self.graph
+        if isinstance(src, _Packed):         # the codes a new-form max-pool left
+            if wstore is not None and _join_store(src.bits, wstore) == src.store and \
+                    len(src.shape) == (4 if kind == "conv" else 2):
+                w = g.weights(i, src.store)
+                if kind == "conv":
+                    N, H, W, _ = src.shape
+                    return _abi.conv2d(w, src.t, src.store, src.bits, N, H, W, inv, shift)[0]
+                return _abi.dense(w, src.t, src.store, src.bits, src.shape[0], inv, shift)
+            # another store is needed (or float weights): the values are on the grid, where binary_tanh / quantized_tanh at
+            # their width are the identity, so the consumer may clip them again on load
+            fn = _abi.FN_BINARY_TANH if src.store == _abi.STORE_BIN else _abi.FN_QUANTIZED_TANH
+            v = _Virtual(src.to_f32(), fn, src.bits, None)
+            v._mat = v.pre
+            src = v
         if isinstance(src, _Virtual) and wstore is not None:
             bits = 1 if src.fn == _abi.FN_BINARY_TANH else src.nb
             if src.fn == _abi.FN_GRID and op["kind"] == "ternary" and TERNARY_T2:
@@ -772,6 +842,8 @@ class GraphModel:
                 # global mean over the batch tensor: not fusable; the result is on the grid {-1,0,1} and is packed as
                 # such by its consumers
                 y = _Virtual(_act(self._plain(src), op), _abi.FN_GRID, 1, op)
+            elif kind in _POOLS and _new_pool(op):
+                y = self._pool(src, op)
             elif kind in _GLUE:
                 y = _GLUE[kind](self._plain(src), op)
             else:
@@ -792,6 +864,15 @@ class _Packed:
 
     def to_f32(self):
         return _abi.unpack(self.t, math.prod(self.shape[:-1]), self.shape[-1], self.store, self.bits).reshape(self.shape)
+
+
+def _pool_packed(src, op, log=None):
+    """A new-form pooling op on the packed NHWC activation `src` (BIN / I4 / I8): the maximum of codes is a code, so
+    maxpool / globalmaxpool give a _Packed of the same store and bits; the averages read the codes and give float32."""
+    y, shape = _pool_run(src.t, src.store, src.bits, src.shape, op)
+    if log is not None:
+        log.append(_abi.last_kernel())
+    return _Packed(y, src.store, src.bits, shape) if y.dtype == torch.int32 else y
 
 
 def _ok_lowbit(op):
@@ -919,15 +1000,18 @@ class ResidualFusedModel(_DomainFlag):
 
     def _act_out_store(self, name, bits):
         """Packed store the consumers of activation `name` want, or None if one needs float32."""
-        joins = []
-        for ci in self.cons.get(name, []):
-            op = self.spec[ci]
-            if op["op"] in ("conv", "dense") and _wstore(op) is not None:
-                joins.append(_join_store(bits, _wstore(op)))
-            elif op["op"] in ("add", "flatten", "avgpool"):
-                continue                 # these read packed codes directly (avgpool: qnn_avgpool_packed_f32)
-            else:
-                return None
+        joins, todo = [], [name]
+        while todo:
+            for ci in self.cons.get(todo.pop(), []):
+                op = self.spec[ci]
+                if op["op"] in ("conv", "dense") and _wstore(op) is not None:
+                    joins.append(_join_store(bits, _wstore(op)))
+                elif op["op"] in ("add", "flatten", "avgpool", "globalavgpool"):
+                    continue             # these read packed codes directly (avgpool: qnn_avgpool_packed_f32 / qnn_pool2d_forward)
+                elif op["op"] in ("maxpool", "globalmaxpool") and _new_pool(op):
+                    todo.append(self.names[ci])      # codes in, codes out (qnn_pool2d_forward): what ITS consumers want
+                else:
+                    return None
         if not joins:
             return _abi.STORE_BIN if bits == 1 else _abi.store_for_bits(bits)
         if all(j == _abi.STORE_BIN for j in joins):
@@ -940,7 +1024,7 @@ class ResidualFusedModel(_DomainFlag):
         out, todo = [], [name]
         while todo:
             for ci in self.cons.get(todo.pop(), []):
-                if self.spec[ci]["op"] in ("maxpool", "flatten"):
+                if self.spec[ci]["op"] in ("maxpool", "globalmaxpool", "flatten"):
                     todo.append(self.names[ci])
                 else:
                     out.append(self.spec[ci])
@@ -1132,13 +1216,18 @@ class ResidualFusedModel(_DomainFlag):
                 return _abi.dense(self.graph.weights(i, src.store), src.t, src.store, src.bits, src.shape[0])
             if kind == "flatten" and src.shape[-1] % _abi.per_word(src.store) == 0:
                 return _Packed(src.t, src.store, src.bits, (src.shape[0], math.prod(src.shape[1:])))
-            if kind == "avgpool" and src.store != _abi.STORE_T2:     # window sums on the codes: no float32 copy
+            if kind in _POOLS and _new_pool(op):
+                if src.store != _abi.STORE_T2 and len(src.shape) == 4:      # on the codes: no float32 copy
+                    return _pool_packed(src, op, self.kernel_log)
+            elif kind == "avgpool" and src.store != _abi.STORE_T2:   # window sums on the codes: no float32 copy
                 return _abi.avgpool_packed(src.t, src.store, src.bits, *src.shape, op.get("size", 8))
         t = src.to_f32() if isinstance(src, _Packed) else src
         if kind == "dense":
             return _abi.dense(self.graph.weights(i, _abi.STORE_F32), t.contiguous(), _abi.STORE_F32, 0, t.shape[0])
         out = _GLUE[kind](t, op)
-        if kind == "maxpool" and isinstance(src, _Packed) and src.store == _abi.STORE_T2:
+        if kind in _POOLS and _new_pool(op) and self.kernel_log is not None:
+            self.kernel_log.append(_abi.last_kernel())
+        if kind in ("maxpool", "globalmaxpool") and isinstance(src, _Packed) and src.store == _abi.STORE_T2:
             # the maximum of ternary codes is a ternary code: stay on the bit planes for the next ternary layer
             out = _Packed(_abi.pack(out.contiguous(), out.shape[-1], _abi.FN_GRID, 1, src.store), src.store, src.bits,
                           out.shape)
@@ -1443,7 +1532,7 @@ class LayerModel:
                 y = _GLUE[kind](src, op)
                 if kind == "act":
                     d = self._grid(op)
-                elif kind in ("maxpool", "flatten"):
+                elif kind in ("maxpool", "globalmaxpool", "flatten"):
                     d = dom.get(sname)      # max of grid values stays on the grid
             else:
                 raise ValueError(kind)

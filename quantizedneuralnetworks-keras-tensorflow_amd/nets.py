@@ -473,6 +473,26 @@ def synthetic_images(cf, n, seed=0):
     return (synthetic_images_u8(cf, n, seed).astype(F32) / F32(255)).astype(F32)
 
 
+def _pool_data_format(c, name):
+    if c.get("data_format") == "channels_first":
+        raise ValueError("pooling layer %r has data_format='channels_first'; only channels_last (NHWC) is supported" % name)
+
+
+def _pool_op(kind, c, name):
+    """The spec op of a MaxPooling2D / AveragePooling2D config.  A square window with strides equal to it (Keras'
+    strides=None) under 'valid' is the size-only op every spec builder emits; everything else carries the window and the
+    strides as pairs and the padding (engine.py: qnn_pool2d_forward)."""
+    _pool_data_format(c, name)
+    size = tuple(int(v) for v in c["pool_size"])
+    strides = size if c.get("strides") is None else tuple(int(v) for v in c["strides"])
+    padding = str(c.get("padding", "valid")).lower()
+    if padding not in ("valid", "same"):
+        raise ValueError("pooling layer %r: unsupported padding %r" % (name, padding))
+    if size[0] == size[1] and strides == size and padding == "valid":
+        return {"op": kind, "size": size[0]}
+    return {"op": kind, "size": size, "strides": strides, "padding": padding}
+
+
 def spec_from_keras_npz(path, wbits=None, abits=None):
     """Rebuild a net spec from a Keras 2.1.3 checkpoint converted by tools/import_keras_hdf5.py
     (counterpart of test_resnet.py:44-66 build + load_weights).  The topology comes from the
@@ -546,10 +566,11 @@ def spec_from_keras_npz(path, wbits=None, abits=None):
             src = None
         elif cls == "Lambda":
             op = {"op": "scale", "value": 0.5}
-        elif cls == "AveragePooling2D":
-            op = {"op": "avgpool", "size": int(c["pool_size"][0])}
-        elif cls == "MaxPooling2D":
-            op = {"op": "maxpool", "size": int(c["pool_size"][0])}
+        elif cls in ("AveragePooling2D", "MaxPooling2D"):
+            op = _pool_op("avgpool" if cls == "AveragePooling2D" else "maxpool", c, name)
+        elif cls in ("GlobalAveragePooling2D", "GlobalMaxPooling2D"):
+            _pool_data_format(c, name)
+            op = {"op": "globalavgpool" if cls == "GlobalAveragePooling2D" else "globalmaxpool"}
         elif cls == "ZeroPadding2D":
             op = {"op": "zeropad", "pad": int(c["padding"][0][0])}
         elif cls == "Flatten":
