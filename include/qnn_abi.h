@@ -215,6 +215,8 @@ typedef struct qnn_epilogue {
  *   QNN_EPI_NO_HALO_TAB  k_conv_mfma_halo with a "bits" fold: every wave derives its lanes' fold constants (and the FP6
  *                        form's accumulator offset) in the kernel's preamble instead of loading the per-lane table that
  *                        qnn_fold_prepare built into the handle
+ *   QNN_EPI_NO_FIRST_WIDE  the byte first layer on 32-pixel-wide images (pooled int4 or float32 output): two 16-column
+ *                        strips per image, each with its column halo, instead of one strip that is the whole row
  * The restricted-domain first-layer kernels are selected by the TYPED input stores QNN_STORE_F32_IMAGE /
  * QNN_STORE_F32_UNIT of the call (above), never by a switch.
  */
@@ -226,6 +228,7 @@ typedef struct qnn_epilogue {
 #define QNN_EPI_NO_FIRST_TAB   32u
 #define QNN_EPI_NO_FIRST_BITS  64u
 #define QNN_EPI_NO_HALO_TAB    128u
+#define QNN_EPI_NO_FIRST_WIDE  256u
 
 /* ---- library ------------------------------------------------------------ */
 int         qnn_version(void);

@@ -68,6 +68,24 @@ __device__ __forceinline__ void image_bytes2(uint32_t& b0, uint32_t& b1, ImageDo
     dom.err = fmaxf(fmaxf(dom.err, fabsf(d0)), fabsf(d1));
 }
 
+// three staged elements (the image-wide strip): the per-element arithmetic of image_bytes2, the two merges regrouped
+__device__ __forceinline__ void image_bytes3(uint32_t& b0, uint32_t& b1, uint32_t& b2, ImageDomain& dom) {
+    float t0, t1, t2, u0, u1, u2;
+    asm("v_mul_f32 %0, 0x437f0000, %1" : "=v"(t0) : "v"(__uint_as_float(b0)));
+    asm("v_mul_f32 %0, 0x437f0000, %1" : "=v"(t1) : "v"(__uint_as_float(b1)));
+    asm("v_mul_f32 %0, 0x437f0000, %1" : "=v"(t2) : "v"(__uint_as_float(b2)));
+    asm("v_add_f32 %0, 0x4b000000, %1" : "=v"(u0) : "v"(t0));
+    asm("v_add_f32 %0, 0x4b000000, %1" : "=v"(u1) : "v"(t1));
+    asm("v_add_f32 %0, 0x4b000000, %1" : "=v"(u2) : "v"(t2));
+    const float d0 = __fsub_rn(t0, __fsub_rn(u0, 8388608.0f)), d1 = __fsub_rn(t1, __fsub_rn(u1, 8388608.0f));
+    const float d2 = __fsub_rn(t2, __fsub_rn(u2, 8388608.0f));
+    b0 = __float_as_uint(u0) ^ 0x4B000080u;
+    b1 = __float_as_uint(u1) ^ 0x4B000080u;
+    b2 = __float_as_uint(u2) ^ 0x4B000080u;
+    dom.orbits = (dom.orbits | b0 | b1) | b2;
+    dom.err = fmaxf(fmaxf(fmaxf(dom.err, fabsf(d0)), fabsf(d1)), fabsf(d2));
+}
+
 // (QNN_STORE_I4, 2, BIN): the fused pipeline, quantized_tanh / binary_tanh codes;  (QNN_STORE_F32, 1, false): the layer
 // behind the float32 surface (any fn)
 // FOLD (round 4): the epilogue of the pooled int4 form as qnn_fold.h's mode 3 -- u = fma(float(S), A2, C2), one
@@ -79,7 +97,12 @@ __device__ __forceinline__ void image_bytes2(uint32_t& b0, uint32_t& b1, ImageDo
 // offset block's last A byte is +1 and meets beta[c], so the pooled maximum IS the bit pattern of the float
 // 12582912 + S + beta (patterns of one binade order like the sums) and one FMA per value replaces conversion + FMA.
 // 0 = the in-kernel preamble and the conversion (no handle, or QNN_EPI_NO_FIRST_TAB).
-template <int OUT, int POOL, bool BIN, bool F32IN, bool FOLD = false, int TAB = 0>
+// SW: conv columns of a strip.  16 = the walk described above, any W % 16 == 0.  32 = the strip IS the row of a 32-pixel
+// image (W == 32 only): two input rows are 192 values = three per lane with no dummy lane-slot, there is no column
+// halo to load (ring pixels -1 and 32 keep the code-0 byte they are initialised with), no column test, one task per
+// image and chunk, and a step is four tiles = 16 MFMAs whose epilogue runs per tile pair, (0, 1) then (2, 3).  The row
+// pitch stays 40 words: the A reads touch pixels -1 .. 33 = 35 words, and 40 == 8 mod 32 keeps their banks.
+template <int OUT, int POOL, bool BIN, bool F32IN, bool FOLD = false, int TAB = 0, int SW = 16>
 __global__ __launch_bounds__(256, 4) void k_conv_first_u8(ConvGeom g, EpiArgs e, const void* __restrict__ x,
                                                            const float* __restrict__ wq, void* __restrict__ y,
                                                            int ntasks, int spr, FastDiv fd_spr, int nch, FastDiv fd_nch,
@@ -93,6 +116,9 @@ __global__ __launch_bounds__(256, 4) void k_conv_first_u8(ConvGeom g, EpiArgs e,
     uint32_t* lds = reinterpret_cast<uint32_t*>(smem_u8) + wave * kWaveLdsU;
     uint8_t* ldsb = reinterpret_cast<uint8_t*>(lds);
     static_assert(TAB == 0 || FOLD, "the operand table belongs to a fold handle");
+    static_assert(SW == 16 || SW == 32, "a 16-column strip, or the whole row of a 32-pixel image");
+    constexpr int NE = SW == 32 ? 3 : 2;                         // staged elements per lane and row pair
+    constexpr int NT = SW / 8;                                   // tiles of 8 conv columns per step
     // code 0 everywhere; the constant block (bits form: its last byte is +1, the A byte that beta meets)
     for (int i = lane; i < kWaveLdsU; i += 64) lds[i] = (TAB == 2 && i == kConstU + 3) ? 0x01808080u : 0x80808080u;
 
@@ -157,12 +183,27 @@ __global__ __launch_bounds__(256, 4) void k_conv_first_u8(ConvGeom g, EpiArgs e,
     constexpr int EB = F32IN ? 4 : 1;                            // bytes per input element
     const int rowb = g.W * 3 * EB;                               // bytes per input row
     ImageDomain dom;                                             // F32IN: what this lane staged, tested once at the end
+    // the wide strip: elements lane, lane + 64, lane + 128 of the 192 values of two whole rows, which are contiguous in
+    // the image; ring pixel = column + 1.  Per-lane constants of the kernel, not of a task.
+    int st[NE];
+    const int vw = lane * EB;                                    // byte offset of element `lane` in a row pair
+    if constexpr (SW == 32) {
+#pragma unroll
+        for (int j = 0; j < NE; ++j) {
+            const int idx = lane + 64 * j;
+            const int erow = idx >= 96 ? 1 : 0, erem = idx - 96 * erow;
+            const int epx = erem / 3, ech = erem - 3 * epx;
+            st[j] = erow * (kRowPitchU * 4) + (epx + 1) * 4 + ech;
+        }
+    } else {
+        st[0] = st0; st[1] = st1;
+    }
 
     for (int task = wid; task < ntasks; task += nw) {
         const uint32_t rest = qnn_div((uint32_t)task, fd_nch);
         const int chunk = task - (int)rest * nch;
-        const int n = (int)qnn_div(rest, fd_spr);
-        const int xs = ((int)rest - n * spr) * 16;
+        const int n = SW == 32 ? (int)rest : (int)qnn_div(rest, fd_spr);
+        const int xs = SW == 32 ? 0 : ((int)rest - n * spr) * 16;
         const int rp0 = chunk * rc, rp1 = min(rp0 + rc, g.H / 2);        // rc is even or nch == 1: rp0 is even
         const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(
             (uint8_t*)const_cast<void*>(x) + (size_t)n * img_x, 0, (int)img_x, 0x00020000);
@@ -178,53 +219,62 @@ __global__ __launch_bounds__(256, 4) void k_conv_first_u8(ConvGeom g, EpiArgs e,
         const int c0col = xs - 1 + e0px, c1col = xs - 1 + e1px;
         const int v0 = (c0col >= 0 && c0col < g.W) ? (c0col * 3 + e0ch) * EB + e0row * rowb : (int)0x80000000;
         const int v1 = (e1ok && c1col >= 0 && c1col < g.W) ? (c1col * 3 + e1ch) * EB + rowb : (int)0x80000000;
-        auto stage_load = [&](int row, uint32_t& b0, uint32_t& b1) {   // rows `row`, `row + 1`
+        struct Staged { uint32_t b[NE]; };
+        // wide strip: rows >= 0 need one sum per lane, elements 1 and 2 ride on the instruction's offset field; the
+        // task's first load may start at row -1, and there each element's whole sum is formed so that it wraps as one
+        auto stage_load = [&](int row, Staged& f, bool first = false) {      // rows `row`, `row + 1`
             const int so = row * rowb;                           // may be negative: the sum wraps out of range
-            if constexpr (F32IN) {
-                b0 = __builtin_amdgcn_raw_buffer_load_b32(xr, v0 + so, 0, 0);      // float bits; converted at the write
-                b1 = __builtin_amdgcn_raw_buffer_load_b32(xr, v1 + so, 0, 0);
-            } else {
-                b0 = __builtin_amdgcn_raw_buffer_load_b8(xr, v0 + so, 0, 0);
-                b1 = __builtin_amdgcn_raw_buffer_load_b8(xr, v1 + so, 0, 0);
+#pragma unroll
+            for (int j = 0; j < NE; ++j) {
+                int vo = (SW == 32 ? vw + 64 * j * EB : j == 0 ? v0 : v1) + so;
+                if (SW == 32 && first) asm volatile("" : "+v"(vo));
+                if constexpr (F32IN) f.b[j] = __builtin_amdgcn_raw_buffer_load_b32(xr, vo, 0, 0);   // float bits; converted at the write
+                else f.b[j] = __builtin_amdgcn_raw_buffer_load_b8(xr, vo, 0, 0);
             }
         };
-        auto stage_write = [&](auto slotc, uint32_t b0, uint32_t b1) {   // into the ring slots SLOT, SLOT + 1
+        auto stage_write = [&](auto slotc, Staged f) {           // into the ring slots SLOT, SLOT + 1
             constexpr int SB = decltype(slotc)::value * (kRowPitchU * 4);
-            if constexpr (F32IN) image_bytes2(b0, b1, dom);      // the low bytes come back as signed bytes
-            else { b0 ^= 0x80u; b1 ^= 0x80u; }
-            ldsb[st0 + SB] = (uint8_t)b0;
-            ldsb[st1 + SB] = (uint8_t)b1;
+            if constexpr (F32IN) {                               // the low bytes come back as signed bytes
+                if constexpr (SW == 32) image_bytes3(f.b[0], f.b[1], f.b[2], dom);
+                else image_bytes2(f.b[0], f.b[1], dom);
+            } else {
+#pragma unroll
+                for (int j = 0; j < NE; ++j) f.b[j] ^= 0x80u;
+            }
+#pragma unroll
+            for (int j = 0; j < NE; ++j) ldsb[st[j] + SB] = (uint8_t)f.b[j];
         };
         const int yy_first = 2 * rp0;
-        uint32_t fa0, fa1, fb0, fb1, fc0, fc1;
-        stage_load(yy_first - 1, fa0, fa1);
-        stage_load(yy_first + 1, fb0, fb1);
-        stage_load(yy_first + 3, fc0, fc1);
-        stage_write(std::integral_constant<int, 0>{}, fa0, fa1);         // rows yy_first - 1, yy_first: slots 0, 1
+        Staged fsa, fsb, fsc;
+        stage_load(yy_first - 1, fsa, true);
+        stage_load(yy_first + 1, fsb);
+        stage_load(yy_first + 3, fsc);
+        stage_write(std::integral_constant<int, 0>{}, fsa);              // rows yy_first - 1, yy_first: slots 0, 1
 
         auto step = [&](auto parc, int rp) {
             constexpr int PAR = decltype(parc)::value;           // rp & 1
             const int yy0 = 2 * rp;
             // rows yy0+1, yy0+2 complete the four rows of this step: slots (yy0 + 2) & 3 and the next
-            stage_write(std::integral_constant<int, PAR ? 0 : 2>{}, fb0, fb1);
-            fb0 = fc0; fb1 = fc1;
-            stage_load(yy0 + 5, fc0, fc1);                       // two steps ahead
+            stage_write(std::integral_constant<int, PAR ? 0 : 2>{}, fsb);
+            fsb = fsc;
+            stage_load(yy0 + 5, fsc);                            // two steps ahead
             const uint32_t* abase = lds + (PAR ? ab1 : ab0);
-            v4i A[2];
+            v4i A[NT];
 #pragma unroll
-            for (int t = 0; t < 2; ++t) {
+            for (int t = 0; t < NT; ++t) {
                 const uint32_t* p = abase + tstep * t;
                 // the 4th dword (the pixel after the three taps) meets zero filter bytes
                 A[t] = __builtin_bit_cast(v4i, make_uint4(p[0], p[1], p[2], p[3]));
             }
-            // 8 groups (tile t = gq >> 2, filter block nt = gq & 3): the MFMA of group gq + 1 is issued before group gq
-            // is consumed
+            // 4 NT groups (tile t = gq >> 2, filter block nt = gq & 3): the MFMA of group gq + 1 is issued before group gq
+            // is consumed; the packing epilogue runs behind every eighth group, on tiles (0, 1) and (wide strip) (2, 3)
+            constexpr int NG = 4 * NT;
             v4i acc[2];
             int T[8];
             auto consume = [&](int gq, const v4i& a) {
                 const int t = gq >> 2, nt = gq & 3;
                 if constexpr (POOL == 2) {
-                    T[gq] = max(max(a[0], a[1]), max(a[2], a[3]));
+                    T[gq & 7] = max(max(a[0], a[1]), max(a[2], a[3]));
                 } else {
                     // position i of window kq -> conv pixel (yy0 + (i >> 1), xs + 8t + 2kq + (i & 1))
 #pragma unroll
@@ -242,43 +292,48 @@ __global__ __launch_bounds__(256, 4) void k_conv_first_u8(ConvGeom g, EpiArgs e,
             };
             acc[0] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[0], bw[0], z, 0, 0, 0);
 #pragma unroll
-            for (int gq = 0; gq < 8; ++gq) {
-                if (gq + 1 < 8)
-                    acc[(gq + 1) & 1] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[(gq + 1) >> 2], bw[(gq + 1) & 3], z, 0, 0, 0);
-                consume(gq, acc[gq & 1]);
-            }
-            if constexpr (OUT == QNN_STORE_I4 && FOLD) {
-                static_assert(!FOLD || (!BIN && POOL == 2), "the fold covers the pooled quantized_tanh form");
-                uint32_t tp[4];
+            for (int h = 0; h < NT / 2; ++h) {
 #pragma unroll
-                for (int j = 0; j < 4; ++j)             // pairs (value j, value j + 4): same filter block, tiles 0 and 1
-                    tp[j] = TAB == 2 ? qnn_fold_pair_bits(T[j], T[j + 4], fa[j], fa[j], fb[j], fb[j])
-                                     : qnn_fold_pair_fma(T[j], T[j + 4], fa[j], fa[j], fb[j], fb[j]);
-                const uint32_t uo = __builtin_amdgcn_perm(tp[3], tp[1], 0x07030501u);
-                const uint32_t ue = __builtin_amdgcn_perm(tp[2], tp[0], 0x07030501u);
-                const uint32_t P = (uo & 0xF0F0F0F0u) | ((ue >> 4) & 0x0F0F0F0Fu);      // nibble j = code of value j
-                __builtin_amdgcn_raw_buffer_store_b32(join_tiles(P), yr, ylane, rp * yrow, 0);
-            } else if constexpr (OUT == QNN_STORE_I4) {
-                // lane (column r, window kq): value j = 4*t + nt = channel 4 r + nt of pooled pixel xs/2 + kq + 4 t
-                int cb[8];
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const float u = __fmaf_rn((float)T[j], fa[j & 3], fb[j & 3]);
-                    if constexpr (BIN) {
-                        cb[j] = u > 0x1p-24f ? kMagicBits + 1 : kMagicBits - 1;
-                    } else {
-                        // rint + clamp in one add and one integer median (the low bits of u + magic are rint(u) + 8)
-                        const int bits = __float_as_int(__fadd_rn(u, magic));
-                        asm("v_med3_i32 %0, %1, %2, %3" : "=v"(cb[j]) : "v"(bits), "v"(code_lo), "v"(code_hi));
-                    }
+                for (int gq = 8 * h; gq < 8 * h + 8; ++gq) {
+                    if (gq + 1 < NG)
+                        acc[(gq + 1) & 1] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[(gq + 1) >> 2], bw[(gq + 1) & 3], z, 0, 0, 0);
+                    consume(gq, acc[gq & 1]);
                 }
-                // sum_j cb[j] << 4j by Horner: seven v_lshl_add_u32 (the compiler's form was 7 shifts + 5 three-way adds)
-                uint32_t P = (uint32_t)cb[7];
-#pragma unroll
-                for (int j = 6; j >= 0; --j) asm("v_lshl_add_u32 %0, %1, 4, %2" : "=v"(P) : "v"(P), "v"(cb[j]));
-                P -= (uint32_t)(kMagicBits - 8) * 0x11111111u;
-                const uint32_t Wd = join_tiles(P) ^ 0x88888888u;
-                __builtin_amdgcn_raw_buffer_store_b32(Wd, yr, ylane, rp * yrow, 0);
+                // tile pair h: pooled pixels kq + 4 * tile start 8 further per pair = 8 * ocw words, on the store's scalar offset
+                const int ys = rp * yrow + h * (32 * e.ocw);
+                if constexpr (OUT == QNN_STORE_I4 && FOLD) {
+                    static_assert(!FOLD || (!BIN && POOL == 2), "the fold covers the pooled quantized_tanh form");
+                    uint32_t tp[4];
+    #pragma unroll
+                    for (int j = 0; j < 4; ++j)             // pairs (value j, value j + 4): same filter block, tiles 0 and 1
+                        tp[j] = TAB == 2 ? qnn_fold_pair_bits(T[j], T[j + 4], fa[j], fa[j], fb[j], fb[j])
+                                         : qnn_fold_pair_fma(T[j], T[j + 4], fa[j], fa[j], fb[j], fb[j]);
+                    const uint32_t uo = __builtin_amdgcn_perm(tp[3], tp[1], 0x07030501u);
+                    const uint32_t ue = __builtin_amdgcn_perm(tp[2], tp[0], 0x07030501u);
+                    const uint32_t P = (uo & 0xF0F0F0F0u) | ((ue >> 4) & 0x0F0F0F0Fu);      // nibble j = code of value j
+                    __builtin_amdgcn_raw_buffer_store_b32(join_tiles(P), yr, ylane, ys, 0);
+                } else if constexpr (OUT == QNN_STORE_I4) {
+                    // lane (column r, window kq): value j = 4*t + nt = channel 4 r + nt of pooled pixel xs/2 + kq + 4 t
+                    int cb[8];
+    #pragma unroll
+                    for (int j = 0; j < 8; ++j) {
+                        const float u = __fmaf_rn((float)T[j], fa[j & 3], fb[j & 3]);
+                        if constexpr (BIN) {
+                            cb[j] = u > 0x1p-24f ? kMagicBits + 1 : kMagicBits - 1;
+                        } else {
+                            // rint + clamp in one add and one integer median (the low bits of u + magic are rint(u) + 8)
+                            const int bits = __float_as_int(__fadd_rn(u, magic));
+                            asm("v_med3_i32 %0, %1, %2, %3" : "=v"(cb[j]) : "v"(bits), "v"(code_lo), "v"(code_hi));
+                        }
+                    }
+                    // sum_j cb[j] << 4j by Horner: seven v_lshl_add_u32 (the compiler's form was 7 shifts + 5 three-way adds)
+                    uint32_t P = (uint32_t)cb[7];
+    #pragma unroll
+                    for (int j = 6; j >= 0; --j) asm("v_lshl_add_u32 %0, %1, 4, %2" : "=v"(P) : "v"(P), "v"(cb[j]));
+                    P -= (uint32_t)(kMagicBits - 8) * 0x11111111u;
+                    const uint32_t Wd = join_tiles(P) ^ 0x88888888u;
+                    __builtin_amdgcn_raw_buffer_store_b32(Wd, yr, ylane, ys, 0);
+                }
             }
         };
         int rp = rp0;
@@ -601,35 +656,37 @@ int qnn_try_launch_first_u8(const ConvGeom& g, const EpiArgs& e, const void* x, 
 #undef U8_FULL
         return 0;
     }
-#define U8_LAUNCH(OUT_, POOL_, BIN_)                                                                                       \
+    // W == 32: the strip is the whole row (SW = 32), one task per image and chunk -- same planner, same LDS, same name in
+    // the kernel log.  QNN_EPI_NO_FIRST_WIDE keeps the two 16-column strips; every other width has only those.
+    const bool wide = g.W == 32 && !(e.flags & QNN_EPI_NO_FIRST_WIDE);
+    if (wide && !qnn_strip_plan(&p, g.N, 1, g.H / 2, blocks_cap, 1.5, 2)) return 1;
+    const dim3 wgrid(p.blocks);
+    const size_t lds_ring = (size_t)4 * kWaveLdsU * 4;           // the table forms keep no operand table in LDS
+    uint32_t* const dflag = e.dom_flag ? e.dom_flag : w->d_flag;
+#define U8_K(OUT_, POOL_, BIN_, F32_, FOLD_, TAB_, LDS_)                                                                    \
     do {                                                                                                                   \
-        if (f32in)                                                                                                         \
-            hipLaunchKernelGGL((k_conv_first_u8<OUT_, POOL_, BIN_, true>), grid, block, lds, s, g, e, x, w->d_wq, y,        \
-                               QNN_STRIP_PLAN_ARGS(p), (uint32_t)img_x, wscale, D, (e.dom_flag ? e.dom_flag : w->d_flag)); \
+        if (!wide)                                                                                                         \
+            hipLaunchKernelGGL((k_conv_first_u8<OUT_, POOL_, BIN_, F32_, FOLD_, TAB_>), grid, block, LDS_, s, g, e, x,      \
+                               w->d_wq, y, QNN_STRIP_PLAN_ARGS(p), (uint32_t)img_x, wscale, D, dflag);                     \
         else                                                                                                               \
-            hipLaunchKernelGGL((k_conv_first_u8<OUT_, POOL_, BIN_, false>), grid, block, lds, s, g, e, x, w->d_wq, y,       \
-                               QNN_STRIP_PLAN_ARGS(p), (uint32_t)img_x, wscale, D, (e.dom_flag ? e.dom_flag : w->d_flag)); \
+            hipLaunchKernelGGL((k_conv_first_u8<OUT_, POOL_, BIN_, F32_, FOLD_, TAB_, 32>), wgrid, block, LDS_, s, g, e, x, \
+                               w->d_wq, y, QNN_STRIP_PLAN_ARGS(p), (uint32_t)img_x, wscale, D, dflag);                     \
     } while (0)
-    if (!fused) U8_LAUNCH(QNN_STORE_F32, 1, false);
-    else if (e.fn == QNN_FN_BINARY_TANH) U8_LAUNCH(QNN_STORE_I4, 2, true);
+#define U8_LAUNCH(OUT_, POOL_, BIN_, FOLD_, TAB_, LDS_)                                                                     \
+    do {                                                                                                                   \
+        if (f32in) U8_K(OUT_, POOL_, BIN_, true, FOLD_, TAB_, LDS_);                                                        \
+        else U8_K(OUT_, POOL_, BIN_, false, FOLD_, TAB_, LDS_);                                                             \
+    } while (0)
+    if (!fused) U8_LAUNCH(QNN_STORE_F32, 1, false, false, 0, lds);
+    else if (e.fn == QNN_FN_BINARY_TANH) U8_LAUNCH(QNN_STORE_I4, 2, true, false, 0, lds);
     else if (e.fold_a && e.fold_c && e.act_m == 8.0f && e.first_tab) {     // ... with the handle's operand table
-        const size_t lds_ring = (size_t)4 * kWaveLdsU * 4;
-#define U8_TAB(F32_, TAB_)                                                                                                  \
-        hipLaunchKernelGGL((k_conv_first_u8<QNN_STORE_I4, 2, false, F32_, true, TAB_>), grid, block, lds_ring, s, g, e, x,   \
-                           w->d_wq, y, QNN_STRIP_PLAN_ARGS(p), (uint32_t)img_x, wscale, D, (e.dom_flag ? e.dom_flag : w->d_flag))
-        if (e.first_tab_bits) { if (f32in) U8_TAB(true, 2); else U8_TAB(false, 2); }
-        else { if (f32in) U8_TAB(true, 1); else U8_TAB(false, 1); }
-#undef U8_TAB
+        if (e.first_tab_bits) U8_LAUNCH(QNN_STORE_I4, 2, false, true, 2, lds_ring);
+        else U8_LAUNCH(QNN_STORE_I4, 2, false, true, 1, lds_ring);
     }
-    else if (e.fold_a && e.fold_c && e.act_m == 8.0f) {       // folded epilogue (mode 3 handle of this layer, qnn_fold.h)
-        if (f32in)
-            hipLaunchKernelGGL((k_conv_first_u8<QNN_STORE_I4, 2, false, true, true>), grid, block, lds, s, g, e, x, w->d_wq, y,
-                               QNN_STRIP_PLAN_ARGS(p), (uint32_t)img_x, wscale, D, (e.dom_flag ? e.dom_flag : w->d_flag));
-        else
-            hipLaunchKernelGGL((k_conv_first_u8<QNN_STORE_I4, 2, false, false, true>), grid, block, lds, s, g, e, x, w->d_wq, y,
-                               QNN_STRIP_PLAN_ARGS(p), (uint32_t)img_x, wscale, D, (e.dom_flag ? e.dom_flag : w->d_flag));
-    }
-    else U8_LAUNCH(QNN_STORE_I4, 2, false);
+    // folded epilogue (mode 3 handle of this layer, qnn_fold.h)
+    else if (e.fold_a && e.fold_c && e.act_m == 8.0f) U8_LAUNCH(QNN_STORE_I4, 2, false, true, 0, lds);
+    else U8_LAUNCH(QNN_STORE_I4, 2, false, false, 0, lds);
 #undef U8_LAUNCH
+#undef U8_K
     return 0;
 }
