@@ -122,6 +122,19 @@ def _join_store(act_bits, wstore):
     return max(a, w, _abi.STORE_I4)
 
 
+def _weights_fit(op, store):
+    """True if the weights of contraction `op` can be prepacked at packed activation store `store` (what _join_store
+    arrives at; a tensor whose store the planner did not join with this op is contracted in float32 instead)."""
+    ws = _wstore(op)
+    if ws is None:
+        return False
+    if store == _abi.STORE_BIN:
+        return ws == _abi.STORE_BIN
+    if store == _abi.STORE_T2:
+        return op["kind"] == "ternary"
+    return ws == _abi.STORE_BIN or ws <= store
+
+
 def _dilation(op):
     """dilation_rate of a conv op as a pair ((1, 1) where the spec says nothing: dense ops, ordinary windows)."""
     d = op.get("dilation_rate", (1, 1))
@@ -998,25 +1011,49 @@ class ResidualFusedModel(_DomainFlag):
               and fn == _abi.FN_QUANTIZED_TANH and bits == 4 and out_store == _abi.STORE_I4)
         return pi if ok else None
 
+    def _channels(self, name):
+        """Channels of tensor `name` as far as the spec alone says: those of the contraction it descends from through
+        the ops that keep them (an add: its first operand), None for the images or behind a flatten."""
+        while name in self.prod:
+            i = self.prod[name]
+            if self.spec[i]["op"] in ("conv", "dense"):
+                return int(self.spec[i]["kernel"].shape[-1])
+            if self.spec[i]["op"] == "flatten":
+                return None
+            name = self.srcs[i][0]
+        return None
+
     def _act_out_store(self, name, bits):
-        """Packed store the consumers of activation `name` want, or None if one needs float32."""
-        joins, todo = [], [name]
+        """Packed store the consumers of activation `name` want, or None if one needs float32.  A flatten is looked
+        through like a new-form max-pool: it hands the packed words on as they are, so the dense behind it joins the
+        store, which is then widened until every pixel's channels fill whole words (the dense weights are packed as one
+        contiguous K = H W C vector, as in FusedModel; channels that fill no store's words are unpacked by the flatten)."""
+        joins, todo, dense_behind_flatten = [], [(name, False)], False
         while todo:
-            for ci in self.cons.get(todo.pop(), []):
+            n, flat = todo.pop()
+            for ci in self.cons.get(n, []):
                 op = self.spec[ci]
                 if op["op"] in ("conv", "dense") and _wstore(op) is not None:
                     joins.append(_join_store(bits, _wstore(op)))
-                elif op["op"] in ("add", "flatten", "avgpool", "globalavgpool"):
+                    dense_behind_flatten |= flat
+                elif op["op"] in ("add", "avgpool", "globalavgpool"):
                     continue             # these read packed codes directly (avgpool: qnn_avgpool_packed_f32 / qnn_pool2d_forward)
+                elif op["op"] == "flatten":
+                    todo.append((self.names[ci], True))      # the same words, seen as (N, K): what ITS consumers want
                 elif op["op"] in ("maxpool", "globalmaxpool") and _new_pool(op):
-                    todo.append(self.names[ci])      # codes in, codes out (qnn_pool2d_forward): what ITS consumers want
+                    todo.append((self.names[ci], flat))      # codes in, codes out (qnn_pool2d_forward): what ITS consumers want
                 else:
                     return None
         if not joins:
             return _abi.STORE_BIN if bits == 1 else _abi.store_for_bits(bits)
         if all(j == _abi.STORE_BIN for j in joins):
-            return _abi.STORE_BIN
-        return max([j for j in joins if j != _abi.STORE_BIN] + [_abi.STORE_I4])
+            store = _abi.STORE_BIN
+        else:
+            store = max([j for j in joins if j != _abi.STORE_BIN] + [_abi.STORE_I4])
+        ch = self._channels(name) if dense_behind_flatten else None
+        while ch is not None and ch % _abi.per_word(store) != 0 and store < _abi.STORE_I8:
+            store = {_abi.STORE_BIN: _abi.STORE_I4, _abi.STORE_I4: _abi.STORE_I8}[store]
+        return store
 
     def _users_through_pools(self, name):
         """The ops that finally consume tensor `name`, looking through max-pools and flattens (both keep ternary
@@ -1212,7 +1249,7 @@ class ResidualFusedModel(_DomainFlag):
                 return y
         src = self._ev(memo, s0)
         if isinstance(src, _Packed):         # the ops that read packed words as they are
-            if kind == "dense" and _wstore(op) is not None:
+            if kind == "dense" and _weights_fit(op, src.store):
                 return _abi.dense(self.graph.weights(i, src.store), src.t, src.store, src.bits, src.shape[0])
             if kind == "flatten" and src.shape[-1] % _abi.per_word(src.store) == 0:
                 return _Packed(src.t, src.store, src.bits, (src.shape[0], math.prod(src.shape[1:])))
