@@ -1,5 +1,5 @@
-"""ctypes binding of include/qnn_abi.h, qnn_abi_dilation.h, qnn_abi_qact.h, qnn_abi_maxact.h and qnn_abi_pool.h
-(csrc/libqnn_hip.so).
+"""ctypes binding of include/qnn_abi.h, qnn_abi_dilation.h, qnn_abi_qact.h, qnn_abi_maxact.h, qnn_abi_pool.h and
+qnn_abi_scaled.h (csrc/libqnn_hip.so).
 
 The library is loaded eagerly and loudly: a missing or unloadable .so raises at
 import time of any op that needs it (there is no CPU implementation to fall back
@@ -53,6 +53,10 @@ EXPORTS_MAXACT = ["qnn_maxact_max_f32", "qnn_maxact_apply_f32", "qnn_quantized_m
 # include/qnn_abi_pool.h: MaxPooling2D / AveragePooling2D with pool_size, strides and padding, on float32 and on packed codes
 EXPORTS_POOL = ["qnn_pool2d_out_hw", "qnn_pool2d_forward"]
 POOL_MAX, POOL_AVG = 0, 1
+
+# include/qnn_abi_scaled.h: the two activations of qnn_abi_maxact.h as packed codes plus the device-resident scale, and the
+# conv / dense entries that consume them
+EXPORTS_SCALED = ["qnn_maxact_pack_f32", "qnn_conv2d_forward_scaled", "qnn_dense_forward_scaled"]
 
 
 class Pool2D(ctypes.Structure):
@@ -164,7 +168,10 @@ def load():
                                              vp, sz, vp]
     lib.qnn_pool2d_out_hw.argtypes = [ci, ci, ctypes.POINTER(Pool2D), ctypes.POINTER(ci), ctypes.POINTER(ci)]
     lib.qnn_pool2d_forward.argtypes = [vp, ci, ci, ci, ci, ci, ci, ctypes.POINTER(Pool2D), vp, ci, vp]
-    for name in EXPORTS + EXPORTS_DILATION + EXPORTS_QACT + EXPORTS_MAXACT + EXPORTS_POOL:   # every symbol the headers declare must be exported
+    lib.qnn_maxact_pack_f32.argtypes = [vp, vp, vp, sz, ci, ci, ci, ci, vp, vp]
+    lib.qnn_conv2d_forward_scaled.argtypes = [vp, vp, ci, ci, ci, ci, ci, ctypes.POINTER(Epilogue), vp, vp, vp]
+    lib.qnn_dense_forward_scaled.argtypes = [vp, vp, ci, ci, ci, ctypes.POINTER(Epilogue), vp, vp, vp]
+    for name in EXPORTS + EXPORTS_DILATION + EXPORTS_QACT + EXPORTS_MAXACT + EXPORTS_POOL + EXPORTS_SCALED:   # every symbol the headers declare must be exported
         getattr(lib, name)
     _lib = lib
     return lib
@@ -297,6 +304,28 @@ def pack(x, channels, fn, nb, store):
     check(load().qnn_pack_f32(ptr(x), ptr(out), pixels, channels, fn, nb, store, stream_ptr()),
           "qnn_pack_f32")
     return out
+
+
+def maxact_pack(x, channels, fn, nb, store, workspace, y=None):
+    """qnn_maxact_pack_f32 (include/qnn_abi_scaled.h): x float32 (..., channels) CUDA -> int32 (pixels, words) codes of
+    quantized_maxrelu / quantized_leakymaxrelu (fn in MAXACT_FNS) at nb bits in STORE_I4 / STORE_I8, scaled by the maximum
+    whose bits qnn_maxact_max_f32 left in `workspace` (int32[4] on the device).  y: a float32 tensor shaped like x (x itself
+    is allowed) that also receives the values qnn_maxact_apply_f32 would write."""
+    x = require_cuda(x, "maxact_pack")
+    pixels = x.numel() // channels
+    if y is not None and (y.dtype != torch.float32 or not y.is_contiguous() or y.numel() != x.numel() or y.device != x.device):
+        raise QnnError("maxact_pack: `y` must be a contiguous float32 tensor of x's size on %s" % (x.device,))
+    out = torch.empty((pixels, words(store, channels)), dtype=torch.int32, device=x.device)
+    check(load().qnn_maxact_pack_f32(ptr(x), ptr(out), ptr(y), pixels, channels, fn, nb, store, ptr(workspace), stream_ptr()),
+          "qnn_maxact_pack_f32")
+    return out
+
+
+def _check_scaled(rc, what):
+    """Status of a scaled entry: its own refusals (each names the entry) as QnnUnsupported, the rest through check()."""
+    if rc == QNN_EUNSUPPORTED:
+        raise QnnUnsupported("%s: %s" % (what, load().qnn_last_error().decode(errors="replace")))
+    check(rc, what)
 
 
 def unpack(p, pixels, channels, store, nb):
@@ -582,10 +611,11 @@ def faithful_trick(klm, promotion="nep50"):
 
 def conv2d(w, x, x_store, x_bits, N, H, W, bn_inv=None, bn_shift=None, fn=FN_NONE, act_bits=0,
            pool=1, out_store=STORE_F32, res=None, res_store=STORE_F32, res_bits=0, post_scale=1.0, out=None, trick=None,
-           fold=None, domain_flag=None, proj=None):
+           fold=None, domain_flag=None, proj=None, x_scale=None):
     """Run qnn_conv2d_forward; x is a float32 NHWC tensor, a uint8 NHWC tensor or an int32 packed tensor.
     Returns (y, Hp, Wp): y float32 (N,Hp,Wp,cout) or int32 (N*Hp*Wp, words); `out` = a tensor of that shape to write
-    into instead of a fresh one.  proj: see make_epilogue (raises QnnUnsupported where no kernel computes it)."""
+    into instead of a fresh one.  proj: see make_epilogue (raises QnnUnsupported where no kernel computes it).
+    x_scale: the workspace word of maxact_pack whose codes x holds -> qnn_conv2d_forward_scaled (qnn_abi_scaled.h)."""
     cout = w.shape[3]
     Ho, Wo = _stored_hw("conv2d", w, H, W, pool)
     if out_store == STORE_F32:
@@ -600,6 +630,10 @@ def conv2d(w, x, x_store, x_bits, N, H, W, bn_inv=None, bn_shift=None, fn=FN_NON
         y = out
     epi = make_epilogue(bn_inv, bn_shift, fn, act_bits, pool, out_store, res, res_store, res_bits, post_scale, trick, fold,
                         domain_flag, proj=proj)
+    if x_scale is not None:
+        _check_scaled(load().qnn_conv2d_forward_scaled(w.handle, ptr(x), x_store, x_bits, N, H, W, ctypes.byref(epi),
+                                                       ptr(x_scale), ptr(y), stream_ptr()), "qnn_conv2d_forward_scaled")
+        return y, Ho, Wo
     rc = load().qnn_conv2d_forward(w.handle, ptr(x), _first_store(x_store), x_bits, N, H, W, ctypes.byref(epi),
                                    ptr(y), stream_ptr())
     if proj is not None and rc == QNN_EUNSUPPORTED:
@@ -697,7 +731,8 @@ def conv2d_f32in(w, x, in_fn, in_bits, bn_inv=None, bn_shift=None, fn=FN_NONE, a
 
 
 def dense(w, x, x_store, x_bits, N, bn_inv=None, bn_shift=None, fn=FN_NONE, act_bits=0,
-          out_store=STORE_F32, out=None):
+          out_store=STORE_F32, out=None, x_scale=None):
+    """Run qnn_dense_forward; x_scale: as in conv2d -> qnn_dense_forward_scaled."""
     cout = w.shape[3]
     if out_store == STORE_F32:
         shape, dt = (N, cout), torch.float32
@@ -710,6 +745,10 @@ def dense(w, x, x_store, x_bits, N, bn_inv=None, bn_shift=None, fn=FN_NONE, act_
             raise QnnError("dense: `out` must be a contiguous %s tensor of shape %s on %s" % (dt, shape, x.device))
         y = out
     epi = make_epilogue(bn_inv, bn_shift, fn, act_bits, 1, out_store)
+    if x_scale is not None:
+        _check_scaled(load().qnn_dense_forward_scaled(w.handle, ptr(x), x_store, x_bits, N, ctypes.byref(epi), ptr(x_scale),
+                                                      ptr(y), stream_ptr()), "qnn_dense_forward_scaled")
+        return y
     check(load().qnn_dense_forward(w.handle, ptr(x), x_store, x_bits, N, ctypes.byref(epi), ptr(y),
                                    stream_ptr()), "qnn_dense_forward")
     return y

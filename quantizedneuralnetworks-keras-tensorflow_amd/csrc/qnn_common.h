@@ -9,6 +9,7 @@
 #include "qnn_abi_dilation.h"
 #include "qnn_abi_qact.h"
 #include "qnn_abi_maxact.h"
+#include "qnn_abi_scaled.h"
 
 #define QNN_WAVE 64
 
@@ -161,6 +162,10 @@ struct ConvCall {
     void* y;
     hipStream_t s;
     bool dense;
+    // qnn_abi_scaled.h: the 16-byte workspace word of the batch-scaled activation that left the packed codes in x, or nullptr
+    // = an ordinary call.  Host side only: it reaches a kernel as a trailing argument of the routes that list CAP_XSCALE, so
+    // no kernel's EpiArgs block (and no ordinary call's code) changes.
+    const uint32_t* x_scale;
 };
 // the matrix-pipe routes: 0 = launched (and `name` set), 1 = declined.  qnn_route_first_f32 and qnn_route_gemm are in
 // qnn_mfma.hip, qnn_route_strip is in qnn_route_strip.hip.
@@ -267,11 +272,21 @@ __device__ __forceinline__ bool qnn_maxact_scales(uint32_t mbits, int nb, float*
 // The per-value arithmetic: clip(rint(x s_in), lo, m - 1) s_out, on L(x) = (x >= 0 ? x : 0.1f x) with lo = -m for the
 // leaky form, lo = 0 otherwise.  Both multiplications are exponent shifts; `+ 0` turns a -0 code into the +0 of the
 // reference's round_through.
-__device__ __forceinline__ float qnn_maxact(int fn, float x, float m, float s_in, float s_out) {
+__device__ __forceinline__ float qnn_maxact_code_f(int fn, float x, float m, float s_in) {
     if (fn == QNN_FN_QUANTIZED_LEAKYMAXRELU) x = x >= 0.0f ? x : __fmul_rn(0.1f, x);
     const float lo = fn == QNN_FN_QUANTIZED_LEAKYMAXRELU ? -m : 0.0f;
     const float code = fminf(fmaxf(rintf(__fmul_rn(x, s_in)), lo), __fsub_rn(m, 1.0f));
-    return __fmul_rn(__fadd_rn(code, 0.0f), s_out);
+    return __fadd_rn(code, 0.0f);
+}
+__device__ __forceinline__ float qnn_maxact(int fn, float x, float m, float s_in, float s_out) {
+    return __fmul_rn(qnn_maxact_code_f(fn, x, m, s_in), s_out);
+}
+// Output scale of a scaled consumer (qnn_abi_scaled.h): scale * P with P = 2^e from the same word and the same helper as
+// the activation itself (qnn_maxact_scales at nb = 1: s_out = P), one uniform load and integer exponent arithmetic.  Both
+// factors are powers of two, so the product is exact; a word outside the exact range gives quiet NaN.
+__device__ __forceinline__ float qnn_scaled_scale(float scale, const uint32_t* __restrict__ word) {
+    float s_in = 0.0f, p = 0.0f;
+    return qnn_maxact_scales(*word, 1, &s_in, &p) ? __fmul_rn(scale, p) : __uint_as_float(0x7FC00000u);
 }
 
 // Keras LeakyReLU() at its default alpha = float32(0.3): one rounding, as torch.where(v >= 0, v, v * 0.3) computes it

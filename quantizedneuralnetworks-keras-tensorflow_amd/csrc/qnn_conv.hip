@@ -232,12 +232,15 @@ __device__ float conv_point(const ConvGeom& g, int x_store, const void* __restri
 }
 
 // one thread per stored output slot: (stored pixel, cout) for float32 outputs,
-// (stored pixel, word) for packed outputs
+// (stored pixel, word) for packed outputs.  XSC: a scaled call (qnn_abi_scaled.h), the output scale is e.scale * P with P
+// from the word `xsc`; XSC = false is the kernel as it was (xsc is not read).
+template <bool XSC>
 __global__ __launch_bounds__(kBlock) void k_conv_generic(ConvGeom g, EpiArgs e, int x_store,
                                                          const void* __restrict__ x,
                                                          const uint32_t* __restrict__ wp,
                                                          const float* __restrict__ wq,
-                                                         void* __restrict__ y) {
+                                                         void* __restrict__ y, const uint32_t* __restrict__ xsc) {
+    const float scale = XSC ? qnn_scaled_scale(e.scale, xsc) : e.scale;
     const int slots = e.ocw;
     const size_t total = (size_t)g.N * g.Hp * g.Wp * slots;
     const int pw = qnn_per_word(e.out_store);
@@ -259,7 +262,7 @@ __global__ __launch_bounds__(kBlock) void k_conv_generic(ConvGeom g, EpiArgs e, 
                 float best = 0.0f;
                 for (int s = 0; s < g.pool * g.pool; ++s) {
                     const int oy = py * g.pool + s / g.pool, ox = px * g.pool + s % g.pool;
-                    const float t = __fmaf_rn(conv_point(g, x_store, x, wp, wq, e.scale, n, oy, ox, c), af.A, af.B);
+                    const float t = __fmaf_rn(conv_point(g, x_store, x, wp, wq, scale, n, oy, ox, c), af.A, af.B);
                     const float v = qnn_u8_value(t, e);          // code (quantized_tanh), +-1 (binary_tanh) or t
                     best = (s == 0) ? v : fmaxf(best, v);
                 }
@@ -278,7 +281,7 @@ __global__ __launch_bounds__(kBlock) void k_conv_generic(ConvGeom g, EpiArgs e, 
             float best = 0.0f;
             for (int s = 0; s < g.pool * g.pool; ++s) {
                 const int oy = py * g.pool + s / g.pool, ox = px * g.pool + s % g.pool;
-                float v = conv_point(g, x_store, x, wp, wq, e.scale, n, oy, ox, c);
+                float v = conv_point(g, x_store, x, wp, wq, scale, n, oy, ox, c);
                 v = qnn_epi_value(v, c, e);
                 v = qnn_epi_residual(v, (long)q, c, e);
                 if (e.fn == QNN_FN_BINARY_TANH) v = qnn_binary_tanh(v);
@@ -297,7 +300,7 @@ __global__ __launch_bounds__(kBlock) void k_conv_generic(ConvGeom g, EpiArgs e, 
                 int best = 0;
                 for (int s = 0; s < g.pool * g.pool; ++s) {
                     const int oy = py * g.pool + s / g.pool, ox = px * g.pool + s % g.pool;
-                    float v = conv_point(g, x_store, x, wp, wq, e.scale, n, oy, ox, c);
+                    float v = conv_point(g, x_store, x, wp, wq, scale, n, oy, ox, c);
                     v = qnn_epi_value(v, c, e);
                     v = qnn_epi_residual(v, (long)q, c, e);
                     const int code = qnn_epi_code(v, e);
@@ -579,11 +582,12 @@ __global__ __launch_bounds__(kBlock) void k_conv_ps(ConvGeom g, EpiArgs e,
 // UP unit-slots of one image sit in adjacent lanes so the activation words are a
 // broadcast load; weights (<= a few KB) stay in L1.  float32 output, full epilogue.
 // ---------------------------------------------------------------------------
-template <int XS, int UP>
+// XSC (both kernels): a scaled call (qnn_abi_scaled.h), e.scale * P with P from the word `xsc`; false = as it was.
+template <int XS, int UP, bool XSC = false>
 __global__ __launch_bounds__(kBlock) void k_dense_packed(const uint32_t* __restrict__ x,
                                                          const uint32_t* __restrict__ wp, EpiArgs e,
                                                          float* __restrict__ y, int N, int cin,
-                                                         int kwords, int units) {
+                                                         int kwords, int units, const uint32_t* __restrict__ xsc) {
     constexpr int IPB = kBlock / UP;                 // images per block
     const int u = threadIdx.x % UP;
     const int img = blockIdx.x * IPB + threadIdx.x / UP;
@@ -611,7 +615,7 @@ __global__ __launch_bounds__(kBlock) void k_dense_packed(const uint32_t* __restr
         for (; k < kwords; ++k) acc = qnn_dot<XS>(xr[k], wr[k], acc);
     }
     if constexpr (XS == QNN_STORE_BIN) acc = cin - 2 * acc;   // pad bits are 0 in both operands
-    float v = __fmul_rn((float)acc, e.scale);
+    float v = __fmul_rn((float)acc, XSC ? qnn_scaled_scale(e.scale, xsc) : e.scale);
     v = qnn_epi_value(v, u, e);
     if (e.fn == QNN_FN_BINARY_TANH) v = qnn_binary_tanh(v);
     else if (qnn_is_qact(e.fn)) v = qnn_qact(e.fn, v, e.act_m);
@@ -621,11 +625,11 @@ __global__ __launch_bounds__(kBlock) void k_dense_packed(const uint32_t* __restr
 // The same layer with the K loop of one (image, unit) cut over KP adjacent lanes (classifier heads: <= 16 units, so
 // one thread per (image, unit) leaves a 4096-image batch with 256 workgroups of long serial loops: 9.8 us for the
 // 4096 x 1024 -> 10 head of the CIFAR VGG against 2-3 us of memory time).  Integer partial sums: any order is exact.
-template <int XS, int UP, int KP>
+template <int XS, int UP, int KP, bool XSC = false>
 __global__ __launch_bounds__(kBlock) void k_dense_packed_split(const uint32_t* __restrict__ x,
                                                                const uint32_t* __restrict__ wp, EpiArgs e,
                                                                float* __restrict__ y, int N, int cin,
-                                                               int kwords, int units) {
+                                                               int kwords, int units, const uint32_t* __restrict__ xsc) {
     constexpr int IPB = kBlock / (UP * KP);          // images per block
     const int kp = threadIdx.x % KP;
     const int u = (threadIdx.x / KP) % UP;
@@ -651,29 +655,30 @@ __global__ __launch_bounds__(kBlock) void k_dense_packed_split(const uint32_t* _
     for (int d = 1; d < KP; d <<= 1) acc += __shfl_xor(acc, d);     // every lane of the group takes part
     if (!live || kp != 0) return;
     if constexpr (XS == QNN_STORE_BIN) acc = cin - 2 * acc;   // pad bits are 0 in both operands
-    float v = __fmul_rn((float)acc, e.scale);
+    float v = __fmul_rn((float)acc, XSC ? qnn_scaled_scale(e.scale, xsc) : e.scale);
     v = qnn_epi_value(v, u, e);
     if (e.fn == QNN_FN_BINARY_TANH) v = qnn_binary_tanh(v);
     else if (qnn_is_qact(e.fn)) v = qnn_qact(e.fn, v, e.act_m);
     y[(size_t)img * units + u] = v;
 }
 
-template <int XS>
-int launch_dense(const void* x, const qnn_weights* w, const EpiArgs& e, void* y, int N, hipStream_t s) {
+template <int XS, bool XSC = false>
+int launch_dense(const void* x, const qnn_weights* w, const EpiArgs& e, void* y, int N, hipStream_t s,
+                 const uint32_t* xsc = nullptr) {
     const int units = w->cout;
     const uint32_t* xu = (const uint32_t*)x;
     if (units <= 16 && (w->kwords % 16) == 0) {
         constexpr int UP = 16, KP = 4;
         const int ipb = kBlock / (UP * KP);
-        hipLaunchKernelGGL((k_dense_packed_split<XS, UP, KP>), dim3((N + ipb - 1) / ipb), dim3(kBlock), 0, s, xu,
-                           w->d_packed, e, (float*)y, N, w->cin, w->kwords, units);
+        hipLaunchKernelGGL((k_dense_packed_split<XS, UP, KP, XSC>), dim3((N + ipb - 1) / ipb), dim3(kBlock), 0, s, xu,
+                           w->d_packed, e, (float*)y, N, w->cin, w->kwords, units, xsc);
         return 0;
     }
 #define DENSE_CASE(UP)                                                                           \
     if (units <= UP) {                                                                           \
         const int ipb = kBlock / UP;                                                             \
-        hipLaunchKernelGGL((k_dense_packed<XS, UP>), dim3((N + ipb - 1) / ipb), dim3(kBlock), 0, s, xu, \
-                           w->d_packed, e, (float*)y, N, w->cin, w->kwords, units);              \
+        hipLaunchKernelGGL((k_dense_packed<XS, UP, XSC>), dim3((N + ipb - 1) / ipb), dim3(kBlock), 0, s, xu, \
+                           w->d_packed, e, (float*)y, N, w->cin, w->kwords, units, xsc);         \
         return 0;                                                                                \
     }
     DENSE_CASE(16)
@@ -1319,6 +1324,7 @@ int conv_describe(ConvCall* c, const qnn_weights* w, const void* x, int x_store,
         return QNN_EINVAL;
     }
     c->w = w; c->x = x; c->x_store = x_store; c->y = y; c->s = (hipStream_t)stream; c->dense = dense;
+    c->x_scale = nullptr;
     return QNN_OK;
 }
 
@@ -1334,6 +1340,11 @@ int route_dense(const ConvCall& c, char* name, size_t name_len) {
         return 0;
     }
     if ((c.w->kwords % 4) != 0) return 1;
+    if (c.x_scale) {                     // a scaled call (qnn_abi_scaled.h): I4 / I8 codes, the entry has checked
+        snprintf(name, name_len, "dense_%s_scaled", xs == QNN_STORE_I4 ? "i4" : "i8");
+        return xs == QNN_STORE_I4 ? launch_dense<QNN_STORE_I4, true>(c.x, c.w, c.e, c.y, c.g.N, c.s, c.x_scale)
+                                  : launch_dense<QNN_STORE_I8, true>(c.x, c.w, c.e, c.y, c.g.N, c.s, c.x_scale);
+    }
     snprintf(name, name_len, "dense_%s", xs == QNN_STORE_BIN ? "bin" : xs == QNN_STORE_T2 ? "t2" : xs == QNN_STORE_I4 ? "i4" : "i8");
     return xs == QNN_STORE_BIN  ? launch_dense<QNN_STORE_BIN>(c.x, c.w, c.e, c.y, c.g.N, c.s)
            : xs == QNN_STORE_T2 ? launch_dense<QNN_STORE_T2>(c.x, c.w, c.e, c.y, c.g.N, c.s)
@@ -1381,8 +1392,14 @@ int route_generic(const ConvCall& c, char* name, size_t name_len) {
     const size_t total = (size_t)c.g.N * c.g.Hp * c.g.Wp * c.e.ocw;
     size_t blocks = (total + kBlock - 1) / kBlock;
     if (blocks > 65535u * 16u) blocks = 65535u * 16u;
-    hipLaunchKernelGGL(k_conv_generic, dim3((unsigned)blocks), dim3(kBlock), 0, c.s, c.g, c.e, c.x_store, c.x,
-                       c.w->d_packed, c.w->d_wq, c.y);
+    if (c.x_scale) {                     // a scaled call (qnn_abi_scaled.h)
+        hipLaunchKernelGGL(k_conv_generic<true>, dim3((unsigned)blocks), dim3(kBlock), 0, c.s, c.g, c.e, c.x_store, c.x,
+                           c.w->d_packed, c.w->d_wq, c.y, c.x_scale);
+        snprintf(name, name_len, "generic_scaled");
+        return 0;
+    }
+    hipLaunchKernelGGL(k_conv_generic<false>, dim3((unsigned)blocks), dim3(kBlock), 0, c.s, c.g, c.e, c.x_store, c.x,
+                       c.w->d_packed, c.w->d_wq, c.y, (const uint32_t*)nullptr);
     snprintf(name, name_len, c.x_store == QNN_STORE_U8 ? "generic_u8" : "generic");
     return 0;
 }
@@ -1402,6 +1419,10 @@ enum : unsigned {
                         // only: check_epilogue refuses such a call first, so today nothing reaches the dispatch with it
                         // (nor the QNN_REFUSE_MAXACT in conv_run); a later entry that forgot the check finds no kernel
                         // instead of quantized_tanh's
+    CAP_XSCALE = 512,   // a scaled call (qnn_abi_scaled.h, ConvCall.x_scale): the kernel multiplies its output scale by the P
+                        // of the device word.  Listed by the routes whose kernels have the preamble: route_dense,
+                        // qnn_route_gemm (its 256 x 128 / 256 x 256 tiles; 64-filter layers decline) and route_generic.
+                        // Not by qnn_route_strip: its kernels store packed codes only, and a scaled call's output is float32
 };
 
 struct Route {
@@ -1412,18 +1433,18 @@ struct Route {
 
 // in order of preference; k_conv_generic last takes every call without a projection
 const Route kRoutes[] = {
-    {route_dense, CAP_DENSE | CAP_QACT, false},
+    {route_dense, CAP_DENSE | CAP_QACT | CAP_XSCALE, false},
     {route_pw, CAP_CONV, false},
     {route_first_u8, CAP_CONV, true},
     {route_stem, CAP_CONV, true},
     {qnn_route_first_f32, CAP_CONV, true},
     {qnn_route_strip, CAP_CONV | CAP_RES | CAP_PROJ | CAP_QACT, true},      // (its un-folded int4 strip kernels; the rest of the family declines)
-    {qnn_route_gemm, CAP_CONV | CAP_RES, true},
+    {qnn_route_gemm, CAP_CONV | CAP_RES | CAP_XSCALE, true},
     {route_xnor_pk, CAP_CONV, false},
     {route_ps, CAP_CONV | CAP_DENSE | CAP_RES | CAP_TRICK, false},
     {route_f32act, CAP_CONV | CAP_RES | CAP_LEAKY, true},
     {qnn_route_strip_dil, CAP_CONV | CAP_RES | CAP_DIL, true},
-    {route_generic, CAP_CONV | CAP_DENSE | CAP_RES | CAP_TRICK | CAP_LEAKY | CAP_DIL | CAP_QACT, false},
+    {route_generic, CAP_CONV | CAP_DENSE | CAP_RES | CAP_TRICK | CAP_LEAKY | CAP_DIL | CAP_QACT | CAP_XSCALE, false},
 };
 
 // the one feature check: may route (caps, mfma) take call c?  (CAP_DIL is the guard of the dilated calls: the routes
@@ -1434,7 +1455,7 @@ bool route_takes(unsigned caps, bool mfma, const ConvCall& c) {
                           (e.trick_s != 0.0f ? CAP_TRICK : 0u) | (e.fn == QNN_FN_LEAKY_RELU ? CAP_LEAKY : 0u) |
                           (c.g.dil_h != 1 || c.g.dil_w != 1 ? CAP_DIL : 0u) |
                           (e.fn == QNN_FN_QUANTIZED_RELU || e.fn == QNN_FN_QUANTIZED_LEAKYRELU ? CAP_QACT : 0u) |
-                          (qnn_is_maxact(e.fn) ? CAP_MAXACT : 0u);
+                          (qnn_is_maxact(e.fn) ? CAP_MAXACT : 0u) | (c.x_scale ? CAP_XSCALE : 0u);
     // a projection call ignores the preference: no VALU kernel computes the shortcut
     return (uses & ~caps) == 0 && !(mfma && !e.proj_x && qnn_conv_impl_pref() == 1);
 }
@@ -1463,6 +1484,32 @@ int conv_forward(const qnn_weights* w, const void* x, int x_store, int x_bits, i
     ConvCall c;
     const int rc = conv_describe(&c, w, x, x_store, x_bits, N, H, W, epi, y, stream, dense);
     return rc != QNN_OK ? rc : conv_run(c);
+}
+
+// The two entries of qnn_abi_scaled.h: their own requirements (each message names the entry), then the ordinary call
+// with the word attached, which only the routes listing CAP_XSCALE take.
+int conv_forward_scaled(const char* who, const qnn_weights* w, const void* x, int x_store, int x_bits, int N, int H, int W,
+                        const qnn_epilogue_t* epi, const void* x_scale16, void* y, void* stream, bool dense) {
+    QNN_REQUIRE(w && x && y && epi, QNN_EINVAL, "%s: null pointer", who);
+    QNN_REQUIRE(x_scale16, QNN_EINVAL, "%s: x_scale16 is NULL (the 16-byte workspace of qnn_maxact_pack_f32)", who);
+    QNN_REQUIRE(x_store == QNN_STORE_I4 || x_store == QNN_STORE_I8, QNN_EUNSUPPORTED,
+                "%s: x_store=%d; scaled codes are QNN_STORE_I4 or QNN_STORE_I8 (qnn_maxact_pack_f32)", who, x_store);
+    QNN_REQUIRE(epi->out_store == QNN_STORE_F32, QNN_EUNSUPPORTED,
+                "%s: out_store=%d; the output of a scaled call is float32 (no fixed-grid activation can follow a value "
+                "that carries the batch scale)", who, epi->out_store);
+    QNN_REQUIRE(!epi->fold, QNN_EUNSUPPORTED, "%s: no folded epilogue on a scaled call", who);
+    QNN_REQUIRE(!epi->proj, QNN_EUNSUPPORTED, "%s: no in-launch projection shortcut on a scaled call", who);
+    QNN_REQUIRE(epi->pool == 1, QNN_EUNSUPPORTED, "%s: pool=%d; a scaled call does not pool", who, epi->pool);
+    ConvCall c;
+    const int rc = conv_describe(&c, w, x, x_store, x_bits, N, H, W, epi, y, stream, dense);
+    if (rc != QNN_OK) return rc;
+    // the contract's "exact integer sum" as a float32: every partial sum must fit 24 bits (the bound of the header, which is
+    // also where the float32 route is exact); beyond it the int32 -> float32 conversion would round, as on the U8 entry
+    QNN_REQUIRE((double)w->kh * w->kw * w->cin * (double)(1 << (x_bits - 1)) * (double)(1 << w->wshift) <= 16777216.0,
+                QNN_EUNSUPPORTED, "%s: sums of this layer (K=%d, x_bits=%d, weight shift %d) may exceed 2^24: keep it on the "
+                "float32 route", who, w->kh * w->kw * w->cin, x_bits, w->wshift);
+    c.x_scale = (const uint32_t*)x_scale16;
+    return conv_run(c);
 }
 
 }  // namespace
@@ -1745,4 +1792,17 @@ extern "C" int qnn_dense_forward(const qnn_weights_t* w, const void* x, int x_st
     QNN_REQUIRE(w->kh == 1 && w->kw == 1, QNN_EINVAL,
                 "qnn_dense_forward: weights were prepacked as a %dx%d conv", w->kh, w->kw);
     return conv_forward(w, x, x_store, x_bits, N, 1, 1, epi, y, stream, true);
+}
+
+extern "C" int qnn_conv2d_forward_scaled(const qnn_weights_t* w, const void* x, int x_store, int x_bits, int N, int H, int W,
+                                         const qnn_epilogue_t* epi, const void* x_scale16, void* y, void* stream) {
+    return conv_forward_scaled("qnn_conv2d_forward_scaled", w, x, x_store, x_bits, N, H, W, epi, x_scale16, y, stream, false);
+}
+
+extern "C" int qnn_dense_forward_scaled(const qnn_weights_t* w, const void* x, int x_store, int x_bits, int N,
+                                        const qnn_epilogue_t* epi, const void* x_scale16, void* y, void* stream) {
+    QNN_REQUIRE(w, QNN_EINVAL, "qnn_dense_forward_scaled: null weights");
+    QNN_REQUIRE(w->kh == 1 && w->kw == 1, QNN_EINVAL,
+                "qnn_dense_forward_scaled: weights were prepacked as a %dx%d conv", w->kh, w->kw);
+    return conv_forward_scaled("qnn_dense_forward_scaled", w, x, x_store, x_bits, N, 1, 1, epi, x_scale16, y, stream, true);
 }

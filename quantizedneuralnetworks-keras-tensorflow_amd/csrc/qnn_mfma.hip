@@ -690,6 +690,15 @@ __device__ __forceinline__ void conv_mfma16_body(const MfmaGeom& mg, const EpiAr
     }
 }
 
+// The LDS-DMA form of the body, named at ONE place: the compiler accepts conv_mfma16_body<..., DMA = true> from a single call
+// site only (a second kernel calling the same specialisation is rejected in the host pass with "substitution failure"; both
+// k_conv_mfma16_dma and its scaled sibling therefore come through here).  Inlined: k_conv_mfma16_dma compiles to what it
+// did (profiles/scaled/README.md).
+template <int XS, int WM, int WN, int OUT, int POOL>
+__device__ __forceinline__ void conv_mfma16_dma_once(const MfmaGeom& mg, const EpiArgs& e, const uint8_t* __restrict__ x,
+                                                     const uint8_t* __restrict__ wq8, void* __restrict__ y) {
+    conv_mfma16_body<XS, WM, WN, OUT, POOL, true>(mg, e, x, wq8, y);
+}
 template <int XS, int WM, int WN, int OUT, int POOL>
 __global__ __launch_bounds__(64 * WM * WN, (WM * WN >= 16 ? 4 : WM * WN >= 8 ? 2 : 3)) void k_conv_mfma16(MfmaGeom mg, EpiArgs e,
                                                            const uint8_t* __restrict__ x,
@@ -700,7 +709,33 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN >= 16 ? 4 : WM * WN >= 8 ? 2
 template <int XS, int WM, int WN, int OUT, int POOL>
 __global__ __launch_bounds__(64 * WM * WN, 4) void k_conv_mfma16_dma(MfmaGeom mg, EpiArgs e, const uint8_t* __restrict__ x,
                                                                      const uint8_t* __restrict__ wq8, void* __restrict__ y) {
-    conv_mfma16_body<XS, WM, WN, OUT, POOL, true>(mg, e, x, wq8, y);
+    conv_mfma16_dma_once<XS, WM, WN, OUT, POOL>(mg, e, x, wq8, y);
+}
+
+// The scaled form of k_conv_mfma16 / k_conv_mfma16_dma (include/qnn_abi_scaled.h): float32 output, no pooling; the output scale is
+// e.scale * P with P from the device word `xsc` (qnn_scaled_scale: one uniform load and exponent arithmetic per block), the
+// body is the same.  Kernels of their own, so that the ordinary two are what they were, argument block included.
+template <int XS, int WN>
+__global__ __launch_bounds__(64 * 4 * WN, (XS == QNN_STORE_I8 || WN >= 4 ? 4 : 2)) void k_conv_mfma16_scaled(
+    MfmaGeom mg, EpiArgs e, const uint8_t* __restrict__ x, const uint8_t* __restrict__ wq8, void* __restrict__ y,
+    const uint32_t* __restrict__ xsc) {
+    e.scale = qnn_scaled_scale(e.scale, xsc);
+    if constexpr (XS == QNN_STORE_I8) conv_mfma16_dma_once<XS, 4, WN, QNN_STORE_F32, 1>(mg, e, x, wq8, y);
+    else conv_mfma16_body<XS, 4, WN, QNN_STORE_F32, 1, false>(mg, e, x, wq8, y);
+}
+
+template <int XS, int WN>
+int launch_tile_scaled(const MfmaGeom& mg, const EpiArgs& e, const void* x, const uint8_t* w, void* y, hipStream_t s,
+                       const uint32_t* xsc) {
+    constexpr int BM = 256, BN = 64 * WN;
+    const dim3 grid((unsigned)((mg.total_q + BM - 1) / BM), (unsigned)(mg.g.cout / BN)), block(64 * 4 * WN);
+    size_t lds = 2 * (BM + BN) * 64;
+    if constexpr (XS == QNN_STORE_I8) {               // three LDS buffers, as launch_tile sets them for k_conv_mfma16_dma
+        lds = (size_t)QNN_DMA_NBUF * (BM + BN) * 64;
+        (void)hipFuncSetAttribute((const void*)k_conv_mfma16_scaled<XS, WN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    }
+    hipLaunchKernelGGL((k_conv_mfma16_scaled<XS, WN>), grid, block, lds, s, mg, e, (const uint8_t*)x, w, y, xsc);
+    return 0;
 }
 
 // int8 weight image for the I4 path: every packed word (8 nibbles) -> two words of
@@ -848,6 +883,20 @@ int qnn_route_gemm(const ConvCall& c, char* name, size_t name_len) {
     if (x_store == QNN_STORE_I4) e2.scale = e.scale * (1.0f / 256.0f);   // both operands carry *16
     // tile shape: waves along M x waves along N (64x64 per wave); measured: 256x256 > 128x256 > 256x128 > 128x128
     const int wn_ = (g.cout % 256) == 0 ? 4 : (g.cout % 128) == 0 ? 2 : 1;
+    if (c.x_scale) {
+        // a scaled call (qnn_abi_scaled.h: float32 output, no pooling, no fold; the entry has checked): the 256 x 128 and
+        // 256 x 256 tiles, whose body is a device function two more kernels can share.  64-filter layers (k_conv_mfma at
+        // 256 x 64, areg, wres) carry their whole body inside the __global__ function; a scaled form of those needs the
+        // body moved out first, which changes how the ordinary kernels compile (profiles/strip_chain/README.md), so such a
+        // call is declined here and runs on k_conv_generic.  A float32 residual: none of the tile kernels has the merge.
+        if (wn_ < 2 || e.res || e.out_store != QNN_STORE_F32 || g.pool != 1 || mg.total_q >= 2000000000L) return 1;
+        snprintf(name, name_len, "mfma_%s_256x%d_scaled", x_store == QNN_STORE_I8 ? "i8" : "i4", 64 * wn_);
+        if (x_store == QNN_STORE_I8)
+            return wn_ == 4 ? launch_tile_scaled<QNN_STORE_I8, 4>(mg, e2, x, w->d_mfma, y, s, c.x_scale)
+                            : launch_tile_scaled<QNN_STORE_I8, 2>(mg, e2, x, w->d_mfma, y, s, c.x_scale);
+        return wn_ == 4 ? launch_tile_scaled<QNN_STORE_I4, 4>(mg, e2, x, w->d_mfma, y, s, c.x_scale)
+                        : launch_tile_scaled<QNN_STORE_I4, 2>(mg, e2, x, w->d_mfma, y, s, c.x_scale);
+    }
     const long rows_ = mg.total_q * (g.pool == 2 ? 4 : 1);
     // one 64-filter slice, 3x3, Cin <= 128: operands straight into registers
     const bool areg = g.cout == 64 && g.kh == 3 && g.kw == 3 && mg.kc <= 2 && rows_ < 2000000000L;

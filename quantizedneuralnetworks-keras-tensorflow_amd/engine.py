@@ -91,9 +91,35 @@ _NEW_QUANT_FNS = (_abi.FN_QUANTIZED_RELU, _abi.FN_QUANTIZED_LEAKYRELU)
 _MAX_ACTS = ("quantized_maxrelu", "quantized_leakymaxrelu")
 
 
+def scaled_route_exact(K, nb, wbits):
+    """The exactness rule of the scaled route (include/qnn_abi_scaled.h).  A batch-scaled activation's consumer
+    may read packed codes plus the device-resident scale instead of the float32 tensor only where the two routes give the
+    same bits: the float32 route's fmaf chain over K products of an nb-bit activation code and a wbits-bit weight code
+    (wbits = 1 for binary and ternary weights) is exact, and so equal to the integer sum, when every partial sum fits 24
+    bits: K * 2^(nb-1) * 2^(wbits-1) <= 2^24.  4/4 networks qualify everywhere, 8/8 up to K = 1024."""
+    return int(K) * 2 ** (int(nb) - 1) * 2 ** (int(wbits) - 1) <= 2 ** 24
+
+
+def _scaled_route_pays(op, store):
+    """False for the one family of consumers the scaled route would slow down (profiles/scaled/README.md, table b): a
+    convolution the float32 route runs on the f32 matrix pipe (k_conv_f32act: 16 / 32 / 64 input channels, 3x3 at stride 1
+    or 2 or 1x1 at stride 2, 'same', up to 256 filters in multiples of 16, undilated -- f32act_shape of csrc/qnn_f32act.hip)
+    while its scaled call would find no matrix-pipe kernel (qnn_route_gemm's scaled tiles need 64 input channels and a
+    multiple of 128 filters) and fall to k_conv_generic.  Such a consumer keeps the float32 tensor."""
+    if op["op"] != "conv":
+        return True
+    kh, kw, cin, cout = op["kernel"].shape
+    stride = tuple(op.get("strides", (1, 1)))[0]
+    f32act = cin in (16, 32, 64) and cout % 16 == 0 and cout <= 256 and op.get("padding", "same") == "same" and kh == kw and \
+        ((kh == 3 and stride in (1, 2)) or (kh == 1 and stride == 2)) and _dilation(op) == (1, 1)
+    tiles = cin % 64 == 0 and cout % 128 == 0 and store in (_abi.STORE_I4, _abi.STORE_I8) and kh * kw <= 9
+    return tiles or not f32act
+
+
 def _refuse_max_acts(spec, who):
     """The packed engines carry codes on the fixed grid k / 2^(nb-1); an activation whose scale is the batch maximum has
-    no such codes (packed codes plus a device-resident scale are not built): GraphModel runs such a spec."""
+    no such codes (packed codes plus a device-resident scale exist in GraphModel only, `scaled_codes`): GraphModel runs
+    such a spec."""
     for op in spec:
         if op["op"] == "act" and op["fn"] in _MAX_ACTS:
             raise _abi.NotFusable("%s: activation %r scales by the maximum of the whole batch tensor; its values are not on "
@@ -732,15 +758,122 @@ class _Virtual:
         return self._mat
 
 
+class _Scaled:
+    """A batch-scaled activation (quantized_maxrelu / quantized_leakymaxrelu at nb <= 8) carried as packed codes plus the
+    device-resident scale (include/qnn_abi_scaled.h): `packs` store -> int32 words, `ws` the 16-byte workspace whose word
+    every scaled consumer reads (this object keeps it alive, and nothing writes it again: each activation has its own),
+    `f32` the float32 tensor of the same pass for the consumers that need one (None: formed on demand from `pre`)."""
+
+    def __init__(self, pre, fn, nb, ws, packs, f32, shape):
+        self.pre, self.fn, self.nb, self.ws, self.packs, self.f32, self.shape = pre, fn, nb, ws, packs, f32, tuple(shape)
+        self.parent = None                   # flat(): the NHWC tensor this one is a view of
+
+    def materialize(self):
+        if self.f32 is None and self.parent is not None:     # one float32 tensor serves both shapes
+            self.f32 = self.parent.materialize().reshape(self.shape)
+        if self.f32 is None:
+            self.f32 = torch.empty_like(self.pre)
+            _abi.check(_abi.load().qnn_maxact_apply_f32(_abi.ptr(self.pre), _abi.ptr(self.f32), self.pre.numel(), self.fn,
+                                                        self.nb, _abi.ptr(self.ws), _abi.stream_ptr()), "qnn_maxact_apply_f32")
+        return self.f32
+
+    def flat(self):
+        """Behind a Flatten: the same words read as (N, H * W * words) -- whole words per pixel only (_scaled_flat_ok)."""
+        n = self.shape[0]
+        v = _Scaled(self.pre.reshape(n, -1), self.fn, self.nb, self.ws, {s: p.reshape(n, -1) for s, p in self.packs.items()},
+                    None if self.f32 is None else self.f32.reshape(n, -1), (n, math.prod(self.shape[1:])))
+        v.parent = self
+        return v
+
+
 class GraphModel:
     """General spec interpreter on the GPU (see module docstring)."""
 
-    def __init__(self, spec, device="cuda"):
+    # Default of `scaled_codes`: False.  Neither benchmark network has a consumer that takes the scaled route (ResNet-20's
+    # convolutions stay on k_conv_f32act, _scaled_route_pays; the VGG's activations feed max-pools), so the measurement the
+    # default was to be decided by shows no gain.  profiles/scaled/README.md.
+    def __init__(self, spec, device="cuda", scaled_codes=False):
         self.device = torch.device(device)
         self.spec = spec
         self.graph = _SpecGraph(spec, device)
         self.fuse_tail = True                # avg-pool + Flatten + Dense [+ softmax] in one launch (_SpecGraph.run_tail)
-        self.kernel_log = None               # tests: set to a list to record the kernel of every new-form pooling op
+        self.kernel_log = None               # tests: set to a list to record the kernel of every new-form pooling op, and of
+                                             # the pack and the consumers of every activation carried as scaled codes
+        self.scaled_codes = bool(scaled_codes)
+        self._scaled_memo = {}               # (op index, nb, input shape) -> _scaled_store: static per spec and shape
+
+    # ---- batch-scaled activations as packed codes plus a device-resident scale (include/qnn_abi_scaled.h) ----
+    def _scaled_store(self, c, nb, shape):
+        """Packed store at which contraction op `c` may consume the nb-bit scaled codes of a tensor of `shape`, or None:
+        low-bit weights, the input rank the op takes, and the exactness rule (scaled_route_exact)."""
+        key = (c, nb, tuple(shape))
+        if key not in self._scaled_memo:
+            self._scaled_memo[key] = self._scaled_store_of(c, nb, shape)
+        return self._scaled_memo[key]
+
+    def _scaled_store_of(self, c, nb, shape):
+        op = self.spec[c]
+        wstore = _wstore(op) if op["op"] in ("conv", "dense") else None
+        if wstore is None or len(shape) != (4 if op["op"] == "conv" else 2):
+            return None
+        k = op["kernel"].shape
+        if int(k[-2]) != int(shape[-1]) or not scaled_route_exact(math.prod(k[:-1]), nb, op["nb"] if op["kind"] == "quantized" else 1):
+            return None
+        store = _join_store(nb, wstore)
+        if not _weights_fit(op, store) or not _scaled_route_pays(op, store):
+            return None
+        return store
+
+    def _scaled_plan(self, name, nb, shape):
+        """(stores to pack at, True if some consumer needs the float32 tensor) for activation tensor `name`.  A Flatten
+        read only by qualifying dense layers is looked through when the channels fill whole words."""
+        g, stores, f32 = self.graph, set(), name == self.graph.names[-1]
+        for c in g.cons.get(name, []):
+            s = self._scaled_store(c, nb, shape)
+            ss = {s} if s is not None else self._scaled_flat_ok(c, nb, shape)
+            if ss is None:
+                f32 = True
+            else:
+                stores |= ss
+        return sorted(stores), f32
+
+    def _scaled_flat_ok(self, c, nb, shape):
+        """The stores behind Flatten op `c` if nothing but qualifying dense layers reads it and the channels fill whole
+        words (the packed words of an NHWC tensor are then those of its flattened form), else None."""
+        g = self.graph
+        if self.spec[c]["op"] != "flatten" or len(shape) != 4 or g.names[c] == g.names[-1]:
+            return None
+        behind = g.cons.get(g.names[c], [])
+        ss = {self._scaled_store(d, nb, (shape[0], math.prod(shape[1:]))) for d in behind}
+        if not behind or None in ss or any(shape[-1] % _abi.per_word(t) for t in ss):
+            return None
+        return ss
+
+    def _scaled_act(self, op, pre, name):
+        """Activation op `op` on `pre` as pass 1 (+ all-reduce under shard.sharded) and one pack per store its consumers
+        join at, the float32 tensor from the same pass when some consumer needs it; None when no consumer qualifies."""
+        stores, f32 = self._scaled_plan(name, int(op["nb"]), pre.shape)
+        if not stores:
+            return None
+        fn = _abi.FN_QUANTIZED_MAXRELU if op["fn"] == "quantized_maxrelu" else _abi.FN_QUANTIZED_LEAKYMAXRELU
+        if fn == _abi.FN_QUANTIZED_LEAKYMAXRELU:
+            quantized_ops.check_leaky_alpha(op.get("alpha", quantized_ops.LEAKY_ALPHA), "quantized_leakymaxrelu")
+        pre = _abi.require_cuda(pre, op["fn"])
+        ws = quantized_ops.maxact_word(pre, None, op["fn"])
+        # the float32 tensor comes from the pack's own pass where that streams at full rate (the I8 form); the I4 dual form
+        # writes half lines (profiles/scaled/README.md: 650 us against 530 us for the two passes), so there the apply pass
+        # runs first and the plain pack after it
+        dual = f32 and stores[0] == _abi.STORE_I8
+        sc = _Scaled(pre, fn, int(op["nb"]), ws, {}, torch.empty_like(pre) if dual else None, pre.shape)
+        if f32 and not dual:
+            sc.materialize()
+            if self.kernel_log is not None:
+                self.kernel_log.append("maxact_apply")
+        for j, store in enumerate(stores):
+            sc.packs[store] = _abi.maxact_pack(pre, pre.shape[-1], fn, int(op["nb"]), store, ws, sc.f32 if dual and j == 0 else None)
+            if self.kernel_log is not None:
+                self.kernel_log.append(_abi.last_kernel())
+        return sc
 
     def _pool(self, src, op):
         """A new-form pooling op.  Behind a low-bit clip the activation is packed as its consumers would pack it on load
@@ -775,11 +908,23 @@ class GraphModel:
     def _plain(t):
         if isinstance(t, _Packed):
             return t.to_f32()
-        return t.materialize() if isinstance(t, _Virtual) else t
+        return t.materialize() if isinstance(t, (_Virtual, _Scaled)) else t
 
     def _contract(self, i, op, src, inv, shift):
         """Conv / dense op `i` on `src` with BN (inv, shift) in its epilogue."""
         kind, wstore, g = op["op"], _wstore(op), self.graph
+        if isinstance(src, _Scaled):         # scaled codes: the integer kernels with the word attached, where this op qualified
+            store = self._scaled_store(i, src.nb, src.shape)
+            if store is not None and store in src.packs:
+                w = g.weights(i, store)
+                if kind == "conv":
+                    N, H, W, _ = src.shape
+                    y = _abi.conv2d(w, src.packs[store], store, src.nb, N, H, W, inv, shift, x_scale=src.ws)[0]
+                else:
+                    y = _abi.dense(w, src.packs[store], store, src.nb, src.shape[0], inv, shift, x_scale=src.ws)
+                if self.kernel_log is not None:
+                    self.kernel_log.append(_abi.last_kernel())
+                return y
         if isinstance(src, _Packed):         # the codes a new-form max-pool left
             if wstore is not None and _join_store(src.bits, wstore) == src.store and \
                     len(src.shape) == (4 if kind == "conv" else 2):
@@ -851,6 +996,13 @@ class GraphModel:
                 y = _add(self._plain(src), self._plain(env[op["b"]]))
             elif kind == "act" and _act_code(op) is not None:
                 y = _Virtual(self._plain(src), *_act_code(op), op)      # its consumers fuse the clip into their pack-on-load
+            elif kind == "act" and self.scaled_codes and op["fn"] in _MAX_ACTS and op["nb"] <= 8:
+                pre = self._plain(src)
+                y = self._scaled_act(op, pre, name)
+                if y is None:                # no consumer qualifies: exactly as without scaled_codes
+                    y = _act(pre, op)
+            elif kind == "flatten" and isinstance(src, _Scaled) and (self._scaled_flat_ok(i, src.nb, src.shape) or {None}) <= set(src.packs):
+                y = src.flat()
             elif kind == "act" and op["fn"] == "ternary_tanh":
                 # global mean over the batch tensor: not fusable; the result is on the grid {-1,0,1} and is packed as
                 # such by its consumers

@@ -47,19 +47,27 @@ def check_leaky_alpha(alpha, what="quantized_leakyrelu"):
 def _quantized_maxact(W, fn, nb, group, what):
     """The reduction kernel, the all-reduce of its word between the halves of a sharded batch, the apply kernel -- built
     like ternary_ops.ternary_tanh.  Nothing is read back to the host."""
-    from .. import shard
     W = _abi.require_cuda(W, what)
     y = torch.empty_like(W)
+    ws = maxact_word(W, group, what)
+    _abi.check(_abi.load().qnn_maxact_apply_f32(_abi.ptr(W), _abi.ptr(y), W.numel(), fn, int(nb), _abi.ptr(ws),
+                                                _abi.stream_ptr()), what)
+    return y
+
+
+def maxact_word(W, group=None, what="maxact_word"):
+    """Pass 1 of the two activations on the contiguous float32 CUDA tensor W: a fresh 16-byte workspace (int32[4]) whose
+    first word holds the bits of the maximum -- of the valid rows under `shard.sharded(..., valid_rows=k)`, all-reduced
+    between the shards.  The apply pass and the pack pass (include/qnn_abi_scaled.h) and every scaled consumer read it."""
+    from .. import shard
     ws = torch.empty(4, dtype=torch.int32, device=W.device)          # the 16-byte workspace: word 0 = bits(M)
-    lib = _abi.load()
     n_max = W.numel()
     valid = shard.active_valid_rows()
     if valid is not None and W.dim() >= 1 and W.shape[0] > 0:
         n_max = min(int(valid), W.shape[0]) * (W.numel() // W.shape[0])
-    _abi.check(lib.qnn_maxact_max_f32(_abi.ptr(W), n_max, _abi.ptr(ws), _abi.stream_ptr()), what)
+    _abi.check(_abi.load().qnn_maxact_max_f32(_abi.ptr(W), n_max, _abi.ptr(ws), _abi.stream_ptr()), what)
     shard.allreduce_max(ws, group)
-    _abi.check(lib.qnn_maxact_apply_f32(_abi.ptr(W), _abi.ptr(y), W.numel(), fn, int(nb), _abi.ptr(ws), _abi.stream_ptr()), what)
-    return y
+    return ws
 
 
 def quantized_maxrelu(W, nb=16, group=None):

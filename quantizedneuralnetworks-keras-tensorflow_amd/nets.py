@@ -303,12 +303,14 @@ class Model:
     test_resnet.py:63-81), reduced to the inference surface: predict / evaluate / summary /
     set of weights, executing on the fused GPU engines."""
 
-    def __init__(self, cf, spec, device="cuda", first_layer="auto", lanes=None):
+    def __init__(self, cf, spec, device="cuda", first_layer="auto", lanes=None, scaled_codes=False):
         """first_layer: kernel for float32 images ("auto" | "exact" | "image" | "fixed", engine.FusedModel; "auto", the
         default, takes every float tensor like the reference's call(): the byte kernel where a batch is image bytes /
         255, the exact kernel where it is not); uint8 images always take the typed QNN_STORE_U8 entry.  lanes: batches
         kept in flight by predict() (engine.Pipelined; default 2 for the chain engine, 3 for the residual engine, whose
-        kernels run at one to three waves per SIMD and leave room for a third batch: +5 % on the ImageNet-224 ResNet)."""
+        kernels run at one to three waves per SIMD and leave room for a third batch: +5 % on the ImageNet-224 ResNet).
+        scaled_codes: handed to engine.GraphModel where a batch-scaled spec falls back to it (packed codes plus a
+        device-resident scale); the other engines do not take such specs."""
         from . import engine, _abi
         self.cf, self.spec = cf, spec
         try:
@@ -322,7 +324,7 @@ class Model:
                 # residual engine refuses stays an error
                 if not any(op["op"] == "act" and op["fn"] in BATCH_SCALED_ACTIVATIONS for op in spec):
                     raise
-                self.engine = engine.GraphModel(spec, device)
+                self.engine = engine.GraphModel(spec, device, scaled_codes=scaled_codes)
         self.layers = [op for op in spec if op["op"] in ("conv", "dense")]
         self.lanes = int(lanes) if lanes is not None else (2 if isinstance(self.engine, engine.FusedModel) else 3)
         self.upload_batches = 8              # predict() on a host array: batches uploaded (and resident) at a time
