@@ -23,6 +23,7 @@ from .layers.quantized_layers import (QuantizedConv2D, QuantizedDense,  # noqa: 
 from .layers.ternary_layers import TernaryConv2D, TernaryDense, TernaryConvolution2D  # noqa: F401
 from .layers.pooling import (MaxPooling2D, AveragePooling2D, GlobalAveragePooling2D,  # noqa: F401
                              GlobalMaxPooling2D)
+from .layers.merge import Concatenate  # noqa: F401
 
 __all__ = [
     "binary_tanh", "binarize", "binary_sigmoid", "quantize", "quantized_tanh", "quantized_relu", "quantized_leakyrelu",
@@ -31,4 +32,5 @@ __all__ = [
     "QuantizedConv2D", "QuantizedDense", "QuantizedConvolution2D",
     "TernaryConv2D", "TernaryDense", "TernaryConvolution2D",
     "MaxPooling2D", "AveragePooling2D", "GlobalAveragePooling2D", "GlobalMaxPooling2D",
+    "Concatenate",
 ]

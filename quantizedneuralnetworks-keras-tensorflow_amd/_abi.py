@@ -1,5 +1,5 @@
-"""ctypes binding of include/qnn_abi.h, qnn_abi_dilation.h, qnn_abi_qact.h, qnn_abi_maxact.h, qnn_abi_pool.h and
-qnn_abi_scaled.h (csrc/libqnn_hip.so).
+"""ctypes binding of include/qnn_abi.h, qnn_abi_dilation.h, qnn_abi_qact.h, qnn_abi_maxact.h, qnn_abi_pool.h,
+qnn_abi_scaled.h and qnn_abi_concat.h (csrc/libqnn_hip.so).
 
 The library is loaded eagerly and loudly: a missing or unloadable .so raises at
 import time of any op that needs it (there is no CPU implementation to fall back
@@ -57,6 +57,15 @@ POOL_MAX, POOL_AVG = 0, 1
 # include/qnn_abi_scaled.h: the two activations of qnn_abi_maxact.h as packed codes plus the device-resident scale, and the
 # conv / dense entries that consume them
 EXPORTS_SCALED = ["qnn_maxact_pack_f32", "qnn_conv2d_forward_scaled", "qnn_dense_forward_scaled"]
+
+# include/qnn_abi_concat.h: Concatenate(axis=-1) on float32 and on packed codes
+EXPORTS_CONCAT = ["qnn_concat_forward"]
+CONCAT_MAX = 8
+
+
+class Concat(ctypes.Structure):
+    """qnn_concat_t"""
+    _fields_ = [("n", ctypes.c_int32), ("channels", ctypes.c_int32 * CONCAT_MAX), ("x", ctypes.c_void_p * CONCAT_MAX)]
 
 
 class Pool2D(ctypes.Structure):
@@ -171,7 +180,8 @@ def load():
     lib.qnn_maxact_pack_f32.argtypes = [vp, vp, vp, sz, ci, ci, ci, ci, vp, vp]
     lib.qnn_conv2d_forward_scaled.argtypes = [vp, vp, ci, ci, ci, ci, ci, ctypes.POINTER(Epilogue), vp, vp, vp]
     lib.qnn_dense_forward_scaled.argtypes = [vp, vp, ci, ci, ci, ctypes.POINTER(Epilogue), vp, vp, vp]
-    for name in EXPORTS + EXPORTS_DILATION + EXPORTS_QACT + EXPORTS_MAXACT + EXPORTS_POOL + EXPORTS_SCALED:   # every symbol the headers declare must be exported
+    lib.qnn_concat_forward.argtypes = [ctypes.POINTER(Concat), ci, ci, sz, vp, vp]
+    for name in EXPORTS + EXPORTS_DILATION + EXPORTS_QACT + EXPORTS_MAXACT + EXPORTS_POOL + EXPORTS_SCALED + EXPORTS_CONCAT:   # every symbol the headers declare must be exported
         getattr(lib, name)
     _lib = lib
     return lib
@@ -378,6 +388,49 @@ def pool2d(x, store, bits, N, H, W, C, mode, size, strides=None, same=False):
     check(load().qnn_pool2d_forward(ptr(x), store, bits, N, H, W, C, ctypes.byref(desc), ptr(y), y_store, stream_ptr()),
           "qnn_pool2d_forward")
     return y, Ho, Wo
+
+
+def concat(tensors, channels, store, bits, pixels):
+    """qnn_concat_forward: Concatenate(axis=-1) of 1 .. CONCAT_MAX tensors that share `pixels` pixels: float32 (store =
+    STORE_F32; tensor i holds pixels * channels[i] values) -> float32 (pixels, sum of the channels), or int32 packed words
+    (STORE_BIN / _I4 / _I8 at `bits`, STORE_T2) as pack() writes them -> the packed words of the concatenation, spare bits
+    zero.  Codes are copied, never re-quantised.  CUDA tensors only: there is no CPU path."""
+    tensors, channels = list(tensors), [int(c) for c in channels]
+    if len(tensors) != len(channels):
+        raise ValueError("concat: %d tensors but %d channel counts" % (len(tensors), len(channels)))
+    if not 1 <= len(tensors) <= CONCAT_MAX:
+        raise QnnError("concat: %d inputs (qnn_concat_forward takes 1 .. %d)" % (len(tensors), CONCAT_MAX))
+    if store not in (STORE_F32, STORE_BIN, STORE_T2, STORE_I4, STORE_I8):
+        raise QnnError("concat: store=%r (float32 or a packed activation store)" % (store,))
+    if min(channels) < 1:
+        raise QnnError("concat: channels=%r (every input has at least one)" % (channels,))
+    pixels = int(pixels)
+    dt = torch.float32 if store == STORE_F32 else torch.int32
+    xs = []
+    for i, (t, c) in enumerate(zip(tensors, channels)):
+        if store == STORE_F32:
+            t = require_cuda(t, "concat")
+            n = pixels * c
+        else:
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int32 and t.is_contiguous()):
+                raise QnnError("concat: a packed input must be a contiguous int32 CUDA tensor")
+            n = pixels * words(store, c)
+        if t.numel() != n:
+            raise QnnError("concat: input %d holds %d elements, %d pixels of %d channels are %d" % (i, t.numel(), pixels, c, n))
+        xs.append(t)
+    desc = Concat()
+    desc.n = len(xs)
+    for i, (t, c) in enumerate(zip(xs, channels)):
+        desc.channels[i] = c
+        desc.x[i] = t.data_ptr()
+    total = sum(channels)
+    cols = total if store == STORE_F32 else words(store, total)
+    y = torch.empty((pixels, cols), dtype=dt, device=xs[0].device)
+    rc = load().qnn_concat_forward(ctypes.byref(desc), int(store), int(bits), pixels, ptr(y), stream_ptr())
+    if rc == QNN_EUNSUPPORTED:
+        raise QnnUnsupported("qnn_concat_forward: " + load().qnn_last_error().decode(errors="replace"))
+    check(rc, "qnn_concat_forward")
+    return y
 
 
 def softmax(x, out=None):

@@ -13,7 +13,9 @@
                       hipGraphs of model(x) per lane.  What nets.Model.predict and bench.py's timed region run.
   GraphModel          general interpreter, one launch per contraction with the activation clip fused into its
                       pack-on-load and BN into its epilogue; the stock Keras layers around it are float32 torch ops.
-                      The plain counterpart the tests hold the fused engines against.
+                      The plain counterpart the tests hold the fused engines against, and the one engine that runs
+                      {"op": "concat", "srcs": [...]} (channel concatenation, qnn_concat_forward: on packed codes
+                      where every branch hands codes of one store); nets.Model falls to it for such a spec.
   LayerModel          the Keras-compatible layer objects called one by one (float32 NHWC in, float32 NHWC out per
                       layer: "M0" traffic model); nets.Model.conv_output reads intermediate tensors through it.
 
@@ -205,8 +207,8 @@ class _SpecGraph:
         self.spec, self.device = spec, torch.device(device)
         self.names = [op.get("dst", "t%d" % i) for i, op in enumerate(spec)]
         self.prod = {n: i for i, n in enumerate(self.names)}
-        # the tensors op i reads: add -> a, b; a named `src`; else the previous op's output; else the images
-        self.srcs = [[op["a"], op["b"]] if op["op"] == "add" else
+        # the tensors op i reads: add -> a, b; concat -> its srcs; a named `src`; else the previous op's output; else the images
+        self.srcs = [[op["a"], op["b"]] if op["op"] == "add" else list(op["srcs"]) if op["op"] == "concat" else
                      [op["src"] if "src" in op else self.names[i - 1] if i > 0 else "input"] for i, op in enumerate(spec)]
         self.cons = {}
         for i, ss in enumerate(self.srcs):
@@ -344,6 +346,43 @@ def _scale(t, op):
 
 def _add(a, b):
     return a + b
+
+
+def _concat_run(tensors, channels, store, bits, pixels, log=None):
+    """qnn_concat_forward over any number of inputs: more than it takes in one call are joined front to back, the
+    result so far as the first input of the next call."""
+    tensors, channels = list(tensors), list(channels)
+    while True:
+        k = _abi.CONCAT_MAX
+        y = _abi.concat(tensors[:k], channels[:k], store, bits, pixels)
+        if log is not None:
+            log.append(_abi.last_kernel())
+        if len(tensors) <= k:
+            return y
+        tensors, channels = [y] + tensors[k:], [sum(channels[:k])] + channels[k:]
+
+
+def _concat_shapes(shapes, what="concat"):
+    """The shape of the channel concatenation of tensors shaped `shapes` (ValueError unless they differ in the last axis only)."""
+    shapes = [tuple(int(d) for d in s) for s in shapes]
+    if len({s[:-1] for s in shapes}) != 1:
+        raise ValueError("%s: the inputs must have matching shapes except for the channel axis, got %s" % (what, shapes))
+    return shapes[0][:-1] + (sum(s[-1] for s in shapes),)
+
+
+def _concat_f32(tensors, log=None):
+    """Concatenate(axis=-1) of float32 tensors (concat_f32)."""
+    shape = _concat_shapes([t.shape for t in tensors])
+    y = _concat_run([t.contiguous() for t in tensors], [t.shape[-1] for t in tensors], _abi.STORE_F32, 0,
+                    math.prod(shape[:-1]), log)
+    return y.reshape(shape)
+
+
+def _refuse_concat(spec, who):
+    """The fused engines and the layer-by-layer one read one tensor per op (an add: two); GraphModel runs a spec whose
+    branches meet by stacking channels."""
+    if any(op["op"] == "concat" for op in spec):
+        raise _abi.NotFusable("%s: op 'concat' (channel concatenation) is not expressed by this engine; use GraphModel" % who)
 
 
 def _bn_apply(t, inv, shift):
@@ -484,6 +523,7 @@ class FusedModel(_DomainFlag):
         self._head_no = {}                   # (H, W) of inputs the library has no fused head kernel for
         self.steps = []
         self._keep = []
+        _refuse_concat(spec, "FusedModel")
         _refuse_max_acts(spec, "FusedModel")
         groups = self._group(spec)
         if groups is None:
@@ -797,8 +837,8 @@ class GraphModel:
         self.spec = spec
         self.graph = _SpecGraph(spec, device)
         self.fuse_tail = True                # avg-pool + Flatten + Dense [+ softmax] in one launch (_SpecGraph.run_tail)
-        self.kernel_log = None               # tests: set to a list to record the kernel of every new-form pooling op, and of
-                                             # the pack and the consumers of every activation carried as scaled codes
+        self.kernel_log = None               # tests: set to a list to record the kernel of every new-form pooling op, of every
+                                             # concat, and of the pack and the consumers of every activation carried as scaled codes
         self.scaled_codes = bool(scaled_codes)
         self._scaled_memo = {}               # (op index, nb, input shape) -> _scaled_store: static per spec and shape
 
@@ -888,6 +928,22 @@ class GraphModel:
         if self.kernel_log is not None:
             self.kernel_log.append(_abi.last_kernel())
         return y
+
+    def _concat(self, srcs):
+        """A concat op on the evaluated tensors `srcs` (include/qnn_abi_concat.h).  Packed codes of one store and width
+        (the new-form max-pools of two branches) are joined as codes and stay packed for the next contraction.  Clips of
+        one function and width that are not materialised yet stay one: concatenation commutes with an elementwise clip,
+        so the pre-activations are joined and the consumers still fuse the clip into their pack-on-load.  Everything else
+        (a batch-scaled activation included) is materialised and joined in float32."""
+        first = srcs[0]
+        if all(isinstance(t, _Packed) for t in srcs) and len({(t.store, t.bits) for t in srcs}) == 1:
+            shape = _concat_shapes([t.shape for t in srcs])
+            y = _concat_run([t.t for t in srcs], [t.shape[-1] for t in srcs], first.store, first.bits,
+                            math.prod(shape[:-1]), self.kernel_log)
+            return _Packed(y, first.store, first.bits, shape)
+        if all(isinstance(t, _Virtual) for t in srcs) and len({(t.fn, t.nb) for t in srcs}) == 1:
+            return _Virtual(_concat_f32([t.pre for t in srcs], self.kernel_log), first.fn, first.nb, first.op)
+        return _concat_f32([self._plain(t) for t in srcs], self.kernel_log)
 
     def _tail(self, i, src):
         """The classifier tail that starts at avgpool op `i`, fused: (its op indices, result) or None.  The clip in front
@@ -994,6 +1050,8 @@ class GraphModel:
                 y = _bn_apply(self._plain(src), *g.bn[i])
             elif kind == "add":
                 y = _add(self._plain(src), self._plain(env[op["b"]]))
+            elif kind == "concat":
+                y = self._concat([env[s] for s in g.srcs[i]])
             elif kind == "act" and _act_code(op) is not None:
                 y = _Virtual(self._plain(src), *_act_code(op), op)      # its consumers fuse the clip into their pack-on-load
             elif kind == "act" and self.scaled_codes and op["fn"] in _MAX_ACTS and op["nb"] <= 8:
@@ -1100,6 +1158,7 @@ class ResidualFusedModel(_DomainFlag):
         library cannot fold exactly keep the chain); False = always the float32 chain.  Same bits either way."""
         if first_layer not in ("auto", "exact", "image"):
             raise ValueError("first_layer must be 'auto', 'exact' or 'image', got %r" % (first_layer,))
+        _refuse_concat(spec, "ResidualFusedModel")
         _refuse_max_acts(spec, "ResidualFusedModel")
         self.first_layer = first_layer
         self.fold = bool(fold)
@@ -1195,7 +1254,7 @@ class ResidualFusedModel(_DomainFlag):
                 elif op["op"] in ("maxpool", "globalmaxpool") and _new_pool(op):
                     todo.append((self.names[ci], flat))      # codes in, codes out (qnn_pool2d_forward): what ITS consumers want
                 else:
-                    return None
+                    return None          # (a concat among them: a float32 consumer)
         if not joins:
             return _abi.STORE_BIN if bits == 1 else _abi.store_for_bits(bits)
         if all(j == _abi.STORE_BIN for j in joins):
@@ -1653,6 +1712,7 @@ class LayerModel:
     (every low-bit layer: float32 NHWC in -> float32 NHWC out)."""
 
     def __init__(self, spec, device="cuda", fuse_input_activation=True):
+        _refuse_concat(spec, "LayerModel")
         self.device = torch.device(device)
         self.spec = spec
         self.layers = {}

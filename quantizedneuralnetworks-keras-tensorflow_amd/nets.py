@@ -320,9 +320,9 @@ class Model:
                 self.engine = engine.ResidualFusedModel(spec, device,
                                                         first_layer=first_layer if first_layer in ("auto", "image") else "exact")
             except _abi.NotFusable:
-                # only the batch-scaled activations (float32 between the layers) are handed on; anything else the
-                # residual engine refuses stays an error
-                if not any(op["op"] == "act" and op["fn"] in BATCH_SCALED_ACTIVATIONS for op in spec):
+                # only the batch-scaled activations (float32 between the layers) and channel concatenation are handed
+                # on; anything else the residual engine refuses stays an error
+                if not any((op["op"] == "act" and op["fn"] in BATCH_SCALED_ACTIVATIONS) or op["op"] == "concat" for op in spec):
                     raise
                 self.engine = engine.GraphModel(spec, device, scaled_codes=scaled_codes)
         self.layers = [op for op in spec if op["op"] in ("conv", "dense")]
@@ -565,6 +565,13 @@ def spec_from_keras_npz(path, wbits=None, abits=None):
             op = {"op": "act", "fn": "leaky_relu", "alpha": float(c.get("alpha", 0.3))}
         elif cls == "Add":
             op = {"op": "add", "a": "input" if inbound[0] == spec_alias else inbound[0], "b": inbound[1]}
+            src = None
+        elif cls == "Concatenate":
+            axis = int(c.get("axis", -1))
+            if axis not in (-1, 3):
+                raise ValueError("Concatenate layer %r has axis=%d; only the channel axis of NHWC tensors (-1 or 3) is "
+                                 "supported" % (name, axis))
+            op = {"op": "concat", "srcs": ["input" if ib == spec_alias else ib for ib in inbound]}
             src = None
         elif cls == "Lambda":
             op = {"op": "scale", "value": 0.5}

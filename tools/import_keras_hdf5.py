@@ -8,7 +8,8 @@ model.load_weights).  Needs h5py, which only the conda interpreter of the build 
 
 HDF5 is read as plain data (datasets + attributes); nothing in the file is executed.  The
 .npz holds one array per Keras weight ("<layer>/<weight>") plus "model_config_json" (uint8).
-`nets.spec_from_keras_npz()` rebuilds the network from it.
+`nets.spec_from_keras_npz()` rebuilds the network from it.  Layers without weights (Add, Concatenate, the pooling layers,
+Flatten, ...) are carried by the model_config alone: their inbound nodes and settings go through as they are.
 """
 import json
 import sys
