@@ -24,6 +24,7 @@ from .layers.ternary_layers import TernaryConv2D, TernaryDense, TernaryConvoluti
 from .layers.pooling import (MaxPooling2D, AveragePooling2D, GlobalAveragePooling2D,  # noqa: F401
                              GlobalMaxPooling2D)
 from .layers.merge import Concatenate  # noqa: F401
+from .layers.spatial import ZeroPadding2D, Cropping2D, UpSampling2D  # noqa: F401
 
 __all__ = [
     "binary_tanh", "binarize", "binary_sigmoid", "quantize", "quantized_tanh", "quantized_relu", "quantized_leakyrelu",
@@ -33,4 +34,5 @@ __all__ = [
     "TernaryConv2D", "TernaryDense", "TernaryConvolution2D",
     "MaxPooling2D", "AveragePooling2D", "GlobalAveragePooling2D", "GlobalMaxPooling2D",
     "Concatenate",
+    "ZeroPadding2D", "Cropping2D", "UpSampling2D",
 ]

@@ -1,5 +1,5 @@
 """ctypes binding of include/qnn_abi.h, qnn_abi_dilation.h, qnn_abi_qact.h, qnn_abi_maxact.h, qnn_abi_pool.h,
-qnn_abi_scaled.h and qnn_abi_concat.h (csrc/libqnn_hip.so).
+qnn_abi_scaled.h, qnn_abi_concat.h and qnn_abi_spatial.h (csrc/libqnn_hip.so).
 
 The library is loaded eagerly and loudly: a missing or unloadable .so raises at
 import time of any op that needs it (there is no CPU implementation to fall back
@@ -7,6 +7,7 @@ to).  Tensors cross the boundary as raw device pointers (``tensor.data_ptr()``)
 plus the current HIP stream of torch.
 """
 import ctypes
+import numbers
 import os
 
 import torch
@@ -61,6 +62,14 @@ EXPORTS_SCALED = ["qnn_maxact_pack_f32", "qnn_conv2d_forward_scaled", "qnn_dense
 # include/qnn_abi_concat.h: Concatenate(axis=-1) on float32 and on packed codes
 EXPORTS_CONCAT = ["qnn_concat_forward"]
 CONCAT_MAX = 8
+
+# include/qnn_abi_spatial.h: Cropping2D / UpSampling2D (nearest) / ZeroPadding2D on float32 and on packed codes
+EXPORTS_SPATIAL = ["qnn_spatial2d_out_hw", "qnn_spatial2d_forward"]
+
+
+class Spatial2D(ctypes.Structure):
+    """qnn_spatial2d_t"""
+    _fields_ = [("crop", ctypes.c_int32 * 4), ("up", ctypes.c_int32 * 2), ("pad", ctypes.c_int32 * 4)]
 
 
 class Concat(ctypes.Structure):
@@ -181,7 +190,9 @@ def load():
     lib.qnn_conv2d_forward_scaled.argtypes = [vp, vp, ci, ci, ci, ci, ci, ctypes.POINTER(Epilogue), vp, vp, vp]
     lib.qnn_dense_forward_scaled.argtypes = [vp, vp, ci, ci, ci, ctypes.POINTER(Epilogue), vp, vp, vp]
     lib.qnn_concat_forward.argtypes = [ctypes.POINTER(Concat), ci, ci, sz, vp, vp]
-    for name in EXPORTS + EXPORTS_DILATION + EXPORTS_QACT + EXPORTS_MAXACT + EXPORTS_POOL + EXPORTS_SCALED + EXPORTS_CONCAT:   # every symbol the headers declare must be exported
+    lib.qnn_spatial2d_out_hw.argtypes = [ci, ci, ctypes.POINTER(Spatial2D), ctypes.POINTER(ci), ctypes.POINTER(ci)]
+    lib.qnn_spatial2d_forward.argtypes = [vp, ci, ci, ci, ci, ci, ci, ctypes.POINTER(Spatial2D), vp, vp]
+    for name in EXPORTS + EXPORTS_DILATION + EXPORTS_QACT + EXPORTS_MAXACT + EXPORTS_POOL + EXPORTS_SCALED + EXPORTS_CONCAT + EXPORTS_SPATIAL:   # every symbol the headers declare must be exported
         getattr(lib, name)
     _lib = lib
     return lib
@@ -387,6 +398,86 @@ def pool2d(x, store, bits, N, H, W, C, mode, size, strides=None, same=False):
         y = torch.empty((N * Ho * Wo, words(store, C)), dtype=torch.int32, device=x.device)
     check(load().qnn_pool2d_forward(ptr(x), store, bits, N, H, W, C, ctypes.byref(desc), ptr(y), y_store, stream_ptr()),
           "qnn_pool2d_forward")
+    return y, Ho, Wo
+
+
+def pairs2d(v, what):
+    """Keras 2.1.3's ZeroPadding2D / Cropping2D argument: an int, a pair of ints (rows, columns: the same on both sides)
+    or a pair of pairs ((top, bottom), (left, right)) -> (top, bottom, left, right)."""
+    if isinstance(v, numbers.Integral) and not isinstance(v, bool):
+        return (int(v),) * 4
+    if isinstance(v, (tuple, list)) and len(v) == 2:
+        out = []
+        for side in v:
+            if isinstance(side, numbers.Integral) and not isinstance(side, bool):
+                out += [int(side), int(side)]
+            elif isinstance(side, (tuple, list)) and len(side) == 2 and \
+                    all(isinstance(k, numbers.Integral) and not isinstance(k, bool) for k in side):
+                out += [int(side[0]), int(side[1])]
+            else:
+                out = None
+                break
+        if out is not None:
+            return tuple(out)
+    raise ValueError("`%s` should be either an int, a tuple of 2 ints (symmetric_height, symmetric_width), or a tuple of "
+                     "2 tuples of 2 ints ((top, bottom), (left, right)). Found: %r" % (what, v))
+
+
+def spatial_desc(crop=0, up=1, pad=0):
+    """qnn_spatial2d_t from Keras' argument forms: crop then repeat then pad."""
+    if isinstance(up, (tuple, list)):
+        if len(up) != 2:
+            raise ValueError("`size` should be an int or a pair of ints, got %r" % (up,))
+        uy, ux = int(up[0]), int(up[1])
+    else:
+        uy = ux = int(up)
+    d = Spatial2D()
+    d.crop[:] = pairs2d(crop, "cropping")
+    d.up[:] = (uy, ux)
+    d.pad[:] = pairs2d(pad, "padding")
+    return d
+
+
+def spatial2d_out_hw(H, W, crop=0, up=1, pad=0):
+    """qnn_spatial2d_out_hw: (Ho, Wo) of crop -> repeat -> pad on an H x W image; touches no device."""
+    desc = spatial_desc(crop, up, pad)
+    Ho, Wo = ctypes.c_int(0), ctypes.c_int(0)
+    check(load().qnn_spatial2d_out_hw(int(H), int(W), ctypes.byref(desc), ctypes.byref(Ho), ctypes.byref(Wo)),
+          "qnn_spatial2d_out_hw")
+    return Ho.value, Wo.value
+
+
+def spatial2d(x, store, bits, N, H, W, C, crop=0, up=1, pad=0):
+    """qnn_spatial2d_forward: Cropping2D(crop), then UpSampling2D(up) (nearest), then ZeroPadding2D(pad) of an NHWC tensor:
+    float32 (store = STORE_F32) -> float32 (N, Ho, Wo, C), or int32 packed words (STORE_BIN / _I4 / _I8 at `bits`,
+    STORE_T2) as pack() writes them -> (N * Ho * Wo, words) codes of the same store and bits, spare bits zero.  Codes are
+    copied, never re-quantised.  Returns (y, Ho, Wo).  A pad on STORE_BIN raises QnnUnsupported (a +-1 code has no zero)."""
+    desc = spatial_desc(crop, up, pad)
+    Ho, Wo = ctypes.c_int(0), ctypes.c_int(0)
+    check(load().qnn_spatial2d_out_hw(int(H), int(W), ctypes.byref(desc), ctypes.byref(Ho), ctypes.byref(Wo)),
+          "qnn_spatial2d_out_hw")
+    Ho, Wo = Ho.value, Wo.value
+    if store == STORE_F32:
+        x = require_cuda(x, "spatial2d")
+        n = N * H * W * C
+    else:
+        if store not in (STORE_BIN, STORE_T2, STORE_I4, STORE_I8):
+            raise QnnError("spatial2d: store=%r (float32 or a packed activation store)" % (store,))
+        if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.int32 and x.is_contiguous()):
+            raise QnnError("spatial2d: a packed input must be a contiguous int32 CUDA tensor")
+        n = N * H * W * words(store, C)
+    if x.numel() != n:
+        raise QnnError("spatial2d: the input holds %d elements, %d x %d x %d pixels of %d channels are %d"
+                       % (x.numel(), N, H, W, C, n))
+    if store == STORE_F32:
+        y = torch.empty((N, Ho, Wo, C), dtype=torch.float32, device=x.device)
+    else:
+        y = torch.empty((N * Ho * Wo, words(store, C)), dtype=torch.int32, device=x.device)
+    rc = load().qnn_spatial2d_forward(ptr(x), int(store), int(bits), int(N), int(H), int(W), int(C), ctypes.byref(desc),
+                                      ptr(y), stream_ptr())
+    if rc == QNN_EUNSUPPORTED:
+        raise QnnUnsupported("qnn_spatial2d_forward: " + load().qnn_last_error().decode(errors="replace"))
+    check(rc, "qnn_spatial2d_forward")
     return y, Ho, Wo
 
 

@@ -15,7 +15,9 @@
                       pack-on-load and BN into its epilogue; the stock Keras layers around it are float32 torch ops.
                       The plain counterpart the tests hold the fused engines against, and the one engine that runs
                       {"op": "concat", "srcs": [...]} (channel concatenation, qnn_concat_forward: on packed codes
-                      where every branch hands codes of one store); nets.Model falls to it for such a spec.
+                      where every branch hands codes of one store) and the new-form spatial ops {"op": "crop"},
+                      {"op": "upsample"} and {"op": "zeropad", "pad": ((t, b), (l, r))} (qnn_spatial2d_forward: behind
+                      a low-bit clip the codes are moved and stay packed); nets.Model falls to it for such a spec.
   LayerModel          the Keras-compatible layer objects called one by one (float32 NHWC in, float32 NHWC out per
                       layer: "M0" traffic model); nets.Model.conv_output reads intermediate tensors through it.
 
@@ -331,9 +333,60 @@ def _avgpool(t, op):
     return win.double().sum(dim=(2, 4)).float() / F32(s * s)
 
 
+# Spatial ops (include/qnn_abi_spatial.h): every output pixel is a copy of one input pixel or zero.  A zeropad op whose
+# `pad` is one integer is the OLD FORM (what every spec builder and reference checkpoint produces, run by the torch code
+# below on float32); `pad` as ((top, bottom), (left, right)), `crop` and `upsample` are the NEW FORM, run by
+# qnn_spatial2d_forward on float32 here and on packed codes by GraphModel.
+_SPATIAL = ("zeropad", "crop", "upsample")
+
+
+def _new_spatial(op):
+    if op["op"] == "zeropad":
+        return not isinstance(op["pad"], (int, np.integer))
+    return op["op"] in ("crop", "upsample")
+
+
+def _spatial_steps(op):
+    """The steps of qnn_spatial2d_t a new-form spatial op sets."""
+    if op["op"] == "upsample":
+        return {"up": _abi._pair(op["size"], "size")}
+    key = "pad" if op["op"] == "zeropad" else "crop"
+    v = op[key]
+    if not (isinstance(v, (tuple, list)) and len(v) == 2 and all(isinstance(side, (tuple, list)) and len(side) == 2 for side in v)):
+        raise ValueError("%s: `%s` is ((top, bottom), (left, right))%s, got %r"
+                         % (op["op"], key, " or one integer" if key == "pad" else "", v))
+    t, b, l, r = _abi.pairs2d(v, key)
+    return {key: ((t, b), (l, r))}
+
+
+def _spatial_run(x, store, bits, shape, op, log=None):
+    """A new-form spatial op on an NHWC tensor `x` (float32, or packed words at (store, bits)): (y, output shape)."""
+    N, H, W, C = shape
+    y, Ho, Wo = _abi.spatial2d(x, store, bits, N, H, W, C, **_spatial_steps(op))
+    if log is not None:
+        log.append(_abi.last_kernel())
+    return y, (N, Ho, Wo, C)
+
+
+def _spatial_f32(t, op):
+    return _spatial_run(t.contiguous(), _abi.STORE_F32, 0, t.shape, op)[0]
+
+
 def _zeropad(t, op):
+    if _new_spatial(op):
+        return _spatial_f32(t, op)
     p = op["pad"]
     return torch.nn.functional.pad(t, (0, 0, p, p, p, p))
+
+
+def _refuse_spatial(spec, who):
+    """The fused engines plan their launches over conv -> BN -> clip chains and size-only pools; GraphModel runs a spec
+    that resizes a map between them."""
+    for op in spec:
+        if op["op"] in _SPATIAL and _new_spatial(op):
+            raise _abi.NotFusable("%s: op %r (%s) is not expressed by this engine; use GraphModel"
+                                  % (who, op["op"], "pair-form zero padding" if op["op"] == "zeropad" else
+                                     "cropping" if op["op"] == "crop" else "nearest-neighbour up-sampling"))
 
 
 def _flatten(t, op):
@@ -413,7 +466,7 @@ def _act(t, op):
     raise ValueError(fn)
 
 
-_GLUE = {"maxpool": _maxpool, "avgpool": _avgpool, "globalmaxpool": _pool_f32, "globalavgpool": _pool_f32, "zeropad": _zeropad, "flatten": _flatten, "scale": _scale, "act": _act,
+_GLUE = {"maxpool": _maxpool, "avgpool": _avgpool, "globalmaxpool": _pool_f32, "globalavgpool": _pool_f32, "zeropad": _zeropad, "crop": _spatial_f32, "upsample": _spatial_f32, "flatten": _flatten, "scale": _scale, "act": _act,
          "softmax": lambda t, op: _abi.softmax(t)}
 
 
@@ -524,6 +577,7 @@ class FusedModel(_DomainFlag):
         self.steps = []
         self._keep = []
         _refuse_concat(spec, "FusedModel")
+        _refuse_spatial(spec, "FusedModel")
         _refuse_max_acts(spec, "FusedModel")
         groups = self._group(spec)
         if groups is None:
@@ -838,7 +892,8 @@ class GraphModel:
         self.graph = _SpecGraph(spec, device)
         self.fuse_tail = True                # avg-pool + Flatten + Dense [+ softmax] in one launch (_SpecGraph.run_tail)
         self.kernel_log = None               # tests: set to a list to record the kernel of every new-form pooling op, of every
-                                             # concat, and of the pack and the consumers of every activation carried as scaled codes
+                                             # concat and new-form spatial op ("unpack" in front of one that left the codes), and
+                                             # of the pack and the consumers of every activation carried as scaled codes
         self.scaled_codes = bool(scaled_codes)
         self._scaled_memo = {}               # (op index, nb, input shape) -> _scaled_store: static per spec and shape
 
@@ -929,21 +984,102 @@ class GraphModel:
             self.kernel_log.append(_abi.last_kernel())
         return y
 
-    def _concat(self, srcs):
+    def _grid_store(self, c):
+        """The store at which contraction op `c` reads ternary codes {-1, 0, 1} (_contract), None for float weights."""
+        op = self.spec[c]
+        wstore = _wstore(op) if op["op"] in ("conv", "dense") else None
+        if wstore is None:
+            return None
+        if op["kind"] == "ternary" and TERNARY_T2:
+            return _abi.STORE_T2             # ternary x ternary: sign / mask planes
+        return max(_abi.STORE_I4, wstore if wstore != _abi.STORE_BIN else _abi.STORE_I4)
+
+    def _grid_plan(self, name):
+        """The one store every contraction behind ternary activation `name` reads it at, looking through the ops that hand
+        packed words on (new-form spatial ops, concats), or None: another consumer, or no common store."""
+        stores, todo = set(), [name]
+        while todo:
+            n = todo.pop()
+            if n == self.graph.names[-1]:
+                return None
+            for c in self.graph.cons.get(n, []):
+                op = self.spec[c]
+                if op["op"] == "concat" or (op["op"] in _SPATIAL and _new_spatial(op)):
+                    todo.append(self.graph.names[c])
+                else:
+                    stores.add(self._grid_store(c))
+        return stores.pop() if len(stores) == 1 else None
+
+    def _pack_clip(self, v, name=None):
+        """The unmaterialised clip `v` as the packed codes its consumers would pack on load, or None where it has no
+        fixed code (a 16-bit clip) or, for ternary codes, its consumers (those of tensor `name`) share no store."""
+        if not isinstance(v, _Virtual) or v.pre.dim() != 4:
+            return None
+        if v.fn == _abi.FN_GRID:
+            store = self._grid_plan(name) if name is not None else None
+            if store is None:
+                return None
+            p = _Packed(_abi.pack(v.materialize(), v.pre.shape[-1], _abi.FN_GRID, 1, store), store, 1, v.pre.shape)
+            p.grid = True
+            return p
+        if v.fn not in (_abi.FN_BINARY_TANH,) + _abi.QUANT_FNS:
+            return None
+        bits = 1 if v.fn == _abi.FN_BINARY_TANH else v.nb
+        store = _abi.STORE_BIN if bits == 1 else _abi.store_for_bits(bits)
+        return _Packed(_abi.pack(v.pre, v.pre.shape[-1], v.fn, bits, store), store, bits, v.pre.shape)
+
+    def _spatial(self, src, op, name):
+        """A new-form spatial op producing tensor `name`.  Behind a low-bit clip the activation is packed as its consumers
+        would pack it on load and moved as codes, which stay packed for the next contraction (ternary codes: on the store
+        every contraction behind reads them at).  A pad behind a 1-bit clip (a +-1 code has no zero), an activation
+        carried as scaled codes and everything else run in float32."""
+        padded = op["op"] == "zeropad"
+        if isinstance(src, _Virtual) and not (padded and src.fn == _abi.FN_BINARY_TANH):
+            src = self._pack_clip(src, name) or src
+        if isinstance(src, _Packed) and len(src.shape) == 4 and not (padded and src.store == _abi.STORE_BIN):
+            y, shape = _spatial_run(src.t, src.store, src.bits, src.shape, op, self.kernel_log)
+            out = _Packed(y, src.store, src.bits, shape)
+            out.grid = src.grid
+            return out
+        if isinstance(src, _Packed) and self.kernel_log is not None:
+            self.kernel_log.append("unpack")
+        t = self._plain(src)
+        return _spatial_run(t.contiguous(), _abi.STORE_F32, 0, t.shape, op, self.kernel_log)[0]
+
+    def _concat(self, srcs, pack_clips=False):
         """A concat op on the evaluated tensors `srcs` (include/qnn_abi_concat.h).  Packed codes of one store and width
         (the new-form max-pools of two branches) are joined as codes and stay packed for the next contraction.  Clips of
         one function and width that are not materialised yet stay one: concatenation commutes with an elementwise clip,
         so the pre-activations are joined and the consumers still fuse the clip into their pack-on-load.  Everything else
-        (a batch-scaled activation included) is materialised and joined in float32."""
+        (a batch-scaled activation included) is materialised and joined in float32.  pack_clips: a branch was resized on
+        its codes (_spatial) and meets clips that are not materialised (the skip of an encoder-decoder): those are packed
+        as their consumers would pack them on load, so the join stays on codes."""
+        if pack_clips and any(isinstance(t, _Packed) for t in srcs):
+            like = next(t for t in srcs if isinstance(t, _Packed))
+            packs = [t if isinstance(t, _Packed) else None if not isinstance(t, _Virtual) else
+                     self._pack_grid_like(t, like) if t.fn == _abi.FN_GRID else self._pack_clip(t) for t in srcs]
+            if all(p is not None for p in packs) and len({(p.store, p.bits, p.grid) for p in packs}) == 1:
+                srcs = packs
         first = srcs[0]
-        if all(isinstance(t, _Packed) for t in srcs) and len({(t.store, t.bits) for t in srcs}) == 1:
+        if all(isinstance(t, _Packed) for t in srcs) and len({(t.store, t.bits, t.grid) for t in srcs}) == 1:
             shape = _concat_shapes([t.shape for t in srcs])
             y = _concat_run([t.t for t in srcs], [t.shape[-1] for t in srcs], first.store, first.bits,
                             math.prod(shape[:-1]), self.kernel_log)
-            return _Packed(y, first.store, first.bits, shape)
+            out = _Packed(y, first.store, first.bits, shape)
+            out.grid = first.grid
+            return out
         if all(isinstance(t, _Virtual) for t in srcs) and len({(t.fn, t.nb) for t in srcs}) == 1:
             return _Virtual(_concat_f32([t.pre for t in srcs], self.kernel_log), first.fn, first.nb, first.op)
         return _concat_f32([self._plain(t) for t in srcs], self.kernel_log)
+
+    @staticmethod
+    def _pack_grid_like(v, like):
+        """Ternary clip `v` packed on the store of `like`, ternary codes themselves; else None."""
+        if not like.grid or v.pre.dim() != 4:
+            return None
+        p = _Packed(_abi.pack(v.materialize(), v.pre.shape[-1], _abi.FN_GRID, 1, like.store), like.store, 1, v.pre.shape)
+        p.grid = True
+        return p
 
     def _tail(self, i, src):
         """The classifier tail that starts at avgpool op `i`, fused: (its op indices, result) or None.  The clip in front
@@ -981,8 +1117,9 @@ class GraphModel:
                 if self.kernel_log is not None:
                     self.kernel_log.append(_abi.last_kernel())
                 return y
-        if isinstance(src, _Packed):         # the codes a new-form max-pool left
-            if wstore is not None and _join_store(src.bits, wstore) == src.store and \
+        if isinstance(src, _Packed):         # the codes a new-form max-pool, spatial op or concat left
+            want = self._grid_store(i) if src.grid else _join_store(src.bits, wstore) if wstore is not None else None
+            if wstore is not None and want == src.store and \
                     len(src.shape) == (4 if kind == "conv" else 2):
                 w = g.weights(i, src.store)
                 if kind == "conv":
@@ -991,7 +1128,7 @@ class GraphModel:
                 return _abi.dense(w, src.t, src.store, src.bits, src.shape[0], inv, shift)
             # another store is needed (or float weights): the values are on the grid, where binary_tanh / quantized_tanh at
             # their width are the identity, so the consumer may clip them again on load
-            fn = _abi.FN_BINARY_TANH if src.store == _abi.STORE_BIN else _abi.FN_QUANTIZED_TANH
+            fn = _abi.FN_GRID if src.grid else _abi.FN_BINARY_TANH if src.store == _abi.STORE_BIN else _abi.FN_QUANTIZED_TANH
             v = _Virtual(src.to_f32(), fn, src.bits, None)
             v._mat = v.pre
             src = v
@@ -1051,7 +1188,11 @@ class GraphModel:
             elif kind == "add":
                 y = _add(self._plain(src), self._plain(env[op["b"]]))
             elif kind == "concat":
-                y = self._concat([env[s] for s in g.srcs[i]])
+                y = self._concat([env[s] for s in g.srcs[i]],
+                                 pack_clips=any(s in g.prod and spec[g.prod[s]]["op"] in _SPATIAL and _new_spatial(spec[g.prod[s]])
+                                                for s in g.srcs[i]))
+            elif kind in _SPATIAL and _new_spatial(op):
+                y = self._spatial(src, op, name)
             elif kind == "act" and _act_code(op) is not None:
                 y = _Virtual(self._plain(src), *_act_code(op), op)      # its consumers fuse the clip into their pack-on-load
             elif kind == "act" and self.scaled_codes and op["fn"] in _MAX_ACTS and op["nb"] <= 8:
@@ -1081,6 +1222,8 @@ class GraphModel:
 # ---------------------------------------------------------------------------
 class _Packed:
     """A packed activation tensor: int32 words (pixels, cw) + what the codes mean."""
+
+    grid = False                             # GraphModel: ternary codes {-1, 0, 1} (value = code), not a `bits`-wide clip
 
     def __init__(self, t, store, bits, shape):
         self.t, self.store, self.bits, self.shape = t, store, bits, tuple(shape)   # shape: NHWC or (N, K)
@@ -1159,6 +1302,7 @@ class ResidualFusedModel(_DomainFlag):
         if first_layer not in ("auto", "exact", "image"):
             raise ValueError("first_layer must be 'auto', 'exact' or 'image', got %r" % (first_layer,))
         _refuse_concat(spec, "ResidualFusedModel")
+        _refuse_spatial(spec, "ResidualFusedModel")
         _refuse_max_acts(spec, "ResidualFusedModel")
         self.first_layer = first_layer
         self.fold = bool(fold)
@@ -1781,8 +1925,8 @@ class LayerModel:
                 y = _GLUE[kind](src, op)
                 if kind == "act":
                     d = self._grid(op)
-                elif kind in ("maxpool", "globalmaxpool", "flatten"):
-                    d = dom.get(sname)      # max of grid values stays on the grid
+                elif kind in ("maxpool", "globalmaxpool", "flatten", "crop", "upsample"):
+                    d = dom.get(sname)      # max of grid values stays on the grid; a copy of pixels does too
             else:
                 raise ValueError(kind)
             env[g.names[i]] = y

@@ -320,9 +320,11 @@ class Model:
                 self.engine = engine.ResidualFusedModel(spec, device,
                                                         first_layer=first_layer if first_layer in ("auto", "image") else "exact")
             except _abi.NotFusable:
-                # only the batch-scaled activations (float32 between the layers) and channel concatenation are handed
-                # on; anything else the residual engine refuses stays an error
-                if not any((op["op"] == "act" and op["fn"] in BATCH_SCALED_ACTIVATIONS) or op["op"] == "concat" for op in spec):
+                # only the batch-scaled activations (float32 between the layers), channel concatenation and the new-form
+                # spatial ops (crop, upsample, pair-form zeropad) are handed on; anything else the residual engine
+                # refuses stays an error
+                if not any((op["op"] == "act" and op["fn"] in BATCH_SCALED_ACTIVATIONS) or op["op"] == "concat" or
+                           (op["op"] in engine._SPATIAL and engine._new_spatial(op)) for op in spec):
                     raise
                 self.engine = engine.GraphModel(spec, device, scaled_codes=scaled_codes)
         self.layers = [op for op in spec if op["op"] in ("conv", "dense")]
@@ -480,6 +482,22 @@ def _pool_data_format(c, name):
         raise ValueError("pooling layer %r has data_format='channels_first'; only channels_last (NHWC) is supported" % name)
 
 
+def _spatial_data_format(c, name):
+    if c.get("data_format") == "channels_first":
+        raise ValueError("layer %r has data_format='channels_first'; only channels_last (NHWC) is supported" % name)
+
+
+def _pairs2d(v, what, name):
+    """Keras' `padding` / `cropping` config (an int, (rows, columns) or ((top, bottom), (left, right))) as
+    (top, bottom, left, right)."""
+    sides = v if isinstance(v, (list, tuple)) else (v, v)
+    if len(sides) == 2:
+        sides = [s if isinstance(s, (list, tuple)) else (s, s) for s in sides]
+        if all(len(s) == 2 for s in sides):
+            return tuple(int(k) for s in sides for k in s)
+    raise ValueError("layer %r has %s=%r; expected an int, a pair of ints or a pair of pairs" % (name, what, v))
+
+
 def _pool_op(kind, c, name):
     """The spec op of a MaxPooling2D / AveragePooling2D config.  A square window with strides equal to it (Keras'
     strides=None) under 'valid' is the size-only op every spec builder emits; everything else carries the window and the
@@ -581,7 +599,22 @@ def spec_from_keras_npz(path, wbits=None, abits=None):
             _pool_data_format(c, name)
             op = {"op": "globalavgpool" if cls == "GlobalAveragePooling2D" else "globalmaxpool"}
         elif cls == "ZeroPadding2D":
-            op = {"op": "zeropad", "pad": int(c["padding"][0][0])}
+            _spatial_data_format(c, name)
+            t, b, l, r = _pairs2d(c["padding"], "padding", name)
+            # a symmetric square pad keeps the integer op every spec builder emits; anything else carries all four numbers
+            op = {"op": "zeropad", "pad": t if t == b == l == r else ((t, b), (l, r))}
+        elif cls == "Cropping2D":
+            _spatial_data_format(c, name)
+            t, b, l, r = _pairs2d(c["cropping"], "cropping", name)
+            op = {"op": "crop", "crop": ((t, b), (l, r))}
+        elif cls == "UpSampling2D":
+            _spatial_data_format(c, name)
+            if c.get("interpolation", "nearest") != "nearest":
+                raise ValueError("UpSampling2D layer %r has interpolation=%r; only 'nearest' is supported" % (name, c["interpolation"]))
+            size = c["size"] if isinstance(c["size"], (list, tuple)) else (c["size"], c["size"])
+            if len(size) != 2:
+                raise ValueError("UpSampling2D layer %r has size=%r" % (name, c["size"]))
+            op = {"op": "upsample", "size": (int(size[0]), int(size[1]))}
         elif cls == "Flatten":
             op = {"op": "flatten"}
         else:
