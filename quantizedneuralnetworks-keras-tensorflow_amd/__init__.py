@@ -25,6 +25,8 @@ from .layers.pooling import (MaxPooling2D, AveragePooling2D, GlobalAveragePoolin
                              GlobalMaxPooling2D)
 from .layers.merge import Concatenate  # noqa: F401
 from .layers.spatial import ZeroPadding2D, Cropping2D, UpSampling2D  # noqa: F401
+from .layers.depthwise import (DepthwiseConv2D, BinaryDepthwiseConv2D, QuantizedDepthwiseConv2D,  # noqa: F401
+                               TernaryDepthwiseConv2D)
 
 __all__ = [
     "binary_tanh", "binarize", "binary_sigmoid", "quantize", "quantized_tanh", "quantized_relu", "quantized_leakyrelu",
@@ -35,4 +37,5 @@ __all__ = [
     "MaxPooling2D", "AveragePooling2D", "GlobalAveragePooling2D", "GlobalMaxPooling2D",
     "Concatenate",
     "ZeroPadding2D", "Cropping2D", "UpSampling2D",
+    "DepthwiseConv2D", "BinaryDepthwiseConv2D", "QuantizedDepthwiseConv2D", "TernaryDepthwiseConv2D",
 ]

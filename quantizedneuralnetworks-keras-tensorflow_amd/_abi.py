@@ -1,5 +1,5 @@
 """ctypes binding of include/qnn_abi.h, qnn_abi_dilation.h, qnn_abi_qact.h, qnn_abi_maxact.h, qnn_abi_pool.h,
-qnn_abi_scaled.h, qnn_abi_concat.h and qnn_abi_spatial.h (csrc/libqnn_hip.so).
+qnn_abi_scaled.h, qnn_abi_concat.h, qnn_abi_spatial.h and qnn_abi_depthwise.h (csrc/libqnn_hip.so).
 
 The library is loaded eagerly and loudly: a missing or unloadable .so raises at
 import time of any op that needs it (there is no CPU implementation to fall back
@@ -65,6 +65,11 @@ CONCAT_MAX = 8
 
 # include/qnn_abi_spatial.h: Cropping2D / UpSampling2D (nearest) / ZeroPadding2D on float32 and on packed codes
 EXPORTS_SPATIAL = ["qnn_spatial2d_out_hw", "qnn_spatial2d_forward"]
+
+# include/qnn_abi_depthwise.h: DepthwiseConv2D with float / binary / quantized / ternary weights on float32 and packed codes
+EXPORTS_DEPTHWISE = ["qnn_depthwise_prepack", "qnn_depthwise_free", "qnn_depthwise_dequant", "qnn_depthwise_out_hw",
+                     "qnn_depthwise_forward"]
+DW_MAX_WINDOW = 7
 
 
 class Spatial2D(ctypes.Structure):
@@ -192,7 +197,13 @@ def load():
     lib.qnn_concat_forward.argtypes = [ctypes.POINTER(Concat), ci, ci, sz, vp, vp]
     lib.qnn_spatial2d_out_hw.argtypes = [ci, ci, ctypes.POINTER(Spatial2D), ctypes.POINTER(ci), ctypes.POINTER(ci)]
     lib.qnn_spatial2d_forward.argtypes = [vp, ci, ci, ci, ci, ci, ci, ctypes.POINTER(Spatial2D), vp, vp]
-    for name in EXPORTS + EXPORTS_DILATION + EXPORTS_QACT + EXPORTS_MAXACT + EXPORTS_POOL + EXPORTS_SCALED + EXPORTS_CONCAT + EXPORTS_SPATIAL:   # every symbol the headers declare must be exported
+    lib.qnn_depthwise_prepack.argtypes = [ci, ci, fl, vp, ci, ci, ci, ci, vp, ci, ci, ci, ci, ci, vp, ctypes.POINTER(vp)]
+    lib.qnn_depthwise_free.argtypes = [vp]
+    lib.qnn_depthwise_dequant.argtypes = [vp, vp, vp]
+    lib.qnn_depthwise_out_hw.argtypes = [vp, ci, ci, ctypes.POINTER(ci), ctypes.POINTER(ci)]
+    lib.qnn_depthwise_forward.argtypes = [vp, vp, ci, ci, ci, ci, ci, ctypes.POINTER(Epilogue), vp, vp]
+    for name in (EXPORTS + EXPORTS_DILATION + EXPORTS_QACT + EXPORTS_MAXACT + EXPORTS_POOL + EXPORTS_SCALED + EXPORTS_CONCAT
+                 + EXPORTS_SPATIAL + EXPORTS_DEPTHWISE):   # every symbol the headers declare must be exported
         getattr(lib, name)
     _lib = lib
     return lib
@@ -896,3 +907,82 @@ def dense(w, x, x_store, x_bits, N, bn_inv=None, bn_shift=None, fn=FN_NONE, act_
     check(load().qnn_dense_forward(w.handle, ptr(x), x_store, x_bits, N, ctypes.byref(epi), ptr(y),
                                    stream_ptr()), "qnn_dense_forward")
     return y
+
+
+class DepthwiseWeights:
+    """Owner of an opaque qnn_dw_weights_t handle (include/qnn_abi_depthwise.h).  kernel: float32 CUDA tensor in Keras'
+    depthwise layout (kh, kw, C, depth_multiplier); bias: (C * depth_multiplier,) or None."""
+
+    def __init__(self, wkind, wbits, H, kernel, bias, stride, same_pad, store, dilation=(1, 1)):
+        kernel = require_cuda(kernel, "depthwise prepack kernel")
+        if kernel.dim() != 4:
+            raise QnnError("depthwise prepack: the kernel must be (kh, kw, C, depth_multiplier), got %s" % (tuple(kernel.shape),))
+        kh, kw, C, M = kernel.shape
+        bias = require_cuda(bias, "depthwise prepack bias") if bias is not None else None
+        if bias is not None and bias.numel() != C * M:
+            raise QnnError("depthwise prepack: bias of %d values for %d x %d channels" % (bias.numel(), C, M))
+        self.shape = (kh, kw, C, M)
+        self.cout = C * M
+        self.wkind, self.wbits, self.store = wkind, wbits, store
+        self.stride, self.same_pad = int(stride), bool(same_pad)
+        self.dilation = (int(dilation[0]), int(dilation[1]))
+        self.handle = ctypes.c_void_p(None)
+        release_deferred()
+        rc = load().qnn_depthwise_prepack(wkind, wbits, float(H), ptr(kernel), kh, kw, C, M, ptr(bias), self.stride,
+                                          1 if same_pad else 0, self.dilation[0], self.dilation[1], store, stream_ptr(),
+                                          ctypes.byref(self.handle))
+        if rc == QNN_EUNSUPPORTED:
+            raise QnnUnsupported("qnn_depthwise_prepack: " + load().qnn_last_error().decode(errors="replace"))
+        check(rc, "qnn_depthwise_prepack")
+        self.device = kernel.device
+
+    def dequant(self):
+        out = torch.empty(self.shape, dtype=torch.float32, device=self.device)
+        check(load().qnn_depthwise_dequant(self.handle, ptr(out), stream_ptr()), "qnn_depthwise_dequant")
+        return out
+
+    def out_hw(self, H, W):
+        Ho, Wo = ctypes.c_int(0), ctypes.c_int(0)
+        check(load().qnn_depthwise_out_hw(self.handle, int(H), int(W), ctypes.byref(Ho), ctypes.byref(Wo)),
+              "qnn_depthwise_out_hw")
+        return Ho.value, Wo.value
+
+    def __del__(self):
+        try:
+            _release("qnn_depthwise_free", self.handle)
+            self.handle = ctypes.c_void_p(None)
+        except Exception:
+            pass
+
+
+def depthwise(w, x, x_store, x_bits, N, H, W, bn_inv=None, bn_shift=None, fn=FN_NONE, act_bits=0, out_store=STORE_F32,
+              out=None, epilogue=None):
+    """qnn_depthwise_forward: x is a float32 NHWC CUDA tensor (x_store = STORE_F32) or int32 packed words as pack()
+    writes them.  Returns (y, Ho, Wo): y float32 (N, Ho, Wo, C * M) or int32 (N * Ho * Wo, words).  `epilogue`: a ready
+    Epilogue instead of the keyword fields (tests of the refusals).  A refusal with QNN_EUNSUPPORTED raises QnnUnsupported."""
+    Ho, Wo = w.out_hw(H, W)
+    if Ho <= 0 or Wo <= 0:
+        raise QnnError("depthwise: empty output: %dx%d input, %dx%d window dilated %dx%d, stride %d, %s padding"
+                       % (H, W, w.shape[0], w.shape[1], w.dilation[0], w.dilation[1], w.stride,
+                          "same" if w.same_pad else "valid"))
+    if x_store == STORE_F32:
+        x = require_cuda(x, "depthwise")
+    elif not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.int32 and x.is_contiguous()):
+        raise QnnError("depthwise: a packed input must be a contiguous int32 CUDA tensor")
+    if out_store == STORE_F32:
+        shape, dt = (N, Ho, Wo, w.cout), torch.float32
+    else:
+        shape, dt = (N * Ho * Wo, words(out_store, w.cout)), torch.int32
+    if out is None:
+        y = torch.empty(shape, dtype=dt, device=x.device)
+    else:
+        if tuple(out.shape) != shape or out.dtype != dt or not out.is_contiguous() or out.device != x.device:
+            raise QnnError("depthwise: `out` must be a contiguous %s tensor of shape %s on %s" % (dt, shape, x.device))
+        y = out
+    epi = epilogue if epilogue is not None else make_epilogue(bn_inv, bn_shift, fn, act_bits, 1, out_store, flags=0)
+    rc = load().qnn_depthwise_forward(w.handle, ptr(x), int(x_store), int(x_bits), int(N), int(H), int(W),
+                                      ctypes.byref(epi), ptr(y), stream_ptr())
+    if rc == QNN_EUNSUPPORTED:
+        raise QnnUnsupported("qnn_depthwise_forward: " + load().qnn_last_error().decode(errors="replace"))
+    check(rc, "qnn_depthwise_forward")
+    return y, Ho, Wo

@@ -18,6 +18,9 @@
                       where every branch hands codes of one store) and the new-form spatial ops {"op": "crop"},
                       {"op": "upsample"} and {"op": "zeropad", "pad": ((t, b), (l, r))} (qnn_spatial2d_forward: behind
                       a low-bit clip the codes are moved and stay packed); nets.Model falls to it for such a spec.
+                      Also the one fused home of {"op": "dwconv"} (depthwise convolution, qnn_depthwise_forward): a
+                      following bn and low-bit activation go into its epilogue and a packed producer into its input, so
+                      pack -> dwconv -> 1x1 conv keeps codes throughout.
   LayerModel          the Keras-compatible layer objects called one by one (float32 NHWC in, float32 NHWC out per
                       layer: "M0" traffic model); nets.Model.conv_output reads intermediate tensors through it.
 
@@ -35,6 +38,8 @@ from . import _abi
 from .layers.binary_layers import BinaryConv2D, BinaryDense
 from .layers.quantized_layers import QuantizedConv2D, QuantizedDense
 from .layers.ternary_layers import TernaryConv2D, TernaryDense
+from .layers.depthwise import (DepthwiseConv2D, BinaryDepthwiseConv2D, QuantizedDepthwiseConv2D,
+                               TernaryDepthwiseConv2D)
 from .layers import binary_ops, quantized_ops, ternary_ops
 
 F32 = np.float32
@@ -166,8 +171,9 @@ def _weights_fit(op, store):
 
 
 def _dilation(op):
-    """dilation_rate of a conv op as a pair ((1, 1) where the spec says nothing: dense ops, ordinary windows)."""
-    d = op.get("dilation_rate", (1, 1))
+    """dilation_rate of a conv op as a pair ((1, 1) where the spec says nothing: dense ops, ordinary windows); a dwconv op
+    carries it as `dilation`."""
+    d = op.get("dilation", (1, 1)) if op["op"] == "dwconv" else op.get("dilation_rate", (1, 1))
     return (int(d), int(d)) if np.isscalar(d) else (int(d[0]), int(d[1]))
 
 
@@ -190,6 +196,12 @@ def _prepack(op, store, device, stride=1, same_pad=True):
     kernel = torch.as_tensor(np.ascontiguousarray(op["kernel"], dtype=F32)).to(device)
     bias = op.get("bias")
     bias = torch.as_tensor(np.ascontiguousarray(bias, dtype=F32)).to(device) if bias is not None else None
+    if op["op"] == "dwconv":                 # Keras' depthwise kernel (kh, kw, C, depth_multiplier)
+        M = int(op.get("depth_multiplier", kernel.shape[3]))
+        if kernel.dim() != 4 or kernel.shape[3] != M:
+            raise ValueError("dwconv: kernel %s does not match depth_multiplier %d" % (tuple(kernel.shape), M))
+        return _abi.DepthwiseWeights(_wkind(op), int(op.get("nb", 1)), float(op.get("H", 1.0)), kernel, bias,
+                                     stride, same_pad, store, dilation=_dilation(op))
     return _abi.Weights(_wkind(op), int(op.get("nb", 1)), float(op.get("H", 1.0)), kernel, bias,
                         stride, same_pad, store, dilation=_dilation(op))
 
@@ -431,6 +443,12 @@ def _concat_f32(tensors, log=None):
     return y.reshape(shape)
 
 
+def _refuse_dwconv(spec, who):
+    """The fused engines plan full convolutions only: a spec that holds a depthwise convolution runs on GraphModel."""
+    if any(op["op"] == "dwconv" for op in spec):
+        raise _abi.NotFusable("%s: op 'dwconv' (depthwise convolution) is not expressed by this engine; use GraphModel" % who)
+
+
 def _refuse_concat(spec, who):
     """The fused engines and the layer-by-layer one read one tensor per op (an add: two); GraphModel runs a spec whose
     branches meet by stacking channels."""
@@ -577,6 +595,7 @@ class FusedModel(_DomainFlag):
         self.steps = []
         self._keep = []
         _refuse_concat(spec, "FusedModel")
+        _refuse_dwconv(spec, "FusedModel")
         _refuse_spatial(spec, "FusedModel")
         _refuse_max_acts(spec, "FusedModel")
         groups = self._group(spec)
@@ -987,7 +1006,7 @@ class GraphModel:
     def _grid_store(self, c):
         """The store at which contraction op `c` reads ternary codes {-1, 0, 1} (_contract), None for float weights."""
         op = self.spec[c]
-        wstore = _wstore(op) if op["op"] in ("conv", "dense") else None
+        wstore = _wstore(op) if op["op"] in ("conv", "dense", "dwconv") else None
         if wstore is None:
             return None
         if op["kind"] == "ternary" and TERNARY_T2:
@@ -1161,6 +1180,58 @@ class GraphModel:
             return _abi.conv2d(w, xin, xs, 0, N, H, W, inv, shift)[0]
         return _abi.dense(w, xin, _abi.STORE_F32, 0, xin.shape[0], inv, shift)
 
+    def _dwconv(self, i, op, src):
+        """Depthwise op `i` on `src` (include/qnn_abi_depthwise.h): (result, index of the last op fused into it).  The
+        planner rules of a conv: a following BN that is the tensor's only consumer goes into the epilogue, a packed producer
+        (codes of the store this op joins at) is read as it is and an unmaterialised clip is packed on load.  Beyond a
+        conv, a low-bit clip that alone reads the (BN) output goes into the epilogue too and the result stays packed at
+        the clip's width -- the entry has no pack-on-load form, and the 1x1 conv behind a separable block reads the codes.
+        A batch-scaled activation is always read as float32 (never as scaled codes)."""
+        g, spec, last = self.graph, self.spec, i
+        inv = shift = None
+        if g.cons.get(g.names[last], []) == [last + 1] and spec[last + 1]["op"] == "bn":
+            inv, shift = g.bn[last + 1]
+            last += 1
+        fn, act_bits, out_store = _abi.FN_NONE, 0, _abi.STORE_F32
+        if last + 1 < len(spec) and g.cons.get(g.names[last], []) == [last + 1] and spec[last + 1]["op"] == "act" and \
+                _act_code(spec[last + 1]) is not None:
+            fn, act_bits = _act_code(spec[last + 1])
+            out_store = _abi.STORE_BIN if act_bits == 1 else _abi.store_for_bits(act_bits)
+            last += 1
+        wstore = _wstore(op)
+        xs, xbits, xt = _abi.STORE_F32, 0, None
+        if isinstance(src, _Packed):
+            want = self._grid_store(i) if src.grid else _join_store(src.bits, wstore) if wstore is not None else None
+            if wstore is not None and want == src.store and len(src.shape) == 4:
+                xs, xbits, xt = src.store, src.bits, src.t
+            else:                            # another store (or float weights): the values are on the grid, clip them again
+                cfn = _abi.FN_GRID if src.grid else _abi.FN_BINARY_TANH if src.store == _abi.STORE_BIN else _abi.FN_QUANTIZED_TANH
+                v = _Virtual(src.to_f32(), cfn, src.bits, None)
+                v._mat = v.pre
+                src = v
+        if xt is None and isinstance(src, _Virtual) and wstore is not None and src.pre.dim() == 4:
+            if src.fn == _abi.FN_GRID:
+                xs = self._grid_store(i)
+                xbits = 1
+                xt = _abi.pack(src.pre, src.pre.shape[-1], _abi.FN_GRID, 1, xs)
+            else:
+                xbits = 1 if src.fn == _abi.FN_BINARY_TANH else src.nb
+                xs = _join_store(xbits, wstore)
+                xt = _abi.pack(src.pre, src.pre.shape[-1], src.fn, src.nb if src.fn in _abi.QUANT_FNS else 1, xs)
+            if self.kernel_log is not None:
+                self.kernel_log.append("pack")
+        shape = src.shape if isinstance(src, _Packed) else src.pre.shape if isinstance(src, _Virtual) else None
+        if xt is None:
+            xt = self._plain(src).contiguous()
+            shape = xt.shape
+        N, H, W, C = shape
+        y, Ho, Wo = _abi.depthwise(g.weights(i, xs), xt, xs, xbits, N, H, W, inv, shift, fn, act_bits, out_store)
+        if self.kernel_log is not None:
+            self.kernel_log.append(_abi.last_kernel())
+        if out_store != _abi.STORE_F32:
+            y = _Packed(y, out_store, act_bits, (N, Ho, Wo, g.weights(i, xs).cout))
+        return y, last
+
     def forward(self, x):
         g, spec = self.graph, self.spec
         env = {"input": _images(x, "GraphModel.forward")}
@@ -1183,6 +1254,10 @@ class GraphModel:
                     skip.add(i + 1)
                     name = g.names[i + 1]
                 y = self._contract(i, op, src, inv, shift)
+            elif kind == "dwconv":
+                y, last = self._dwconv(i, op, src)
+                skip.update(range(i + 1, last + 1))
+                name = g.names[last]
             elif kind == "bn":
                 y = _bn_apply(self._plain(src), *g.bn[i])
             elif kind == "add":
@@ -1302,6 +1377,7 @@ class ResidualFusedModel(_DomainFlag):
         if first_layer not in ("auto", "exact", "image"):
             raise ValueError("first_layer must be 'auto', 'exact' or 'image', got %r" % (first_layer,))
         _refuse_concat(spec, "ResidualFusedModel")
+        _refuse_dwconv(spec, "ResidualFusedModel")
         _refuse_spatial(spec, "ResidualFusedModel")
         _refuse_max_acts(spec, "ResidualFusedModel")
         self.first_layer = first_layer
@@ -1863,10 +1939,24 @@ class LayerModel:
         self.graph = _SpecGraph(spec, device)
         prev_act = {}
         for i, op in enumerate(spec):
-            if op["op"] not in ("conv", "dense"):
+            if op["op"] not in ("conv", "dense", "dwconv"):
                 continue
             kw = dict(use_bias=op.get("bias") is not None, device=device)
-            if op["op"] == "conv":
+            if op["op"] == "dwconv":
+                kh, kw_, cin, M = op["kernel"].shape
+                kw.update(strides=tuple(op.get("strides", (1, 1))), padding=op.get("padding", "same"),
+                          dilation_rate=_dilation(op), depth_multiplier=int(op.get("depth_multiplier", M)))
+                H = float(op.get("H", 1.0))
+                if op["kind"] == "binary":
+                    layer = BinaryDepthwiseConv2D((kh, kw_), H=H, **kw)
+                elif op["kind"] == "quantized":
+                    layer = QuantizedDepthwiseConv2D((kh, kw_), H=H, nb=op["nb"], **kw)
+                elif op["kind"] == "ternary":
+                    layer = TernaryDepthwiseConv2D((kh, kw_), H=H, **kw)
+                else:
+                    layer = DepthwiseConv2D((kh, kw_), **kw)
+                layer.build((None, None, None, cin))
+            elif op["op"] == "conv":
                 kh, kw_, cin, cout = op["kernel"].shape
                 kw.update(kernel_size=(kh, kw_), strides=tuple(op.get("strides", (1, 1))),
                           padding=op.get("padding", "same"), dilation_rate=_dilation(op))
@@ -1915,7 +2005,7 @@ class LayerModel:
             src, d = env[sname], None
             if kind == "add":
                 y = _add(src, env[op["b"]])
-            elif kind in ("conv", "dense"):
+            elif kind in ("conv", "dense", "dwconv"):
                 layer = self.layers[i]
                 layer.input_domain = dom.get(sname) if self.fuse_input_activation else None
                 y = layer(src)

@@ -320,10 +320,11 @@ class Model:
                 self.engine = engine.ResidualFusedModel(spec, device,
                                                         first_layer=first_layer if first_layer in ("auto", "image") else "exact")
             except _abi.NotFusable:
-                # only the batch-scaled activations (float32 between the layers), channel concatenation and the new-form
+                # only the batch-scaled activations (float32 between the layers), channel concatenation, depthwise
+                # convolution and the new-form
                 # spatial ops (crop, upsample, pair-form zeropad) are handed on; anything else the residual engine
                 # refuses stays an error
-                if not any((op["op"] == "act" and op["fn"] in BATCH_SCALED_ACTIVATIONS) or op["op"] == "concat" or
+                if not any((op["op"] == "act" and op["fn"] in BATCH_SCALED_ACTIVATIONS) or op["op"] in ("concat", "dwconv") or
                            (op["op"] in engine._SPATIAL and engine._new_spatial(op)) for op in spec):
                     raise
                 self.engine = engine.GraphModel(spec, device, scaled_codes=scaled_codes)
@@ -548,6 +549,29 @@ def spec_from_keras_npz(path, wbits=None, abits=None):
                   "klm": np.float32(c.get("kernel_lr_multiplier") or 1.0)}
             if kind == "quantized":
                 op["nb"] = int(wbits)
+        elif cls in ("DepthwiseConv2D", "SeparableConv2D"):
+            # keras.layers.DepthwiseConv2D -> dwconv (float weights); SeparableConv2D -> a bias-less, activation-free
+            # dwconv and the 1x1 conv of its pointwise_kernel with the layer's bias, strides (1, 1)
+            _spatial_data_format(c, name)
+            if c.get("activation") not in (None, "linear"):
+                raise ValueError("layer %r has activation=%r; only 'linear' is supported in a %s" % (name, c["activation"], cls))
+            sep = cls == "SeparableConv2D"
+            bias = d[name + "/bias"] if c.get("use_bias", True) else None
+            dw = {"op": "dwconv", "kind": "float", "kernel": d[name + "/depthwise_kernel"], "bias": None if sep else bias,
+                  "strides": tuple(int(v) for v in c["strides"]), "padding": str(c["padding"]).lower(),
+                  "dilation": tuple(int(v) for v in c.get("dilation_rate", (1, 1))),
+                  "depth_multiplier": int(c.get("depth_multiplier", 1)), "H": 1.0}
+            if sep:
+                if src is not None:
+                    dw["src"] = src
+                dw["dst"] = name + "_depthwise"
+                spec.append(dw)
+                src = dw["dst"]
+                op = {"op": "conv", "kind": "float", "kernel": d[name + "/pointwise_kernel"], "bias": bias,
+                      "strides": (1, 1), "padding": "valid", "klm": np.float32(1.0)}
+                c = dict(c, dilation_rate=(1, 1))       # the dilation is the depthwise half's
+            else:
+                op = dw
         elif cls in ("TernaryConv2D", "TernaryDense"):
             op = {"op": "conv" if cls == "TernaryConv2D" else "dense", "kind": "ternary",
                   "kernel": d[name + "/kernel"], "bias": d[name + "/bias"] if c.get("use_bias", True) else None,
