@@ -217,6 +217,9 @@ typedef struct qnn_epilogue {
  *                        qnn_fold_prepare built into the handle
  *   QNN_EPI_NO_FIRST_WIDE  the byte first layer on 32-pixel-wide images (pooled int4 or float32 output): two 16-column
  *                        strips per image, each with its column halo, instead of one strip that is the whole row
+ *   QNN_EPI_NO_HALO_EDGE k_conv_mfma_halo on images one 8 x 2 tile wide (16 columns) or one 4 x 4 tile large (8 x 8): the
+ *                        general staging (the tile's whole region with its halo, border pixels loaded out of range)
+ *                        instead of the image's pixels alone beside a padding written once per wave
  * The restricted-domain first-layer kernels are selected by the TYPED input stores QNN_STORE_F32_IMAGE /
  * QNN_STORE_F32_UNIT of the call (above), never by a switch.
  */
@@ -229,6 +232,7 @@ typedef struct qnn_epilogue {
 #define QNN_EPI_NO_FIRST_BITS  64u
 #define QNN_EPI_NO_HALO_TAB    128u
 #define QNN_EPI_NO_FIRST_WIDE  256u
+#define QNN_EPI_NO_HALO_EDGE   512u
 
 /* ---- library ------------------------------------------------------------ */
 int         qnn_version(void);

@@ -231,7 +231,7 @@ def set_conv_impl(impl):
 
 
 EPI_NO_STRIP, EPI_NO_STRIP64, EPI_NO_HALO, EPI_NO_LDS16, EPI_NO_FP6 = 1, 2, 4, 8, 16      # qnn_epilogue_t.flags (qnn_abi.h)
-EPI_NO_FIRST_TAB, EPI_NO_FIRST_BITS, EPI_NO_HALO_TAB, EPI_NO_FIRST_WIDE = 32, 64, 128, 256
+EPI_NO_FIRST_TAB, EPI_NO_FIRST_BITS, EPI_NO_HALO_TAB, EPI_NO_FIRST_WIDE, EPI_NO_HALO_EDGE = 32, 64, 128, 256, 512
 _default_flags = 0
 _default_first = None
 
@@ -240,7 +240,7 @@ def set_option(key, value):
     """TEST / TOOL HELPER of this binding -- the C library keeps no such state (round 4: qnn_set_option is gone from the
     ABI).  Sets what calls made THROUGH THIS MODULE pass per call when the caller says nothing:
       "strip" 0 / 1, "strip64" -1 / 0 / 1, "halo" 0 / 1, "lds16" 0 / 1, "fp6" 0 / 1, "first_tab" 0 / 1, "first_wide" 0 / 1,
-      "halo_tab" 0 / 1   -> qnn_epilogue_t.flags
+      "halo_tab" 0 / 1, "halo_edge" 0 / 1   -> qnn_epilogue_t.flags
                   (QNN_EPI_NO_*): kernel selection only, results bit-identical;
       "first_bits" 0 / 1   -> QNN_EPI_NO_FIRST_BITS in the epilogue that Fold() hands to qnn_fold_prepare: folds of the image
                   entry prepared while it is 0 keep the mode-3 constants in their operand table;
@@ -248,7 +248,8 @@ def set_option(key, value):
                   QNN_STORE_F32_IMAGE (the typed stores the engines pass explicitly)."""
     global _default_flags, _default_first
     bits = {"strip": EPI_NO_STRIP, "strip64": EPI_NO_STRIP64, "halo": EPI_NO_HALO, "lds16": EPI_NO_LDS16, "fp6": EPI_NO_FP6,
-            "first_tab": EPI_NO_FIRST_TAB, "first_wide": EPI_NO_FIRST_WIDE, "first_bits": EPI_NO_FIRST_BITS, "halo_tab": EPI_NO_HALO_TAB}
+            "first_tab": EPI_NO_FIRST_TAB, "first_wide": EPI_NO_FIRST_WIDE, "first_bits": EPI_NO_FIRST_BITS, "halo_tab": EPI_NO_HALO_TAB,
+            "halo_edge": EPI_NO_HALO_EDGE}
     if key in bits:
         _default_flags = (_default_flags | bits[key]) if int(value) == 0 else (_default_flags & ~bits[key])
     elif key in ("first_fixed", "first_image"):

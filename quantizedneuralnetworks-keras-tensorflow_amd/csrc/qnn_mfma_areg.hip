@@ -799,7 +799,17 @@ __global__ __launch_bounds__(256, (OUT == QNN_STORE_F32 ? 2 : 3)) void k_conv_mf
 // waves per SIMD leave and spilled (the bnn step went from 66.6 to 83.8 us).
 // What a FOLD wave needs per lane beside the filters -- slope, FMA constant, offset, pooling sign -- comes from the fold
 // handle's table (qnn_fold.h, qnn_halo_epi_entry; QNN_EPI_NO_HALO_TAB: derived here by the same function).
-template <int TWP, int NW, bool HEAD, bool FOLD = false, bool FP6 = false>
+// EDGE (profiles/halo_edge/): the launcher's choice when an 8 x 2 tile spans the image width (16-column images, CIFAR B0)
+// or a 4 x 4 tile is the image (8 x 8, CIFAR C0 and the classifier form); QNN_EPI_NO_HALO_EDGE keeps the general form.
+// Region layout, fragment reads, MFMA loop and epilogue are the same; what differs is who writes the region.  Its columns
+// 0 and RW - 1 (TWP 4: its rows 0 and RH - 1 too) are padding for EVERY tile of such an image, so each wave writes the
+// padding once, before its first tile (the whole region: zero bytes, FP6: code 0 through grp, u = 8 in every field), and
+// a tile stages the image's pixels alone: chunk j = lane + 64 i is half j & 1 of pixel j >> 1 of a block 2 TWP wide, whose
+// 16 j bytes are one contiguous piece of the image from a wave-uniform origin -- 6 rows = 3 full rounds (TWP 8; the rows
+// above the first and below the last tile still fall out of the image's buffer descriptor) or the 8 x 8 image = 2 rounds
+// (TWP 4) instead of 4 rounds with a partial last one; no division by RW, no edge masks, no out-of-range select.  Task
+// order and grid are unchanged (a tile per wave and step).
+template <int TWP, int NW, bool HEAD, bool FOLD = false, bool FP6 = false, bool EDGE = false>
 __global__ __launch_bounds__(NW * 64, 1) void k_conv_mfma_halo(MfmaGeom mg, EpiArgs e, const uint8_t* __restrict__ x,
                                                                const uint8_t* __restrict__ wq8, void* __restrict__ y,
                                                                int ntiles, FastDiv fd_tpi, int txn, FastDiv fd_txn,
@@ -816,6 +826,11 @@ __global__ __launch_bounds__(NW * 64, 1) void k_conv_mfma_halo(MfmaGeom mg, EpiA
     static_assert(!FP6 || FOLD, "the FP6 form serves the folded layers");
     constexpr int HTAB = FILT + NW * REGION;
     static_assert(NCH <= 256, "four load rounds per lane");
+    // EDGE: the tile spans the image width (TWP 8) or is the image (TWP 4).  Only the pixels of the image are staged:
+    // EW per row on ER rows from region row ROW0, NR full rounds of 64 chunks
+    constexpr int EW = 2 * TWP, ER = TWP == 4 ? RH - 2 : RH, ROW0 = TWP == 4 ? 1 : 0;
+    constexpr int NR = EDGE ? 2 * EW * ER / 64 : 4;
+    static_assert(!EDGE || 2 * EW * ER == 64 * NR, "the image's chunks of a tile fill whole rounds");
     const ConvGeom& g = mg.g;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x;
@@ -919,16 +934,19 @@ __global__ __launch_bounds__(NW * 64, 1) void k_conv_mfma_halo(MfmaGeom mg, EpiA
     unsigned long long edgeL[4], edgeR[4];
     bool wr_ok[4];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
+    for (int i = 0; i < NR; ++i) {
         const int j = lane + 64 * i;
         const int p = j >> 1, half = j & 1;
-        const int ry = p / RW, rx = p - ry * RW;
-        wr_ok[i] = j < NCH;
-        rel[i] = wr_ok[i] ? (ry * g.W + rx) * 32 + half * 16 : (int)0x80000000;
+        const int ry = EDGE ? ROW0 + p / EW : p / RW, rx = EDGE ? 1 + (p & (EW - 1)) : p - ry * RW;
+        wr_ok[i] = EDGE || j < NCH;
+        if constexpr (EDGE) rel[i] = 16 * j;               // (the image is EW pixels wide: the tile's chunks are contiguous)
+        else rel[i] = wr_ok[i] ? (ry * g.W + rx) * 32 + half * 16 : (int)0x80000000;
         wr_addr[i] = regbase + ry * PITCH + rx * 32 + ((half ^ (ry & 1)) << 4);
         wrb_addr[i] = regbase + PLANE + ry * PITCHB + rx * 16 + ((half ^ (ry & 1)) << 3);
-        edgeL[i] = __ballot(rx == 0);
-        edgeR[i] = __ballot(rx == RW - 1);
+        if constexpr (!EDGE) {
+            edgeL[i] = __ballot(rx == 0);
+            edgeR[i] = __ballot(rx == RW - 1);
+        }
     }
     // ---- A fragments: rows mt * 32 + li = 4 * (pooled pixel) + (position in its 2x2 window) ----
     int a_even[2], a_odd[2], ab_even[2], ab_odd[2];
@@ -959,6 +977,20 @@ __global__ __launch_bounds__(NW * 64, 1) void k_conv_mfma_halo(MfmaGeom mg, EpiA
     int n_next = 0;
     auto fetch = [&](int tile) {                       // tile -> (image, tile row, tile column): wave-uniform
         if (tile >= ntiles) return;
+        if constexpr (EDGE) {                          // one tile per row of tiles (TWP 8) or per image (TWP 4)
+            const int n = TWP == 4 ? tile : (int)qnn_div((uint32_t)tile, fd_tpi);
+            const int ty = TWP == 4 ? 0 : tile - n * (int)fd_tpi.d;
+            n_next = n;
+            pq_next = ((long)n * g.Hp + ty * THP) * g.Wp;
+            const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(
+                const_cast<uint8_t*>(x) + (size_t)n * img_bytes, 0, (int)img_bytes, 0x00020000);
+            // TWP 8: the rows above the first and below the last tile fall out of the image's descriptor, as in the other form
+            const int origin = TWP == 4 ? 0 : (2 * ty * THP - 1) * EW * 32;
+#pragma unroll
+            for (int i = 0; i < NR; ++i)
+                L[i] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(xr, rel[i] + origin, 0, 0));
+            return;
+        }
         const int n = (int)qnn_div((uint32_t)tile, fd_tpi);
         const int rest = tile - n * (int)fd_tpi.d;
         const int ty = (int)qnn_div((uint32_t)rest, fd_txn);
@@ -977,24 +1009,45 @@ __global__ __launch_bounds__(NW * 64, 1) void k_conv_mfma_halo(MfmaGeom mg, EpiA
             L[i] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(xr, voff, 0, 0));
         }
     };
+    // 32 codes -> 32 six-bit fields (qnn_fp6_channel) of code XOR 8: per pair of words one rotate each and two
+    // v_bitop3_b32 per output word, (x & M1) ^ K then ^ (x' & M2).  The XOR commutes with the rotate and the two
+    // masks are disjoint, so K = (8s & M1) | (rot(8s) & M2) carries the XOR bits of both parts; 24 bytes per chunk
+    auto grp = [](uint32_t x0, uint32_t y0, uint32_t& d0, uint32_t& d1, uint32_t& d2) {
+        constexpr uint32_t E = 0x88888888u, ER = 0x22222222u;      // the XOR 8 of eight codes, and rotated left by two
+        constexpr uint32_t AND_XOR = 0x6A;                         // v_bitop3_b32 truth table of (a & b) ^ c
+        const uint32_t xr = __builtin_amdgcn_alignbit(x0, x0, 30), yr = __builtin_amdgcn_alignbit(y0, y0, 30);
+        d0 = __builtin_amdgcn_bitop3_b32(x0, 0x0F00F00Fu, (E & 0x0F00F00Fu) | (ER & 0xC03C03C0u), AND_XOR);
+        d0 = __builtin_amdgcn_bitop3_b32(xr, 0xC03C03C0u, d0, AND_XOR);
+        d1 = __builtin_amdgcn_bitop3_b32(xr, 0x03C03C03u, (ER & 0x03C03C03u) | (E & 0xF00F00F0u), AND_XOR);
+        d1 = __builtin_amdgcn_bitop3_b32(y0, 0xF00F00F0u, d1, AND_XOR);
+        d2 = __builtin_amdgcn_bitop3_b32(y0, 0x00F00F00u, (E & 0x00F00F00u) | (ER & 0x3C03C03Cu), AND_XOR);
+        d2 = __builtin_amdgcn_bitop3_b32(yr, 0x3C03C03Cu, d2, AND_XOR);
+    };
+    if constexpr (EDGE) {
+        // The region's padding, once: stage() writes the image's pixels only, so what lies around them -- columns 0 and
+        // RW - 1, with TWP 4 also rows 0 and RH - 1 -- keeps what a chunk loaded as zeros is staged as.  The whole region is
+        // filled (LDS is not zero on entry): a plane holds one 16-byte value everywhere, zero bytes in the int8 form, the
+        // image of code 0 (u = 8 in every field) through grp in the FP6 one.  The wave's own LDS operations stay in order.
+        uint4 padA = make_uint4(0, 0, 0, 0), padB = padA;
+        if constexpr (FP6) {
+            uint32_t z[3];
+            grp(0u, 0u, z[0], z[1], z[2]);                 // both word pairs of a zero chunk: d[0..2] = d[3..5]
+            padA = make_uint4(z[0], z[1], z[2], z[0]);
+            padB = make_uint4(z[1], z[2], z[1], z[2]);     // two 8-byte slots
+        }
+        constexpr int PA = FP6 ? PLANE : 2 * PLANE;        // (int8: both k-block planes are zero bytes)
+        static_assert(PA % 16 == 0 && REGION % 16 == 0, "the padding is written in 16-byte pieces");
+#pragma unroll
+        for (int o = 0; o < PA; o += 64 * 16)
+            if (o + 64 * 16 <= PA || o + lane * 16 < PA) *reinterpret_cast<uint4*>(smem + regbase + o + lane * 16) = padA;
+#pragma unroll
+        for (int o = PA; o < REGION; o += 64 * 16)
+            if (o + 64 * 16 <= REGION || o + lane * 16 < REGION) *reinterpret_cast<uint4*>(smem + regbase + o + lane * 16) = padB;
+    }
     auto stage = [&]() {
         if constexpr (FP6) {
-            // 32 codes -> 32 six-bit fields (qnn_fp6_channel) of code XOR 8: per pair of words one rotate each and two
-            // v_bitop3_b32 per output word, (x & M1) ^ K then ^ (x' & M2).  The XOR commutes with the rotate and the two
-            // masks are disjoint, so K = (8s & M1) | (rot(8s) & M2) carries the XOR bits of both parts; 24 bytes per chunk
-            auto grp = [](uint32_t x0, uint32_t y0, uint32_t& d0, uint32_t& d1, uint32_t& d2) {
-                constexpr uint32_t E = 0x88888888u, ER = 0x22222222u;      // the XOR 8 of eight codes, and rotated left by two
-                constexpr uint32_t AND_XOR = 0x6A;                         // v_bitop3_b32 truth table of (a & b) ^ c
-                const uint32_t xr = __builtin_amdgcn_alignbit(x0, x0, 30), yr = __builtin_amdgcn_alignbit(y0, y0, 30);
-                d0 = __builtin_amdgcn_bitop3_b32(x0, 0x0F00F00Fu, (E & 0x0F00F00Fu) | (ER & 0xC03C03C0u), AND_XOR);
-                d0 = __builtin_amdgcn_bitop3_b32(xr, 0xC03C03C0u, d0, AND_XOR);
-                d1 = __builtin_amdgcn_bitop3_b32(xr, 0x03C03C03u, (ER & 0x03C03C03u) | (E & 0xF00F00F0u), AND_XOR);
-                d1 = __builtin_amdgcn_bitop3_b32(y0, 0xF00F00F0u, d1, AND_XOR);
-                d2 = __builtin_amdgcn_bitop3_b32(y0, 0x00F00F00u, (E & 0x00F00F00u) | (ER & 0x3C03C03Cu), AND_XOR);
-                d2 = __builtin_amdgcn_bitop3_b32(yr, 0x3C03C03Cu, d2, AND_XOR);
-            };
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
+            for (int i = 0; i < NR; ++i) {
                 const uint4 q = L[i];
                 uint32_t d[6];
                 grp(q.x, q.y, d[0], d[1], d[2]);
@@ -1007,7 +1060,7 @@ __global__ __launch_bounds__(NW * 64, 1) void k_conv_mfma_halo(MfmaGeom mg, EpiA
             return;
         }
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
+        for (int i = 0; i < NR; ++i) {
             const uint4 q = L[i];
             const uint4 k0 = make_uint4((q.x << 4) & 0xF0F0F0F0u, q.x & 0xF0F0F0F0u, (q.y << 4) & 0xF0F0F0F0u, q.y & 0xF0F0F0F0u);
             const uint4 k1 = make_uint4((q.z << 4) & 0xF0F0F0F0u, q.z & 0xF0F0F0F0u, (q.w << 4) & 0xF0F0F0F0u, q.w & 0xF0F0F0F0u);
@@ -1182,7 +1235,7 @@ __global__ __launch_bounds__(NW * 64, 1) void k_conv_mfma_halo(MfmaGeom mg, EpiA
     }
 }
 
-template <int TWP, int NW, bool HEAD, bool FOLD, bool FP6>
+template <int TWP, int NW, bool HEAD, bool FOLD, bool FP6, bool EDGE>
 void launch_halo_one_f(const MfmaGeom& mg, const EpiArgs& e, const void* x, const uint8_t* w, const int32_t* wsum, void* y,
                        const HeadArgs& hd, hipStream_t s) {
     const ConvGeom& g = mg.g;
@@ -1198,25 +1251,37 @@ void launch_halo_one_f(const MfmaGeom& mg, const EpiArgs& e, const void* x, cons
     const int cap = 256 / ny > 0 ? 256 / ny : 1;             // one resident workgroup per CU
     if (gx > cap) gx = cap;
     static const bool lds_ok = [] {
-        (void)hipFuncSetAttribute((const void*)k_conv_mfma_halo<TWP, NW, HEAD, FOLD, FP6>,
+        (void)hipFuncSetAttribute((const void*)k_conv_mfma_halo<TWP, NW, HEAD, FOLD, FP6, EDGE>,
                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         return true;
     }();
     (void)lds_ok;
-    hipLaunchKernelGGL((k_conv_mfma_halo<TWP, NW, HEAD, FOLD, FP6>), dim3((unsigned)gx, (unsigned)ny), dim3(NW * 64), lds, s, mg,
+    hipLaunchKernelGGL((k_conv_mfma_halo<TWP, NW, HEAD, FOLD, FP6, EDGE>), dim3((unsigned)gx, (unsigned)ny), dim3(NW * 64), lds, s, mg,
                        e, (const uint8_t*)x, w, y, ntiles, qnn_fastdiv((uint32_t)tpi), txn, qnn_fastdiv((uint32_t)txn),
                        (uint32_t)(g.H * g.W * 32), hd, wsum);
 }
 
 // a usable fold in the "bits" form (qnn_fold.h mode 2: e.fold_c set) takes the folded epilogue; with an FP6 filter image
 // on the FP6 form, with the classifier or without
+template <int TWP, int NW, bool HEAD, bool EDGE>
+void launch_halo_one_e(const MfmaGeom& mg, const EpiArgs& e, const void* x, const uint8_t* w, HaloFp6 w6, void* y,
+                       const HeadArgs& hd, hipStream_t s) {
+    const bool fold = e.fold_a && e.fold_c && e.fn == QNN_FN_QUANTIZED_TANH;
+    if (fold && w6.w) return launch_halo_one_f<TWP, NW, HEAD, true, true, EDGE>(mg, e, x, w6.w, w6.wsum, y, hd, s);
+    if (fold) launch_halo_one_f<TWP, NW, HEAD, true, false, EDGE>(mg, e, x, w, nullptr, y, hd, s);
+    else launch_halo_one_f<TWP, NW, HEAD, false, false, EDGE>(mg, e, x, w, nullptr, y, hd, s);
+}
+
+// The EDGE staging (only the image's pixels, constant padding) when an 8 x 2 tile spans the image width or a 4 x 4 tile
+// is the image; QNN_EPI_NO_HALO_EDGE keeps the general staging
 template <int TWP, int NW, bool HEAD>
 void launch_halo_one(const MfmaGeom& mg, const EpiArgs& e, const void* x, const uint8_t* w, HaloFp6 w6, void* y,
                      const HeadArgs& hd, hipStream_t s) {
-    const bool fold = e.fold_a && e.fold_c && e.fn == QNN_FN_QUANTIZED_TANH;
-    if (fold && w6.w) return launch_halo_one_f<TWP, NW, HEAD, true, true>(mg, e, x, w6.w, w6.wsum, y, hd, s);
-    if (fold) launch_halo_one_f<TWP, NW, HEAD, true, false>(mg, e, x, w, nullptr, y, hd, s);
-    else launch_halo_one_f<TWP, NW, HEAD, false, false>(mg, e, x, w, nullptr, y, hd, s);
+    const ConvGeom& g = mg.g;
+    const bool spans = TWP == 8 ? g.Wp == 8 : g.Wp == 4 && g.Hp == 4;
+    if (spans && g.W == 2 * g.Wp && g.H == 2 * g.Hp && !(e.flags & QNN_EPI_NO_HALO_EDGE))
+        launch_halo_one_e<TWP, NW, HEAD, true>(mg, e, x, w, w6, y, hd, s);
+    else launch_halo_one_e<TWP, NW, HEAD, false>(mg, e, x, w, w6, y, hd, s);
 }
 
 // 0 = launched.  The pooled map must tile into 8 x 2 or 4 x 4 rectangles; everything else stays on k_conv_mfma_areg.
