@@ -27,6 +27,8 @@ from .layers.merge import Concatenate  # noqa: F401
 from .layers.spatial import ZeroPadding2D, Cropping2D, UpSampling2D  # noqa: F401
 from .layers.depthwise import (DepthwiseConv2D, BinaryDepthwiseConv2D, QuantizedDepthwiseConv2D,  # noqa: F401
                                TernaryDepthwiseConv2D)
+from .layers.conv_transpose import (Conv2DTranspose, BinaryConv2DTranspose, QuantizedConv2DTranspose,  # noqa: F401
+                                    TernaryConv2DTranspose)
 
 __all__ = [
     "binary_tanh", "binarize", "binary_sigmoid", "quantize", "quantized_tanh", "quantized_relu", "quantized_leakyrelu",
@@ -38,4 +40,5 @@ __all__ = [
     "Concatenate",
     "ZeroPadding2D", "Cropping2D", "UpSampling2D",
     "DepthwiseConv2D", "BinaryDepthwiseConv2D", "QuantizedDepthwiseConv2D", "TernaryDepthwiseConv2D",
+    "Conv2DTranspose", "BinaryConv2DTranspose", "QuantizedConv2DTranspose", "TernaryConv2DTranspose",
 ]

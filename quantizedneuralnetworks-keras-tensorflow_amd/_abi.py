@@ -1,5 +1,5 @@
 """ctypes binding of include/qnn_abi.h, qnn_abi_dilation.h, qnn_abi_qact.h, qnn_abi_maxact.h, qnn_abi_pool.h,
-qnn_abi_scaled.h, qnn_abi_concat.h, qnn_abi_spatial.h and qnn_abi_depthwise.h (csrc/libqnn_hip.so).
+qnn_abi_scaled.h, qnn_abi_concat.h, qnn_abi_spatial.h, qnn_abi_depthwise.h and qnn_abi_tconv.h (csrc/libqnn_hip.so).
 
 The library is loaded eagerly and loudly: a missing or unloadable .so raises at
 import time of any op that needs it (there is no CPU implementation to fall back
@@ -70,6 +70,10 @@ EXPORTS_SPATIAL = ["qnn_spatial2d_out_hw", "qnn_spatial2d_forward"]
 EXPORTS_DEPTHWISE = ["qnn_depthwise_prepack", "qnn_depthwise_free", "qnn_depthwise_dequant", "qnn_depthwise_out_hw",
                      "qnn_depthwise_forward"]
 DW_MAX_WINDOW = 7
+
+# include/qnn_abi_tconv.h: Conv2DTranspose with float / binary / quantized / ternary weights on float32 and packed codes
+EXPORTS_TCONV = ["qnn_tconv_prepack", "qnn_tconv_free", "qnn_tconv_dequant", "qnn_tconv_out_hw", "qnn_tconv_forward"]
+TC_MAX_WINDOW, TC_MAX_STRIDE = 8, 4
 
 
 class Spatial2D(ctypes.Structure):
@@ -202,8 +206,13 @@ def load():
     lib.qnn_depthwise_dequant.argtypes = [vp, vp, vp]
     lib.qnn_depthwise_out_hw.argtypes = [vp, ci, ci, ctypes.POINTER(ci), ctypes.POINTER(ci)]
     lib.qnn_depthwise_forward.argtypes = [vp, vp, ci, ci, ci, ci, ci, ctypes.POINTER(Epilogue), vp, vp]
+    lib.qnn_tconv_prepack.argtypes = [ci, ci, fl, vp, ci, ci, ci, ci, vp, ci, ci, ci, vp, ctypes.POINTER(vp)]
+    lib.qnn_tconv_free.argtypes = [vp]
+    lib.qnn_tconv_dequant.argtypes = [vp, vp, vp]
+    lib.qnn_tconv_out_hw.argtypes = [vp, ci, ci, ctypes.POINTER(ci), ctypes.POINTER(ci)]
+    lib.qnn_tconv_forward.argtypes = [vp, vp, ci, ci, ci, ci, ci, ctypes.POINTER(Epilogue), vp, vp]
     for name in (EXPORTS + EXPORTS_DILATION + EXPORTS_QACT + EXPORTS_MAXACT + EXPORTS_POOL + EXPORTS_SCALED + EXPORTS_CONCAT
-                 + EXPORTS_SPATIAL + EXPORTS_DEPTHWISE):   # every symbol the headers declare must be exported
+                 + EXPORTS_SPATIAL + EXPORTS_DEPTHWISE + EXPORTS_TCONV):   # every symbol the headers declare must be exported
         getattr(lib, name)
     _lib = lib
     return lib
@@ -986,4 +995,88 @@ def depthwise(w, x, x_store, x_bits, N, H, W, bn_inv=None, bn_shift=None, fn=FN_
     if rc == QNN_EUNSUPPORTED:
         raise QnnUnsupported("qnn_depthwise_forward: " + load().qnn_last_error().decode(errors="replace"))
     check(rc, "qnn_depthwise_forward")
+    return y, Ho, Wo
+
+
+def tconv_out_hw(size, k, stride, same_pad):
+    """Output size of one axis of a transposed convolution (csrc/qnn_conv_geom.h, qnn_tconv_out_pad)."""
+    return size * stride + (0 if same_pad else max(k - stride, 0))
+
+
+def tconv_takes_mfma(kh, kw, stride, store, cout, cin, out_store):
+    """The shape half of the route rule of the matrix-pipe form (include/qnn_abi_tconv.h); the library adds 16-byte
+    aligned pointers and an input image below 2^31 bytes."""
+    return (stride == 2 and kh == kw and 2 <= kh <= 4 and store in (STORE_I4, STORE_I8) and out_store == store and
+            cin % 64 == 0 and cin <= 16384 and cout % 16 == 0)
+
+
+class TConvWeights:
+    """Owner of an opaque qnn_tconv_weights_t handle (include/qnn_abi_tconv.h).  kernel: float32 CUDA tensor in Keras'
+    Conv2DTranspose layout (kh, kw, Cout, Cin); bias: (Cout,) or None."""
+
+    def __init__(self, wkind, wbits, H, kernel, bias, stride, same_pad, store):
+        kernel = require_cuda(kernel, "tconv prepack kernel")
+        if kernel.dim() != 4:
+            raise QnnError("tconv prepack: the kernel must be (kh, kw, Cout, Cin), got %s" % (tuple(kernel.shape),))
+        kh, kw, cout, cin = kernel.shape
+        bias = require_cuda(bias, "tconv prepack bias") if bias is not None else None
+        if bias is not None and bias.numel() != cout:
+            raise QnnError("tconv prepack: bias of %d values for %d filters" % (bias.numel(), cout))
+        self.shape = (kh, kw, cout, cin)
+        self.cout, self.cin = cout, cin
+        self.wkind, self.wbits, self.store = wkind, wbits, store
+        self.stride, self.same_pad = int(stride), bool(same_pad)
+        self.handle = ctypes.c_void_p(None)
+        release_deferred()
+        rc = load().qnn_tconv_prepack(wkind, wbits, float(H), ptr(kernel), kh, kw, cout, cin, ptr(bias), self.stride,
+                                      1 if same_pad else 0, store, stream_ptr(), ctypes.byref(self.handle))
+        if rc == QNN_EUNSUPPORTED:
+            raise QnnUnsupported("qnn_tconv_prepack: " + load().qnn_last_error().decode(errors="replace"))
+        check(rc, "qnn_tconv_prepack")
+        self.device = kernel.device
+
+    def dequant(self):
+        out = torch.empty(self.shape, dtype=torch.float32, device=self.device)
+        check(load().qnn_tconv_dequant(self.handle, ptr(out), stream_ptr()), "qnn_tconv_dequant")
+        return out
+
+    def out_hw(self, H, W):
+        Ho, Wo = ctypes.c_int(0), ctypes.c_int(0)
+        check(load().qnn_tconv_out_hw(self.handle, int(H), int(W), ctypes.byref(Ho), ctypes.byref(Wo)), "qnn_tconv_out_hw")
+        return Ho.value, Wo.value
+
+    def __del__(self):
+        try:
+            _release("qnn_tconv_free", self.handle)
+            self.handle = ctypes.c_void_p(None)
+        except Exception:
+            pass
+
+
+def tconv(w, x, x_store, x_bits, N, H, W, bn_inv=None, bn_shift=None, fn=FN_NONE, act_bits=0, out_store=STORE_F32,
+          out=None, epilogue=None):
+    """qnn_tconv_forward: x is a float32 NHWC CUDA tensor (x_store = STORE_F32) or int32 packed words as pack() writes
+    them.  Returns (y, Ho, Wo): y float32 (N, Ho, Wo, Cout) or int32 (N * Ho * Wo, words).  `epilogue`: a ready Epilogue
+    instead of the keyword fields (tests of the refusals).  A refusal with QNN_EUNSUPPORTED raises QnnUnsupported."""
+    Ho, Wo = w.out_hw(H, W)
+    if x_store == STORE_F32:
+        x = require_cuda(x, "tconv")
+    elif not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.int32 and x.is_contiguous()):
+        raise QnnError("tconv: a packed input must be a contiguous int32 CUDA tensor")
+    if out_store == STORE_F32:
+        shape, dt = (N, Ho, Wo, w.cout), torch.float32
+    else:
+        shape, dt = (N * Ho * Wo, words(out_store, w.cout)), torch.int32
+    if out is None:
+        y = torch.empty(shape, dtype=dt, device=x.device)
+    else:
+        if tuple(out.shape) != shape or out.dtype != dt or not out.is_contiguous() or out.device != x.device:
+            raise QnnError("tconv: `out` must be a contiguous %s tensor of shape %s on %s" % (dt, shape, x.device))
+        y = out
+    epi = epilogue if epilogue is not None else make_epilogue(bn_inv, bn_shift, fn, act_bits, 1, out_store, flags=0)
+    rc = load().qnn_tconv_forward(w.handle, ptr(x), int(x_store), int(x_bits), int(N), int(H), int(W),
+                                  ctypes.byref(epi), ptr(y), stream_ptr())
+    if rc == QNN_EUNSUPPORTED:
+        raise QnnUnsupported("qnn_tconv_forward: " + load().qnn_last_error().decode(errors="replace"))
+    check(rc, "qnn_tconv_forward")
     return y, Ho, Wo

@@ -24,3 +24,15 @@ static inline void qnn_same_pad(int in, int k, int s, int same, int* out, int* b
 static inline void qnn_same_pad_dilated(int in, int k, int s, int d, int same, int* out, int* before) {
     qnn_same_pad(in, d * (k - 1) + 1, s, same, out, before);
 }
+
+// The transposed convolution (tf.nn.conv2d_transpose, include/qnn_abi_tconv.h): the scatter of `in` cells at stride s
+// through a window of k fills `full` = (in - 1) * s + k cells; the output is cells [before, before + out) of it, read as
+// zero beyond `full`.
+// VALID: out = in * s + max(k - s, 0), before = 0 (k < s: the last s - k cells lie beyond `full`).
+// SAME:  out = in * s, before = max(k - s, 0) / 2 (the odd cell is cut after) -- the padding of the forward SAME
+//        convolution that maps `out` cells back to `in`.
+static inline void qnn_tconv_out_pad(int in, int k, int s, int same, int* out, int* before) {
+    const int extra = k > s ? k - s : 0;
+    *out = same ? in * s : in * s + extra;
+    *before = same ? extra / 2 : 0;
+}

@@ -20,7 +20,8 @@
                       a low-bit clip the codes are moved and stay packed); nets.Model falls to it for such a spec.
                       Also the one fused home of {"op": "dwconv"} (depthwise convolution, qnn_depthwise_forward): a
                       following bn and low-bit activation go into its epilogue and a packed producer into its input, so
-                      pack -> dwconv -> 1x1 conv keeps codes throughout.
+                      pack -> dwconv -> 1x1 conv keeps codes throughout.  {"op": "tconv"} (transposed convolution,
+                      qnn_tconv_forward) runs under the same rules; the codes it leaves meet a skip as codes in a concat.
   LayerModel          the Keras-compatible layer objects called one by one (float32 NHWC in, float32 NHWC out per
                       layer: "M0" traffic model); nets.Model.conv_output reads intermediate tensors through it.
 
@@ -40,6 +41,8 @@ from .layers.quantized_layers import QuantizedConv2D, QuantizedDense
 from .layers.ternary_layers import TernaryConv2D, TernaryDense
 from .layers.depthwise import (DepthwiseConv2D, BinaryDepthwiseConv2D, QuantizedDepthwiseConv2D,
                                TernaryDepthwiseConv2D)
+from .layers.conv_transpose import (Conv2DTranspose, BinaryConv2DTranspose, QuantizedConv2DTranspose,
+                                    TernaryConv2DTranspose)
 from .layers import binary_ops, quantized_ops, ternary_ops
 
 F32 = np.float32
@@ -202,6 +205,11 @@ def _prepack(op, store, device, stride=1, same_pad=True):
             raise ValueError("dwconv: kernel %s does not match depth_multiplier %d" % (tuple(kernel.shape), M))
         return _abi.DepthwiseWeights(_wkind(op), int(op.get("nb", 1)), float(op.get("H", 1.0)), kernel, bias,
                                      stride, same_pad, store, dilation=_dilation(op))
+    if op["op"] == "tconv":                  # Keras' Conv2DTranspose kernel (kh, kw, Cout, Cin)
+        if kernel.dim() != 4:
+            raise ValueError("tconv: kernel %s is not (kh, kw, Cout, Cin)" % (tuple(kernel.shape),))
+        return _abi.TConvWeights(_wkind(op), int(op.get("nb", 1)), float(op.get("H", 1.0)), kernel, bias, stride, same_pad,
+                                 store)
     return _abi.Weights(_wkind(op), int(op.get("nb", 1)), float(op.get("H", 1.0)), kernel, bias,
                         stride, same_pad, store, dilation=_dilation(op))
 
@@ -449,6 +457,12 @@ def _refuse_dwconv(spec, who):
         raise _abi.NotFusable("%s: op 'dwconv' (depthwise convolution) is not expressed by this engine; use GraphModel" % who)
 
 
+def _refuse_tconv(spec, who):
+    """The fused engines plan forward convolutions only: a spec that holds a transposed convolution runs on GraphModel."""
+    if any(op["op"] == "tconv" for op in spec):
+        raise _abi.NotFusable("%s: op 'tconv' (transposed convolution) is not expressed by this engine; use GraphModel" % who)
+
+
 def _refuse_concat(spec, who):
     """The fused engines and the layer-by-layer one read one tensor per op (an add: two); GraphModel runs a spec whose
     branches meet by stacking channels."""
@@ -596,6 +610,7 @@ class FusedModel(_DomainFlag):
         self._keep = []
         _refuse_concat(spec, "FusedModel")
         _refuse_dwconv(spec, "FusedModel")
+        _refuse_tconv(spec, "FusedModel")
         _refuse_spatial(spec, "FusedModel")
         _refuse_max_acts(spec, "FusedModel")
         groups = self._group(spec)
@@ -1006,7 +1021,7 @@ class GraphModel:
     def _grid_store(self, c):
         """The store at which contraction op `c` reads ternary codes {-1, 0, 1} (_contract), None for float weights."""
         op = self.spec[c]
-        wstore = _wstore(op) if op["op"] in ("conv", "dense", "dwconv") else None
+        wstore = _wstore(op) if op["op"] in ("conv", "dense", "dwconv", "tconv") else None
         if wstore is None:
             return None
         if op["kind"] == "ternary" and TERNARY_T2:
@@ -1180,7 +1195,12 @@ class GraphModel:
             return _abi.conv2d(w, xin, xs, 0, N, H, W, inv, shift)[0]
         return _abi.dense(w, xin, _abi.STORE_F32, 0, xin.shape[0], inv, shift)
 
-    def _dwconv(self, i, op, src):
+    def _tconv(self, i, op, src):
+        """Transposed-convolution op `i` on `src` (include/qnn_abi_tconv.h) under _dwconv's planner rules: (result, index
+        of the last op fused into it)."""
+        return self._dwconv(i, op, src, run=_abi.tconv)
+
+    def _dwconv(self, i, op, src, run=None):
         """Depthwise op `i` on `src` (include/qnn_abi_depthwise.h): (result, index of the last op fused into it).  The
         planner rules of a conv: a following BN that is the tensor's only consumer goes into the epilogue, a packed producer
         (codes of the store this op joins at) is read as it is and an unmaterialised clip is packed on load.  Beyond a
@@ -1225,7 +1245,7 @@ class GraphModel:
             xt = self._plain(src).contiguous()
             shape = xt.shape
         N, H, W, C = shape
-        y, Ho, Wo = _abi.depthwise(g.weights(i, xs), xt, xs, xbits, N, H, W, inv, shift, fn, act_bits, out_store)
+        y, Ho, Wo = (run or _abi.depthwise)(g.weights(i, xs), xt, xs, xbits, N, H, W, inv, shift, fn, act_bits, out_store)
         if self.kernel_log is not None:
             self.kernel_log.append(_abi.last_kernel())
         if out_store != _abi.STORE_F32:
@@ -1236,6 +1256,7 @@ class GraphModel:
         g, spec = self.graph, self.spec
         env = {"input": _images(x, "GraphModel.forward")}
         skip = set()
+        upsampled = set()                    # tensors a tconv left as packed codes
         for i, op in enumerate(spec):
             if i in skip:
                 continue
@@ -1254,18 +1275,20 @@ class GraphModel:
                     skip.add(i + 1)
                     name = g.names[i + 1]
                 y = self._contract(i, op, src, inv, shift)
-            elif kind == "dwconv":
-                y, last = self._dwconv(i, op, src)
+            elif kind in ("dwconv", "tconv"):
+                y, last = self._dwconv(i, op, src) if kind == "dwconv" else self._tconv(i, op, src)
                 skip.update(range(i + 1, last + 1))
                 name = g.names[last]
+                if kind == "tconv" and isinstance(y, _Packed):
+                    upsampled.add(name)      # a decoder's codes: the skip they are joined with is packed to meet them
             elif kind == "bn":
                 y = _bn_apply(self._plain(src), *g.bn[i])
             elif kind == "add":
                 y = _add(self._plain(src), self._plain(env[op["b"]]))
             elif kind == "concat":
                 y = self._concat([env[s] for s in g.srcs[i]],
-                                 pack_clips=any(s in g.prod and spec[g.prod[s]]["op"] in _SPATIAL and _new_spatial(spec[g.prod[s]])
-                                                for s in g.srcs[i]))
+                                 pack_clips=any(s in upsampled or (s in g.prod and spec[g.prod[s]]["op"] in _SPATIAL and
+                                                                   _new_spatial(spec[g.prod[s]])) for s in g.srcs[i]))
             elif kind in _SPATIAL and _new_spatial(op):
                 y = self._spatial(src, op, name)
             elif kind == "act" and _act_code(op) is not None:
@@ -1378,6 +1401,7 @@ class ResidualFusedModel(_DomainFlag):
             raise ValueError("first_layer must be 'auto', 'exact' or 'image', got %r" % (first_layer,))
         _refuse_concat(spec, "ResidualFusedModel")
         _refuse_dwconv(spec, "ResidualFusedModel")
+        _refuse_tconv(spec, "ResidualFusedModel")
         _refuse_spatial(spec, "ResidualFusedModel")
         _refuse_max_acts(spec, "ResidualFusedModel")
         self.first_layer = first_layer
@@ -1939,9 +1963,26 @@ class LayerModel:
         self.graph = _SpecGraph(spec, device)
         prev_act = {}
         for i, op in enumerate(spec):
-            if op["op"] not in ("conv", "dense", "dwconv"):
+            if op["op"] not in ("conv", "dense", "dwconv", "tconv"):
                 continue
             kw = dict(use_bias=op.get("bias") is not None, device=device)
+            if op["op"] == "tconv":
+                kh, kw_, cout, cin = op["kernel"].shape
+                kw.update(strides=tuple(op.get("strides", (1, 1))), padding=op.get("padding", "same"))
+                H = float(op.get("H", 1.0))
+                if op["kind"] == "binary":
+                    layer = BinaryConv2DTranspose(cout, (kh, kw_), H=H, **kw)
+                elif op["kind"] == "quantized":
+                    layer = QuantizedConv2DTranspose(cout, (kh, kw_), H=H, nb=op["nb"], **kw)
+                elif op["kind"] == "ternary":
+                    layer = TernaryConv2DTranspose(cout, (kh, kw_), H=H, **kw)
+                else:
+                    layer = Conv2DTranspose(cout, (kh, kw_), **kw)
+                layer.build((None, None, None, cin))
+                ws = [op["kernel"]] + ([op["bias"]] if op.get("bias") is not None else [])
+                layer.set_weights(ws)
+                self.layers[i] = layer
+                continue
             if op["op"] == "dwconv":
                 kh, kw_, cin, M = op["kernel"].shape
                 kw.update(strides=tuple(op.get("strides", (1, 1))), padding=op.get("padding", "same"),
@@ -2005,7 +2046,7 @@ class LayerModel:
             src, d = env[sname], None
             if kind == "add":
                 y = _add(src, env[op["b"]])
-            elif kind in ("conv", "dense", "dwconv"):
+            elif kind in ("conv", "dense", "dwconv", "tconv"):
                 layer = self.layers[i]
                 layer.input_domain = dom.get(sname) if self.fuse_input_activation else None
                 y = layer(src)

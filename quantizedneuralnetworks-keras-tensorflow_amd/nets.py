@@ -320,11 +320,11 @@ class Model:
                 self.engine = engine.ResidualFusedModel(spec, device,
                                                         first_layer=first_layer if first_layer in ("auto", "image") else "exact")
             except _abi.NotFusable:
-                # only the batch-scaled activations (float32 between the layers), channel concatenation, depthwise
-                # convolution and the new-form
+                # only the batch-scaled activations (float32 between the layers), channel concatenation, depthwise and
+                # transposed convolution and the new-form
                 # spatial ops (crop, upsample, pair-form zeropad) are handed on; anything else the residual engine
                 # refuses stays an error
-                if not any((op["op"] == "act" and op["fn"] in BATCH_SCALED_ACTIVATIONS) or op["op"] in ("concat", "dwconv") or
+                if not any((op["op"] == "act" and op["fn"] in BATCH_SCALED_ACTIVATIONS) or op["op"] in ("concat", "dwconv", "tconv") or
                            (op["op"] in engine._SPATIAL and engine._new_spatial(op)) for op in spec):
                     raise
                 self.engine = engine.GraphModel(spec, device, scaled_codes=scaled_codes)
@@ -514,6 +514,10 @@ def _pool_op(kind, c, name):
     return {"op": kind, "size": size, "strides": strides, "padding": padding}
 
 
+_TCONV_KINDS = {"Conv2DTranspose": "float", "BinaryConv2DTranspose": "binary", "QuantizedConv2DTranspose": "quantized",
+                "TernaryConv2DTranspose": "ternary"}
+
+
 def spec_from_keras_npz(path, wbits=None, abits=None):
     """Rebuild a net spec from a Keras 2.1.3 checkpoint converted by tools/import_keras_hdf5.py
     (counterpart of test_resnet.py:44-66 build + load_weights).  The topology comes from the
@@ -572,6 +576,25 @@ def spec_from_keras_npz(path, wbits=None, abits=None):
                 c = dict(c, dilation_rate=(1, 1))       # the dilation is the depthwise half's
             else:
                 op = dw
+        elif cls in _TCONV_KINDS:
+            # keras.layers.Conv2DTranspose (float weights) and the low-bit classes of layers/conv_transpose.py -> tconv
+            _spatial_data_format(c, name)
+            if c.get("activation") not in (None, "linear"):
+                raise ValueError("layer %r has activation=%r; only 'linear' is supported in a %s" % (name, c["activation"], cls))
+            if c.get("output_padding") is not None:
+                raise ValueError("layer %r has output_padding=%r; only None is supported" % (name, c["output_padding"]))
+            if tuple(int(v) for v in c.get("dilation_rate", (1, 1))) != (1, 1):
+                raise ValueError("layer %r has dilation_rate=%r; a %s supports (1, 1) only" % (name, c["dilation_rate"], cls))
+            kind = _TCONV_KINDS[cls]
+            op = {"op": "tconv", "kind": kind, "kernel": d[name + "/kernel"],
+                  "bias": d[name + "/bias"] if c.get("use_bias", True) else None,
+                  "strides": tuple(int(v) for v in c["strides"]), "padding": str(c["padding"]).lower(),
+                  "H": float(c.get("H", 1.0)) if kind != "float" else 1.0,
+                  "klm": np.float32(c.get("kernel_lr_multiplier") or 1.0)}
+            if kind == "quantized":
+                if wbits is None:
+                    raise ValueError("layer %r is a %s: pass wbits (`nb` is not serialised)" % (name, cls))
+                op["nb"] = int(wbits)
         elif cls in ("TernaryConv2D", "TernaryDense"):
             op = {"op": "conv" if cls == "TernaryConv2D" else "dense", "kind": "ternary",
                   "kernel": d[name + "/kernel"], "bias": d[name + "/bias"] if c.get("use_bias", True) else None,
