@@ -172,45 +172,17 @@ class Net(S.Net):
 
 
 def sources(spec):
-    names = S.names_of(spec)
-    return [list(op["srcs"]) if op["op"] == "concat" else [op["a"], op["b"]] if op["op"] == "add" else
-            [op["src"] if "src" in op else names[i - 1] if i > 0 else "input"] for i, op in enumerate(spec)]
+    return S.sources(spec)
 
 
 def reference(spec, x, return_all=False):
-    """spec_graph_cases.reference op by op, with concat as np.concatenate(axis=-1) and add as the float32 sum."""
-    x = np.asarray(x, dtype=F32)
-    env, cur = {"input": x}, x
-    for i, op in enumerate(spec):
-        if op["op"] == "concat":
-            y = np.concatenate([env[s] for s in op["srcs"]], axis=-1)
-        elif op["op"] == "add":
-            y = env[op["a"]] + env[op["b"]]
-        else:
-            one = {k: v for k, v in op.items() if k not in ("src", "dst")}
-            y = S.reference([one], env[op["src"]] if "src" in op else cur)
-        env[op.get("dst", "t%d" % i)] = cur = np.asarray(y, dtype=F32)
-    return env if return_all else cur
+    """spec_graph_cases.reference: the shared op-by-op float32 reference knows the concat op."""
+    return S.reference(spec, x, return_all)
 
 
 def guard(spec, x):
-    """spec_graph_cases.guard's rule for the contractions of a spec with concat ops: operands dyadic, the exact result a
-    float32 value, the sum of the products' magnitudes below 2^24 units.  None, or the reason."""
-    env = reference(spec, x, return_all=True)
-    for i, (op, ss) in enumerate(zip(spec, sources(spec))):
-        if op["op"] not in ("conv", "dense"):
-            continue
-        try:
-            xc, a = S._codes(env[ss[0]], "input of op %d" % i)
-            wc, b = S._codes(S.weights(op), "weights of op %d" % i)
-        except ValueError as e:
-            return str(e)
-        s64 = S._contract(xc, wc, op).astype(np.float64) * 2.0 ** -(a + b)
-        if not np.array_equal(s64.astype(F32).astype(np.float64), s64):
-            return "op %d: the float64 contraction is not a float32 value" % i
-        if S._contract(np.abs(xc), np.abs(wc), op).max(initial=0) >= 2 ** 24:
-            return "op %d: partial sums may pass 2^24 units" % i
-    return None
+    """spec_graph_cases.guard: None, or the reason the case is not exact by construction."""
+    return S.guard(spec, x)
 
 
 def _packed_branches(seed, fn, abits, wkind, wnb, c):

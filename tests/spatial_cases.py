@@ -107,59 +107,17 @@ class Net(C.Net):
 
 def op_desc(op):
     """The descriptor of a new-form spatial spec op, or None."""
-    if op["op"] == "zeropad" and not isinstance(op["pad"], (int, np.integer)):
-        return desc(pad=op["pad"])
-    if op["op"] == "crop":
-        return desc(crop=op["crop"])
-    if op["op"] == "upsample":
-        return desc(up=tuple(op["size"]))
-    return None
+    return S.spatial_desc(op)
 
 
 def reference(spec, x, return_all=False):
-    """concat_cases.reference op by op, with the new-form spatial ops as spatial_array."""
-    x = np.asarray(x, dtype=F32)
-    env, cur = {"input": x}, x
-    for i, op in enumerate(spec):
-        src = env[op["src"]] if "src" in op else cur
-        if op_desc(op) is not None:
-            y = spatial_array(src, op_desc(op))
-        elif op["op"] == "concat":
-            y = np.concatenate([env[s] for s in op["srcs"]], axis=-1)
-        elif op["op"] == "add":
-            y = env[op["a"]] + env[op["b"]]
-        else:
-            one = {k: v for k, v in op.items() if k not in ("src", "dst")}
-            y = S.reference([one], src)
-        env[op.get("dst", "t%d" % i)] = cur = np.asarray(y, dtype=F32)
-    return env if return_all else cur
+    """spec_graph_cases.reference: the shared op-by-op float32 reference knows the spatial ops (spatial_array)."""
+    return S.reference(spec, x, return_all)
 
 
 def guard(spec, x):
-    """spec_graph_cases.guard's rules on a spec with spatial and concat ops: every contraction exact in every order, no
-    value within one ulp of a ternary cutoff.  None, or the reason."""
-    env = reference(spec, x, return_all=True)
-    for i, (op, ss) in enumerate(zip(spec, C.sources(spec))):
-        src = env[ss[0]]
-        if op["op"] in ("conv", "dense"):
-            try:
-                xc, a = S._codes(src, "input of op %d" % i)
-                wc, b = S._codes(S.weights(op), "weights of op %d" % i)
-            except ValueError as e:
-                return str(e)
-            s64 = S._contract(xc, wc, op).astype(np.float64) * 2.0 ** -(a + b)
-            if not np.array_equal(s64.astype(F32).astype(np.float64), s64):
-                return "op %d: the float64 contraction is not a float32 value" % i
-            if S._contract(np.abs(xc), np.abs(wc), op).max(initial=0) >= 2 ** 24:
-                return "op %d: partial sums may pass 2^24 units" % i
-        elif op["op"] == "act" and op["fn"] == "ternary_tanh":
-            t = np.clip(src, F32(-1), F32(1))
-            mean = F32(np.mean(np.abs(t), dtype=np.float64))
-            lo = np.nextafter(F32(0.7) * np.nextafter(mean, F32(-np.inf)), F32(-np.inf))
-            hi = np.nextafter(F32(0.7) * np.nextafter(mean, F32(np.inf)), F32(np.inf))
-            if np.any((np.abs(t) >= lo) & (np.abs(t) <= hi)):
-                return "op %d: a value within one ulp of the ternary cutoff" % i
-    return None
+    """spec_graph_cases.guard: None, or the reason the case is not exact by construction."""
+    return S.guard(spec, x)
 
 
 # activation name -> (fn, abits, weight kind, weight bits, the spatial kernel GraphModel logs)

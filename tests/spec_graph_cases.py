@@ -20,9 +20,11 @@ import numpy as np
 from oracle import qnn_oracle as O
 
 import conv_dilation_cases as D
+import depthwise_cases as DW
 import maxrelu_cases as M
 import pool_cases as P
 import qrelu_cases as Q
+import tconv_cases as TC
 
 F32 = np.float32
 N = 3
@@ -35,9 +37,10 @@ def names_of(spec):
 
 
 def sources(spec):
-    """The tensors every op reads: add -> a, b; a named `src`; else the previous op's output; else the images."""
+    """The tensors every op reads: add -> a, b; concat -> its srcs; a named `src`; else the previous op's output; else
+    the images."""
     names = names_of(spec)
-    return [[op["a"], op["b"]] if op["op"] == "add" else
+    return [[op["a"], op["b"]] if op["op"] == "add" else list(op["srcs"]) if op["op"] == "concat" else
             [op["src"] if "src" in op else names[i - 1] if i > 0 else "input"] for i, op in enumerate(spec)]
 
 
@@ -71,6 +74,47 @@ def weights(op):
     if op["kind"] == "quantized":
         return O.quantize(k, op["nb"])
     return k
+
+
+def spatial_desc(op):
+    """The crop / repeat / pad descriptor (spatial_cases.desc) of a new-form spatial op, or None: `crop`, `upsample`, and
+    `zeropad` whose pad is ((top, bottom), (left, right)) rather than one integer."""
+    ident = {"crop": ((0, 0), (0, 0)), "up": (1, 1), "pad": ((0, 0), (0, 0))}
+    if op["op"] == "zeropad" and not isinstance(op["pad"], (int, np.integer)):
+        return dict(ident, pad=op["pad"])
+    if op["op"] == "crop":
+        return dict(ident, crop=op["crop"])
+    if op["op"] == "upsample":
+        return dict(ident, up=tuple(op["size"]))
+    return None
+
+
+def dw_dilation(op):
+    """A dwconv op carries its dilation as `dilation`."""
+    return P.pair(op.get("dilation", (1, 1)))
+
+
+def _stride(op):
+    sh, sw = op.get("strides", (1, 1))
+    assert sh == sw, "dwconv / tconv take one stride for both axes"
+    return int(sh)
+
+
+def _depthwise_or_transposed(op, src):
+    """dwconv / tconv: the integer sum (depthwise_cases.dw_sum / tconv_cases.tconv_sum) on the exact integer codes of
+    input and weights, scaled by their power of two, plus the bias in float32.  Operands that are no dyadic numbers
+    (guard refuses such a case) are summed in float64 and rounded once."""
+    w = weights(op)
+    try:
+        (xc, a), (wc, b) = _codes(src, "input"), _codes(w, "weights")
+        v = (_contract(xc, wc, op).astype(F32) * F32(2.0 ** -(a + b))).astype(F32)
+    except ValueError:
+        same = op.get("padding", "same") == "same"
+        v = (DW.dw_sum(src, w, _stride(op), same, dw_dilation(op), np.float64) if op["op"] == "dwconv" else
+             TC.tconv_sum(src, w, _stride(op), same, np.float64)).astype(F32)
+    if op.get("bias") is not None:
+        v = (v + np.asarray(op["bias"], dtype=F32)).astype(F32)
+    return v
 
 
 # ---- the reference ---------------------------------------------------------------------------------------------------------
@@ -108,6 +152,13 @@ def reference(spec, x, return_all=False):
             elif kind == "act" and op["fn"] in M.FNS:
                 assert F32(op.get("alpha", M.ALPHA)) == M.ALPHA
                 y = M.maxact(src, op["nb"], op["fn"])
+            elif kind == "concat":
+                y = np.concatenate([env[s] for s in op["srcs"]], axis=-1)
+            elif spatial_desc(op) is not None:
+                import spatial_cases                         # (it imports this module)
+                y = spatial_cases.spatial_array(src, spatial_desc(op))
+            elif kind in ("dwconv", "tconv"):
+                y = _depthwise_or_transposed(op, src)
             else:
                 one = _undilated(op) if kind == "conv" and dilation(op) != (1, 1) else dict(op)
                 e = dict(env)
@@ -136,6 +187,10 @@ def _contract(x, w, op):
     """Integer contraction of codes: conv (the stuffed window for a dilated one) or matrix product."""
     if op["op"] == "dense":
         return x.dot(w)
+    if op["op"] == "dwconv":
+        return DW.dw_sum(x, w, _stride(op), op.get("padding", "same") == "same", dw_dilation(op))
+    if op["op"] == "tconv":
+        return TC.tconv_sum(x, w, _stride(op), op.get("padding", "same") == "same")
     dh, dw = dilation(op)
     return O.int_conv2d(x, D.stuff(w, dh, dw), tuple(op.get("strides", (1, 1))), op.get("padding", "same"))
 
@@ -148,7 +203,7 @@ def guard(spec, x):
     env = reference(spec, x, return_all=True)
     for i, (op, ss) in enumerate(zip(spec, sources(spec))):
         src = env[ss[0]]
-        if op["op"] in ("conv", "dense"):
+        if op["op"] in ("conv", "dense", "dwconv", "tconv"):
             try:
                 xc, a = _codes(src, "input of op %d" % i)
                 wc, b = _codes(weights(op), "weights of op %d" % i)
@@ -159,6 +214,10 @@ def guard(spec, x):
                 return "op %d: the float64 contraction is not a float32 value" % i
             if _contract(np.abs(xc), np.abs(wc), op).max(initial=0) >= 2 ** 24:
                 return "op %d: partial sums may pass 2^24 units" % i
+            if op["op"] == "tconv":
+                kh, kw, _, cin = wc.shape
+                if TC.int32_refused(kh, kw, _stride(op), cin, a + 1, b):
+                    return "op %d: the transposed convolution's int32 bound" % i
         elif op["op"] == "act" and op["fn"] == "ternary_tanh":
             t = np.clip(src, F32(-1), F32(1))
             mean = F32(np.mean(np.abs(t), dtype=np.float64))
@@ -302,11 +361,91 @@ class Net:
     def softmax(self, src=None):
         return self._put({"op": "softmax"}, src, self.shape[self.cur if src is None else src])
 
+    # -- concat, the new-form spatial ops, dwconv and tconv
+    def concat(self, srcs, dst=None):
+        shapes = [self.shape[s] for s in srcs]
+        assert len({s[:-1] for s in shapes}) == 1, shapes
+        op = {"op": "concat", "srcs": list(srcs)}
+        if dst is not None:
+            op["dst"] = dst
+        self.spec.append(op)
+        name = names_of(self.spec)[-1]
+        assert name not in self.shape, name
+        self.shape[name] = shapes[0][:-1] + (sum(s[-1] for s in shapes),)
+        self.cur = name
+        return name
+
+    def _spatial(self, op, src, dst):
+        h, w, c = self.shape[self.cur if src is None else src]
+        d = spatial_desc(op)                 # crop, then repeat, then pad (spatial_cases.out_hw; that module imports this one)
+        ho = (h - sum(d["crop"][0])) * d["up"][0] + sum(d["pad"][0])
+        wo = (w - sum(d["crop"][1])) * d["up"][1] + sum(d["pad"][1])
+        assert ho > 0 and wo > 0
+        return self._put(op, src, (ho, wo, c), dst)
+
+    def zeropad2(self, pad, src=None, dst=None):
+        return self._spatial({"op": "zeropad", "pad": pad}, src, dst)
+
+    def crop(self, crop, src=None, dst=None):
+        return self._spatial({"op": "crop", "crop": crop}, src, dst)
+
+    def upsample(self, size, src=None, dst=None):
+        return self._spatial({"op": "upsample", "size": size}, src, dst)
+
+    def _bias(self, n, bias):
+        """None, the float bias of conv(), or ("dyadic") multiples of 1 / 16: the sums stay dyadic without a clip."""
+        if bias == "dyadic":
+            return (self.rng.integers(-8, 9, n) / 16.0).astype(F32)
+        return (self.rng.standard_normal(n) * 0.05).astype(F32) if bias else None
+
+    def dwconv(self, M=1, kind="quantized", nb=4, k=3, s=1, pad="same", dil=1, bias=False, src=None, dst=None):
+        """Keras' DepthwiseConv2D: kernel (kh, kw, C, M)."""
+        h, w, c = self.shape[self.cur if src is None else src]
+        (kh, kw), (dh, dw) = P.pair(k), P.pair(dil)
+        op = {"op": "dwconv", "kind": kind, "kernel": _kernel(self.rng, kind, nb, (kh, kw, c, M)),
+              "bias": self._bias(c * M, bias), "strides": (s, s), "padding": pad, "dilation": (dh, dw),
+              "depth_multiplier": M, "H": 1.0}
+        if kind == "quantized":
+            op["nb"] = nb
+        ho, wo = DW.out_pad(h, kh, s, pad == "same", dh)[0], DW.out_pad(w, kw, s, pad == "same", dw)[0]
+        assert ho > 0 and wo > 0
+        self.fan = kh * kw * _WVAR[kind]
+        return self._put(op, src, (ho, wo, c * M), dst)
+
+    def tconv(self, cout, kind="quantized", nb=4, k=2, s=2, pad="same", bias=False, src=None, dst=None):
+        """Keras' Conv2DTranspose: kernel (kh, kw, Cout, Cin)."""
+        h, w, cin = self.shape[self.cur if src is None else src]
+        kh, kw = P.pair(k)
+        op = {"op": "tconv", "kind": kind, "kernel": _kernel(self.rng, kind, nb, (kh, kw, cout, cin)),
+              "bias": self._bias(cout, bias), "strides": (s, s), "padding": pad, "H": 1.0}
+        if kind == "quantized":
+            op["nb"] = nb
+        ho, wo = TC.out_pad(h, kh, s, pad == "same")[0], TC.out_pad(w, kw, s, pad == "same")[0]
+        self.fan = -(-kh // s) * -(-kw // s) * cin * _WVAR[kind]
+        return self._put(op, src, (ho, wo, cout), dst)
+
+    def dyadic_bn(self, src=None, dst=None):
+        """Constants that are powers of two and multiples of 1 / 32 (eps 0, mean 0, variance 1, so inv = gamma and
+        shift = beta exactly): what is behind it stays dyadic without a clip."""
+        shape = self.shape[self.cur if src is None else src]
+        c, rng = shape[-1], self.rng
+        lo = -1 - int(np.log2(max(self.fan, 1.0))) // 2
+        op = dict(op="bn", eps=0.0, gamma=((2.0 ** rng.integers(lo, lo + 2, c)) * rng.choice([-1.0, 1.0], c)).astype(F32),
+                  beta=(rng.integers(-8, 9, c) / 32.0).astype(F32), mean=np.zeros(c, F32), var=np.ones(c, F32))
+        return self._put(op, src, shape, dst)
+
     # a few groups the cases below repeat
     def group(self, cout, kind="quantized", nb=4, fn="quantized_tanh", abits=4, **kw):
         self.conv(cout, kind, nb, **kw)
         self.bn()
         return self.act(fn, abits)
+
+    def clipped(self, cout, w="q4", a="q4", dst=None, bn=True, **kw):
+        """conv -> [bn] -> clip by the names of WEIGHT_OF / ACT_OF; `dst` names the clip."""
+        self.conv(cout, *WEIGHT_OF[w], **kw)
+        if bn:
+            self.bn()
+        return self.act(*ACT_OF[a], dst=dst)
 
     def classifier(self, kind="quantized", nb=4):
         self.flatten()
@@ -910,3 +1049,836 @@ REQUIRED = ({"op %s" % k for k in ("conv", "dense", "bn", "act", "add", "scale",
             {"shortcut %s" % k for k in ("i4", "bin", "i8", "ternary", "float32 bn", "float32 conv")} |
             {"one tensor, two stores wanted", "flatten before wider dense", "projection eligible", "projection near miss",
              "tail fused", "tail declined", "FusedModel accepts", "FusedModel refuses", "dilated conv"})
+
+
+# ============================================================================================================================
+# The wide vocabulary: concat, crop / upsample / pair-form zeropad, dwconv, tconv.
+#
+#   plan(spec)            GraphModel's planner restated on symbols: per tensor whether it travels as packed codes, as a
+#                         clip not yet applied or as float32, the launches GraphModel.kernel_log records, and the
+#                         decisions taken on the way (what categories() counts)
+#   HAND_WIDE             one spec per planner decision, with the log the GPU file expects
+#   generate_wide(seed)   random encoder-decoders, separable blocks, dense-net growth and inception branches
+# ============================================================================================================================
+_STORE_NAME = {0: "f32", 1: "bin", 2: "t2", 4: "i4", 8: "i8"}
+_FN_OF = {"binary_tanh": "bin", "quantized_tanh": "qtanh", "quantized_relu": "qrelu", "quantized_leakyrelu": "qleaky"}
+_DWFN = {"bin": DW.FN_BINARY_TANH, "qtanh": DW.FN_QUANTIZED_TANH, "qrelu": DW.FN_QUANTIZED_RELU,
+         "qleaky": DW.FN_QUANTIZED_LEAKYRELU}
+
+
+def _wstore(op):
+    """Narrowest packed store of a contraction's weights (1 / 4 / 8), None for float or 16-bit weights."""
+    if op["kind"] == "binary":
+        return 1
+    if op["kind"] == "ternary":
+        return 4
+    if op["kind"] == "quantized" and op["nb"] <= 8:
+        return 4 if op["nb"] <= 4 else 8
+    return None
+
+
+def _bits_store(bits):
+    return 1 if bits == 1 else 4 if bits <= 4 else 8
+
+
+def _join(bits, wstore):
+    """The store both operands of a contraction are brought to (engine._join_store)."""
+    if wstore is None:
+        return None
+    a = _bits_store(bits)
+    if a == 1 and wstore == 1:
+        return 1
+    return max(0 if a == 1 else a, 0 if wstore == 1 else wstore, 4)
+
+
+def _grid_store(op):
+    """The store a contraction reads ternary codes {-1, 0, 1} at (engine.GraphModel._grid_store)."""
+    ws = _wstore(op) if op["op"] in ("conv", "dense", "dwconv", "tconv") else None
+    if ws is None:
+        return None
+    return 2 if op["kind"] == "ternary" else max(4, ws if ws != 1 else 4)
+
+
+def _clip_of(op):
+    """(fn, bits) of an activation op that is a low-bit clip, else None (engine._act_code)."""
+    if op["fn"] == "binary_tanh":
+        return "bin", 1
+    if op["fn"] in _FN_OF and op["nb"] <= 8:
+        return _FN_OF[op["fn"]], int(op["nb"])
+    return None
+
+
+def _F(ndim):
+    return {"k": "F", "ndim": ndim}
+
+
+def _V(fn, nb, ndim, origin=None):
+    return {"k": "V", "fn": fn, "nb": nb, "ndim": ndim, "origin": origin}
+
+
+def _P(store, bits, ndim, grid=False, origin=None):
+    return {"k": "P", "store": store, "bits": bits, "grid": grid, "ndim": ndim, "origin": origin}
+
+
+def _shapes(spec, hw_c):
+    """name -> shape without the batch axis, from the reference on one zero image."""
+    env = reference(spec, np.zeros((1,) + tuple(hw_c), F32), return_all=True)
+    return {k: v.shape[1:] for k, v in env.items()}
+
+
+def plan(spec, image=(8, 8, 3)):
+    """(state per tensor, kernel_log, decisions) of GraphModel(spec) without scaled codes.  kernel_log: what the engine
+    appends to GraphModel.kernel_log; decisions: a set of strings."""
+    names, srcs, cons = names_of(spec), sources(spec), consumers(spec)
+    prod = {n: i for i, n in enumerate(names)}
+    shape = _shapes(spec, image)
+    env, log, dec, skip, upsampled = {"input": _F(4)}, [], set(), set(), set()
+
+    def origin_tags(st, through):
+        """Categories of codes going through a spatial op or a concat."""
+        dec.add("codes through %s: %s" % (through, _STORE_NAME[st["store"]]))
+        o = st.get("origin")
+        if o is not None:
+            fn, nb = o
+            for tag, hit in (("relu", fn == "qrelu"), ("leaky", fn == "qleaky"), ("2-bit", nb == 2 and fn != "bin"),
+                             ("3-bit", nb == 3)):
+                if hit:
+                    dec.add("%s codes through a spatial op or concat" % tag)
+
+    def grid_plan(name):
+        stores, todo, looked = set(), [name], False
+        while todo:
+            n = todo.pop()
+            if n == names[-1]:
+                return None
+            for c in cons.get(n, []):
+                o = spec[c]
+                if o["op"] == "concat" or spatial_desc(o) is not None:
+                    todo.append(names[c])
+                    looked |= o["op"] == "concat"
+                else:
+                    stores.add(_grid_store(o))
+        if len(stores) > 1 and None not in stores and looked:
+            dec.add("ternary: no common store behind a concat")
+        return stores.pop() if len(stores) == 1 else None
+
+    def pack_clip(v, name=None):
+        if v["k"] != "V" or v["ndim"] != 4:
+            return None
+        if v["fn"] == "grid":
+            store = grid_plan(name) if name is not None else None
+            return None if store is None else _P(store, 1, 4, True, ("grid", 1))
+        bits = 1 if v["fn"] == "bin" else v["nb"]
+        return _P(_bits_store(bits), bits, 4, False, (v["fn"], v["nb"]))
+
+    def read_packed(i, op, src, ndim):
+        """A contraction on packed codes: True if it reads them as they are, else the re-clip branch."""
+        ws = _wstore(op)
+        want = _grid_store(op) if src["grid"] else _join(src["bits"], ws) if ws is not None else None
+        if ws is not None and want == src["store"] and src["ndim"] == ndim:
+            return True
+        if ws is not None:
+            dec.add("packed producer, other store wanted")
+        return False
+
+    def depth(i, op, src):
+        kind, last = op["op"], i
+        if cons.get(names[last], []) == [last + 1] and spec[last + 1]["op"] == "bn":
+            last += 1
+        elif any(spec[c]["op"] == "bn" for c in cons.get(names[i], [])) and len(cons.get(names[i], [])) > 1:
+            dec.add("a second reader beside the BN behind %s" % kind)
+        if last > i and len(cons.get(names[last], [])) > 1:
+            dec.add("BN behind %s read twice" % kind)
+        out = None
+        if last + 1 < len(spec) and cons.get(names[last], []) == [last + 1] and spec[last + 1]["op"] == "act" and \
+                _clip_of(spec[last + 1]) is not None:
+            out = _clip_of(spec[last + 1])
+            last += 1
+            dec.add("%s clip in the epilogue" % kind)
+            for c in cons.get(names[last], []):
+                dec.add("packed %s output read by %s" % (kind, spec[c]["op"] + (" (new form)" if new_pool(spec[c]) and
+                                                                                 spec[c]["op"] in ("maxpool", "avgpool") else "")))
+            if names[last] == names[-1]:
+                dec.add("packed %s output is the last tensor" % kind)
+            if len(cons.get(names[last], [])) > 1:
+                dec.add("clip behind %s read twice" % kind)
+        ws = _wstore(op)
+        xs, xbits = 0, 0
+        if src["k"] == "P":
+            if read_packed(i, op, src, 4):
+                xs, xbits = src["store"], src["bits"]
+            else:
+                src = _V("grid" if src["grid"] else "bin" if src["store"] == 1 else "qtanh", src["bits"], src["ndim"])
+        if xs == 0 and src["k"] == "V" and ws is not None and src["ndim"] == 4:
+            if src["fn"] == "grid":
+                xs, xbits = _grid_store(op), 1
+            else:
+                xbits = 1 if src["fn"] == "bin" else src["nb"]
+                xs = _join(xbits, ws)
+            log.append("pack")
+        # the kernel's name
+        kh, kw = op["kernel"].shape[:2]
+        wshift = op["nb"] - 1 if op["kind"] == "quantized" else 0
+        ostore = 0 if out is None else _bits_store(out[1])
+        suffix = ""
+        if kind == "dwconv" and xs in (4, 8):
+            pk16 = DW.takes_pk16(dict(store=xs, out_store=ostore, M=op["kernel"].shape[3], window=(kh, kw), stride=_stride(op),
+                                      dil=dw_dilation(op), x_bits=xbits, wkind=DW.W_QUANT if op["kind"] == "quantized" else 1,
+                                      wbits=op.get("nb", 1)))
+            suffix = "" if pk16 else "_plain"
+            if pk16:
+                dec.add("depthwise 16-bit-lane form")
+        elif kind == "tconv" and xs in (4, 8):
+            mfma = TC.takes_mfma(dict(window=(kh, kw), stride=_stride(op), store=xs, out_store=ostore, Cin=op["kernel"].shape[3],
+                                      Cout=op["kernel"].shape[2], misalign=False))
+            suffix = "_mfma" if mfma else "_plain"
+            if mfma:
+                dec.add("tconv matrix-pipe form")
+        log.append("%s_%s%s" % ("depthwise" if kind == "dwconv" else "tconv", _STORE_NAME[xs], suffix))
+        y = _F(4) if out is None else _P(ostore, out[1], 4, False, out)
+        return y, last
+
+    for i, op in enumerate(spec):
+        if i in skip:
+            continue
+        kind, name = op["op"], names[i]
+        src = env[srcs[i][0]]
+        pi = prod.get(srcs[i][0])
+        if pi is not None and spec[pi]["op"] == "act" and spec[pi]["fn"] in M.FNS:
+            for tag, hit in (("dwconv", kind == "dwconv"), ("tconv", kind == "tconv"), ("spatial", spatial_desc(op) is not None)):
+                if hit:
+                    dec.add("max activation in front of %s" % tag)
+        if kind == "concat" and any(prod.get(s) is not None and spec[prod[s]]["op"] == "act" and spec[prod[s]]["fn"] in M.FNS
+                                    for s in srcs[i]):
+            dec.add("max activation in front of concat")
+        if kind == "avgpool" and not new_pool(op) and src["k"] == "V" and src["fn"] != "grid" and _tail_at(spec, names, cons, i):
+            t = _tail_at(spec, names, cons, i)
+            skip.update(t)
+            name, y = names[max(t)], _F(2)
+        elif kind in ("conv", "dense"):
+            if cons.get(name, []) == [i + 1] and spec[i + 1]["op"] == "bn":
+                skip.add(i + 1)
+                name = names[i + 1]
+            if src["k"] == "P":
+                read_packed(i, op, src, 4 if kind == "conv" else 2)
+            y = _F(4 if kind == "conv" else 2)
+        elif kind in ("dwconv", "tconv"):
+            y, last = depth(i, op, src)
+            skip.update(range(i + 1, last + 1))
+            name = names[last]
+            if kind == "tconv" and y["k"] == "P":
+                upsampled.add(name)
+        elif kind == "concat":
+            ins = [env[s] for s in srcs[i]]
+            pack_clips = any(s in upsampled or (s in prod and spatial_desc(spec[prod[s]]) is not None) for s in srcs[i])
+            if pack_clips and any(t["k"] == "P" for t in ins):
+                like = next(t for t in ins if t["k"] == "P")
+                packs = [t if t["k"] == "P" else None if t["k"] != "V" else
+                         (_P(like["store"], 1, 4, True, ("grid", 1)) if like["grid"] and t["ndim"] == 4 else None)
+                         if t["fn"] == "grid" else pack_clip(t) for t in ins]
+                if all(p is not None for p in packs) and len({(p["store"], p["bits"], p["grid"]) for p in packs}) == 1:
+                    if any(t["k"] == "V" for t in ins):
+                        dec.add("pack_clips join")
+                    ins = packs
+            if all(t["k"] == "P" for t in ins) and len({(t["store"], t["bits"], t["grid"]) for t in ins}) == 1:
+                dec.add("concat join: codes")
+                for t in ins:
+                    origin_tags(t, "concat")
+                log.append("concat_" + _STORE_NAME[ins[0]["store"]])
+                y = _P(ins[0]["store"], ins[0]["bits"], ins[0]["ndim"], ins[0]["grid"], ins[0]["origin"])
+            elif all(t["k"] == "V" for t in ins) and len({(t["fn"], t["nb"]) for t in ins}) == 1:
+                dec.add("concat join: clips")
+                log.append("concat_f32")
+                y = _V(ins[0]["fn"], ins[0]["nb"], ins[0]["ndim"])
+            else:
+                dec.add("concat join: float32")
+                if any(t["k"] == "P" for t in ins) and any(t["k"] == "V" for t in ins):
+                    dec.add("concat: codes meet a clip, joined in float32")
+                log.append("concat_f32")
+                y = _F(ins[0]["ndim"])
+        elif spatial_desc(op) is not None:
+            padded = kind == "zeropad"
+            if src["k"] == "V" and not (padded and src["fn"] == "bin"):
+                src = pack_clip(src, name) or src
+            if src["k"] == "P" and src["ndim"] == 4 and not (padded and src["store"] == 1):
+                origin_tags(src, kind)
+                log.append("spatial_" + _STORE_NAME[src["store"]])
+                y = _P(src["store"], src["bits"], 4, src["grid"], src["origin"])
+            else:
+                if src["k"] == "P":
+                    log.append("unpack")
+                log.append("spatial_f32")
+                y = _F(4)
+        elif kind == "act" and _clip_of(op) is not None:
+            y = _V(*_clip_of(op), src["ndim"])
+        elif kind == "act" and op["fn"] == "ternary_tanh":
+            y = _V("grid", 1, src["ndim"])
+        elif kind in POOLS and new_pool(op):
+            mode = "max" if "max" in kind else "avg"
+            if src["k"] == "V" and src["fn"] != "grid" and src["ndim"] == 4:
+                src = pack_clip(src)
+            if src["k"] == "P" and src["ndim"] == 4:
+                log.append("pool_%s_%s" % (mode, _STORE_NAME[src["store"]]))
+                if src.get("origin") is not None and prod.get(srcs[i][0]) is not None and \
+                        spec[prod[srcs[i][0]]]["op"] == "act" and _epilogue_of(spec, names, cons, prod[srcs[i][0]]):
+                    dec.add("pool on the codes of a dwconv / tconv")
+                y = _P(src["store"], src["bits"], 2 if kind.startswith("global") else 4, False, src["origin"]) if mode == "max" \
+                    else _F(2 if kind.startswith("global") else 4)
+            else:
+                log.append("pool_%s_f32" % mode)
+                y = _F(2 if kind.startswith("global") else 4)
+        elif kind == "flatten":
+            y = _F(2)
+        else:                                                # bn, add, scale, softmax, the other activations, old-form pools and pads
+            y = _F(src["ndim"])
+        env[name] = y
+    return env, log, dec
+
+
+def _tail_at(spec, names, cons, ap):
+    """The ops (flatten, dense[, softmax]) the classifier tail at old-form avgpool `ap` takes with it, or ()."""
+    def only(i, kind):
+        c = cons.get(names[i], []) if i is not None else []
+        return c[0] if len(c) == 1 and spec[c[0]]["op"] == kind else None
+    fl = only(ap, "flatten")
+    de = only(fl, "dense")
+    if de is None:
+        return ()
+    sm = only(de, "softmax")
+    if sm is None:
+        return (fl, de) if de == len(spec) - 1 and not cons.get(names[de]) else ()
+    return (fl, de, sm) if len(cons.get(names[de], [])) == 1 and not cons.get(names[sm]) else ()
+
+
+def _epilogue_of(spec, names, cons, ai):
+    """True if activation op `ai` goes into the epilogue of a dwconv / tconv (alone behind it or behind its BN)."""
+    srcs = sources(spec)
+    prod = {n: i for i, n in enumerate(names)}
+    p = prod.get(srcs[ai][0])
+    if p is None or p != ai - 1 or cons.get(names[p], []) != [ai]:
+        return False
+    if spec[p]["op"] == "bn":
+        q = prod.get(srcs[p][0])
+        return q == p - 1 and spec[q]["op"] in ("dwconv", "tconv") and cons.get(names[q], []) == [p]
+    return spec[p]["op"] in ("dwconv", "tconv")
+
+
+# ---- hand-written specs, one per planner decision ---------------------------------------------------------------------------
+HAND_WIDE = []
+
+
+def _wide(name, net, log=None, layer_model=None):
+    """log: the launches GraphModel.kernel_log must hold, in order, written out by hand (None: plan()'s prediction alone
+    is asserted, as for every spec).  layer_model: "float conv" where LayerModel answers with its low-bit-only error."""
+    assert name not in [c["name"] for c in HAND_WIDE], name
+    HAND_WIDE.append(dict(name=name, spec=net.spec, x=net.images(), image=net.shape["input"], log=log, layer_model=layer_model))
+
+
+def _head(net, w="q4", flat=True):
+    if not flat:
+        net.pool("globalmaxpool")
+        return net.dense(10, *WEIGHT_OF[w], bias=True)
+    return net.classifier(*WEIGHT_OF[w])
+
+
+# GraphModel._spatial / _concat / _pack_clip: codes of every clip function and width through crop, upsample, pair zeropad
+# and a concat with the skip (pack_clips packs the skip to meet them); bin: the pad runs in float32
+_W_FOR = {"bin": "bin", "q2": "q2", "q3": "q4", "q4": "q4", "q8": "q8", "relu4": "q4", "relu8": "q8", "leaky4": "q4",
+          "leaky2": "q2", "tern": "tern"}
+for _a in ("bin", "q2", "q3", "q8", "relu4", "relu8", "leaky4", "leaky2", "tern"):
+    _w = _W_FOR[_a]
+    net = Net(_seed("through_" + _a), hw=(9, 7))
+    a0 = net.clipped(8, _w, _a, dst="a0")
+    net.crop(((1, 0), (0, 1)), src=a0, dst="cr")                      # 8 x 6
+    net.pool("maxpool", (2, 2), (2, 2), "valid", dst="p")             # 4 x 3: on the codes the crop left
+    a1 = net.clipped(12, _w, _a, dst="a1")
+    net.upsample((2, 2), dst="up")                                    # 8 x 6
+    net.concat(["up", "cr"], dst="cat")
+    net.zeropad2(((0, 1), (1, 0)), dst="zp")                          # 9 x 7
+    net.clipped(8, _w, _a, pad="valid")
+    _head(net, _w)
+    _wide("codes_through_%s" % _a, net)
+
+# _dwconv / _tconv: the packed output of a fused clip read by everything but a matching conv
+for _k in ("dwconv", "tconv"):
+    def _producer(net, a="q4", w="q4", bn=True, dst="y"):
+        if _k == "dwconv":
+            net.dwconv(1, *WEIGHT_OF[w], bias=True)
+        else:
+            net.tconv(8, *WEIGHT_OF[w], k=3, s=1, bias=True)
+        if bn:
+            net.bn()
+        return net.act(*ACT_OF[a], dst=dst)
+
+    def _stem(name, hw=(8, 8), c=8, a="q4"):
+        net = Net(_seed(name), hw=hw)
+        net.clipped(c, "q4", a, dst="a0")
+        return net
+
+    # a new-form max-pool and a global max-pool: pooled on the codes
+    net = _stem(_k + "_pool")
+    _producer(net)
+    net.pool("maxpool", (3, 3), (2, 2), "same")
+    net.clipped(8)
+    _head(net)
+    _wide(_k + "_then_new_maxpool", net, log=["pack", "depthwise_i4" if _k == "dwconv" else "tconv_i4_plain", "pool_max_i4"])
+    net = _stem(_k + "_gpool")
+    _producer(net, a="q8")
+    _head(net, "q8", flat=False)
+    _wide(_k + "_then_global_maxpool", net)
+    net = _stem(_k + "_avg")
+    _producer(net)
+    net.pool("avgpool", (2, 2), (2, 2), "valid")
+    _head(net)
+    _wide(_k + "_then_new_avgpool", net)
+    # a spatial op, then a conv
+    net = _stem(_k + "_spatial", hw=(9, 7))
+    _producer(net, a="relu4")
+    net.crop(((0, 1), (1, 0)))
+    net.upsample((1, 2))
+    net.clipped(8)
+    _head(net)
+    _wide(_k + "_then_spatial", net)
+    # flatten -> dense, and the network's last tensor
+    net = _stem(_k + "_flat", hw=(4, 4))
+    _producer(net)
+    _head(net)
+    _wide(_k + "_then_flatten_dense", net)
+    net = _stem(_k + "_last")
+    _producer(net, a="leaky4")
+    _wide(_k + "_clip_is_last", net)
+    # add, bn
+    net = _stem(_k + "_add")
+    y = _producer(net)
+    net.add("a0", y)
+    net.scale(0.5)
+    net.act()
+    _head(net)
+    _wide(_k + "_then_add", net)
+    net = _stem(_k + "_bn")
+    _producer(net, bn=False)
+    net.bn()
+    net.act()
+    _head(net)
+    _wide(_k + "_then_bn", net)
+    # two consumers that want different stores; a contraction whose join store differs (the re-clip branch)
+    net = _stem(_k + "_two")
+    y = _producer(net)
+    net.conv(8, "quantized", 4, src=y)
+    b1 = net.bn()
+    net.conv(8, "quantized", 8, src=y)
+    b2 = net.bn()
+    net.add(b1, b2)
+    net.act()
+    _head(net)
+    _wide(_k + "_two_consumers_two_stores", net)
+    net = _stem(_k + "_reclip")
+    _producer(net, a="bin")
+    net.dwconv(2, "quantized", 8, k=(2, 3))                           # 1-bit codes, 8-bit weights: another store
+    net.bn()
+    net.act("quantized_tanh", 8)
+    _head(net, "q8")
+    _wide(_k + "_other_store_wanted", net)
+    # the BN behind it read twice stays a tensor; the clip behind it read twice is still fused
+    net = _stem(_k + "_bn2")
+    _producer(net, bn=False, dst="y0")
+    net2 = net                                                        # (the producer without a BN, then one read twice)
+    net = _stem(_k + "_bn_twice")
+    if _k == "dwconv":
+        net.dwconv(1, bias=True)
+    else:
+        net.tconv(8, k=3, s=1, bias=True)
+    b = net.bn(dst="b")
+    a1 = net.act(src=b, dst="a1")
+    net.clipped(8, src=a1, dst="a2")
+    net.act("quantized_tanh", 8, src=b, dst="a3")
+    net.concat(["a2", "a3"])
+    net.clipped(8)
+    _head(net)
+    _wide(_k + "_bn_read_twice", net)
+    net = _stem(_k + "_clip_twice")
+    y = _producer(net)
+    net.pool("maxpool", (2, 2), (2, 2), "valid", src=y, dst="p")
+    net.clipped(8, s=2, src=y, dst="c")
+    net.concat(["p", "c"])
+    net.clipped(8)
+    _head(net)
+    _wide(_k + "_clip_read_twice", net)
+    # a batch-maximum activation in front: always read as float32
+    net = Net(_seed(_k + "_max"), hw=(8, 8))
+    net.conv(8, bias=True)
+    net.act("quantized_maxrelu", 4)
+    _producer(net)
+    net.clipped(8)
+    _head(net)
+    _wide(_k + "_behind_max_activation", net)
+    # ternary weights reading grid codes; float kind (LayerModel takes it, while it refuses a float conv)
+    net = Net(_seed(_k + "_tern"), hw=(8, 8))
+    net.clipped(8, "tern", "tern")
+    _producer(net, a="tern", w="tern")
+    net.clipped(8, "tern", "tern")
+    _head(net, "tern")
+    _wide(_k + "_ternary_on_grid_codes", net)
+    net = Net(_seed(_k + "_float"), hw=(8, 8))
+    if _k == "dwconv":
+        net.dwconv(2, "float", 0, s=2, bias="dyadic")
+    else:
+        net.tconv(5, "float", 0, k=3, s=2, pad="valid", bias="dyadic")
+    net.act()
+    net.clipped(8)
+    _head(net)
+    _wide(_k + "_float_kind", net)
+
+# _concat: a dwconv's packed codes meet an unmaterialised clip: pack_clips is false, the join falls to float32 ...
+net = Net(_seed("dw_meets_clip"), hw=(8, 8))
+a0 = net.clipped(8, dst="a0")
+net.dwconv(1, bias=True)
+net.bn()
+net.act(dst="d")
+net.concat(["d", "a0"])
+net.clipped(8)
+_head(net)
+_wide("dwconv_codes_meet_a_clip", net, log=["pack", "depthwise_i4", "concat_f32"])
+# ... and the same network with a tconv stays on codes
+net = Net(_seed("tc_meets_clip"), hw=(8, 8))
+a0 = net.clipped(8, dst="a0")
+net.tconv(8, k=3, s=1, bias=True)
+net.bn()
+net.act(dst="d")
+net.concat(["d", "a0"])
+net.clipped(8)
+_head(net)
+_wide("tconv_codes_meet_a_clip", net, log=["pack", "tconv_i4_plain", "concat_i4"])
+
+# tconv across a skip on the matrix pipe: a 64-channel 4 x 4 map, 2 x 2 / 2 and 4 x 4 / 2, int4 and int8
+for _a, _k2 in (("q4", 2), ("q8", 4), ("q4", 3)):
+    net = Net(_seed("unet_%s_%d" % (_a, _k2)), hw=(8, 8))
+    a0 = net.clipped(16, _a, _a, dst="skip")
+    net.pool("maxpool", 2)
+    net.clipped(64, _a, _a)
+    net.tconv(16, *WEIGHT_OF[_a], k=_k2, s=2, bias=True)
+    net.bn()
+    net.act(*ACT_OF[_a], dst="up")
+    net.concat(["up", "skip"])
+    net.clipped(16, _a, _a)
+    _head(net, _a, flat=False)
+    _s = {"q4": "i4", "q8": "i8"}[_a]
+    _wide("tconv_skip_%s_k%d" % (_a, _k2), net, log=["pack", "tconv_%s_mfma" % _s, "concat_" + _s, "pool_max_" + _s])
+
+# a depthwise block on the 16-bit lanes and on the plain form (dilated, strided, depth multiplier 2)
+for _n, _kw in (("pk16", dict()), ("dilated", dict(dil=2)), ("strided_m2", dict(M=2, s=2, k=(2, 3))), ("k5", dict(k=5))):
+    net = Net(_seed("sep_" + _n), hw=(9, 7))
+    net.clipped(16, dst="a0")
+    net.dwconv(bias=True, **_kw)
+    net.bn()
+    net.act()
+    net.clipped(12, k=1)
+    _head(net)
+    _wide("separable_" + _n, net, log=["pack", "depthwise_i4" if _n == "pk16" else "depthwise_i4_plain"])
+
+# _grid_plan: ternary activations behind a concat whose contractions disagree on the store (T2, I4 and I8) ...
+net = Net(_seed("tern_no_store"), hw=(8, 8))
+a0 = net.clipped(8, "tern", "tern", dst="a0")
+a1 = net.clipped(8, "tern", "tern", dst="a1")
+net.upsample((1, 1), src=a0, dst="u")
+net.concat(["u", "a1"], dst="cat")
+net.conv(8, "ternary", 1, src="cat")
+b1 = net.bn()
+net.conv(8, "quantized", 4, src="cat")
+b2 = net.bn()
+net.conv(8, "quantized", 8, src="cat")
+b3 = net.bn()
+net.add(b1, b2)
+net.add(net.cur, b3)
+net.act("ternary_tanh")
+_head(net, "tern")
+_wide("ternary_no_common_store", net, log=["spatial_f32", "concat_f32"])
+# ... and where they agree (all ternary): planes through the up-sampling and the join
+net = Net(_seed("tern_concat"), hw=(8, 8))
+a0 = net.clipped(8, "tern", "tern", dst="a0")
+net.pool("maxpool", 2)
+net.clipped(12, "tern", "tern")
+net.upsample((2, 2), dst="u")
+net.concat(["u", "a0"], dst="cat")
+net.clipped(8, "tern", "tern")
+_head(net, "tern")
+_wide("ternary_concat_on_planes", net, log=["spatial_t2", "concat_t2"])
+
+# _concat's joins
+net = Net(_seed("cat_fns"), hw=(8, 8))                       # one width, different functions: float32
+a0 = net.clipped(8, dst="a0")
+net.clipped(8, "q4", "q4", src=a0, dst="x")
+net.clipped(8, "q4", "relu4", src=a0, dst="y")
+net.concat(["x", "y"])
+net.clipped(8)
+_head(net)
+_wide("concat_one_width_two_functions", net, log=["concat_f32"])
+net = Net(_seed("cat_widths"), hw=(8, 8))                    # two widths in one store, as pooled codes: float32
+a0 = net.clipped(8, dst="a0")
+net.clipped(8, "q4", "q2", src=a0)
+net.pool("maxpool", (2, 2), (2, 2), "valid", dst="x")
+net.clipped(8, "q4", "q4", src=a0)
+net.pool("maxpool", (2, 2), (2, 2), "valid", dst="y")
+net.concat(["x", "y"])
+net.clipped(8)
+_head(net)
+_wide("concat_two_widths_one_store", net, log=["pool_max_i4", "pool_max_i4", "concat_f32"])
+net = Net(_seed("cat_twice"), hw=(8, 8))                     # one tensor twice, three inputs, a concat of a concat, last op
+a0 = net.clipped(5, dst="a0")
+a1 = net.clipped(3, src=a0, dst="a1")
+net.concat(["a0", "a0"], dst="c1")
+net.concat(["c1", "a1", "a0"], dst="c2")
+net.clipped(8, src="c2", dst="a2")
+net.concat(["a2", "c2", "a2", "a0"])
+_wide("concat_twice_nested_and_last", net, log=["concat_f32"] * 3)
+net = Net(_seed("cat_binpad"), hw=(8, 8))                    # a float32 pair zeropad behind a 1-bit clip beside packed codes
+a0 = net.clipped(8, "bin", "bin", dst="a0")
+net.crop(((1, 1), (1, 1)), src=a0, dst="c")
+net.zeropad2(((1, 1), (1, 1)), dst="z")
+net.pool("maxpool", (3, 3), (1, 1), "same", src=a0, dst="p")
+net.concat(["z", "p"])
+net.clipped(8, "bin", "bin")
+_head(net, "bin")
+_wide("binary_pad_beside_packed_branch", net, log=["spatial_bin", "unpack", "spatial_f32", "pool_max_bin", "concat_f32"])
+
+# a batch-maximum activation in front of a spatial op and of a concat
+net = Net(_seed("max_spatial"), hw=(8, 8))
+net.conv(8, bias=True)
+m = net.act("quantized_leakymaxrelu", 4, dst="m")
+net.upsample((2, 1), dst="u")
+net.crop(((4, 4), (0, 0)), dst="c")
+net.concat(["c", "m"])
+net.clipped(8)
+_head(net)
+_wide("max_activation_spatial_and_concat", net, log=["spatial_f32", "spatial_f32", "concat_f32"])
+
+# LayerModel's domain protocol: the grid kept through crop / upsample, dropped at a zeropad; a float conv still refused
+net = Net(_seed("lm_chain"), hw=(9, 7))
+net.clipped(8, "q4", "q4")
+net.crop(((1, 0), (0, 1)))
+net.upsample((2, 2))
+net.clipped(8, "q4", "q8")
+net.zeropad2(((1, 1), (2, 0)))
+net.clipped(8, "q8", "bin", pad="valid")
+net.upsample((1, 2))
+net.dwconv(1, "binary", 1, bias=True)
+net.bn()
+net.act("binary_tanh", 1)
+_head(net, "bin")
+_wide("layermodel_domains_through_spatial_ops", net)
+net = Net(_seed("lm_float"), hw=(8, 8))
+net.clipped(8)
+net.upsample((2, 2))
+net.conv(8, "float", 0, s=2)
+net.bn()
+net.act()
+_head(net)
+_wide("float_conv_behind_an_upsample", net, layer_model="float conv")
+
+CAPTURED = ("tconv_skip_q4_k2", "separable_pk16", "ternary_concat_on_planes")
+
+# ternary planes through a crop and a pair zeropad, each read by a ternary conv alone
+net = Net(_seed("tern_crop_pad"), hw=(9, 7))
+net.clipped(8, "tern", "tern")
+net.crop(((1, 0), (0, 1)))
+net.clipped(8, "tern", "tern")
+net.zeropad2(((1, 1), (0, 2)))
+net.clipped(8, "tern", "tern", pad="valid")
+_head(net, "tern")
+_wide("ternary_planes_through_crop_and_pad", net, log=["spatial_t2", "spatial_t2"])
+
+
+# ---- the second generator ---------------------------------------------------------------------------------------------------
+SEEDS_WIDE = range(64)
+CHANNELS_WIDE = (3, 5, 8, 12, 16, 24, 32, 33, 64)
+MAX_CONTRACTIONS_WIDE = 7
+
+
+def generate_wide(seed):
+    """(spec, images, image shape) of a random network over the wide vocabulary: a stem, 2 to 4 blocks out of {plain
+    group, pool, identity residual, encoder-decoder with a concat skip, separable block, dense-net growth, inception
+    branches}, some of them inside a residual add, and a head; weights and activations are drawn per op.  Seeds 0 mod 8
+    hold the matrix-pipe transposed convolution, seeds 1 mod 8 the 16-bit-lane depthwise form."""
+    rng = np.random.default_rng(70000 + seed)
+    force = {0: "mfma", 1: "pk16"}.get(seed % 8)
+    net = Net(60000 + seed, hw=(8, 8) if force == "mfma" or rng.random() < 0.5 else (9, 7))
+    pick = lambda seq: seq[int(rng.integers(len(seq)))]      # noqa: E731
+    use_max = force is None and rng.random() < 0.2
+    left = [MAX_CONTRACTIONS_WIDE - 1]                       # (the head's dense is one)
+    wkeys = ("bin", "tern", "q2", "q3", "q4", "q4", "q8")
+    akeys = ("bin", "q2", "q3", "q4", "q4", "q8", "relu4", "relu8", "leaky4", "leaky2", "tern")
+    small = tuple(c for c in CHANNELS_WIDE if c <= 33)
+
+    def act(a=None):
+        if a is None and use_max and rng.random() < 0.4:
+            return net.act(pick(("quantized_maxrelu", "quantized_leakymaxrelu")), pick((3, 4)))
+        return net.act(*ACT_OF[a or pick(akeys)])
+
+    def clipped(cout, w=None, a=None, **kw):
+        left[0] -= 1
+        net.conv(cout, *WEIGHT_OF[w or pick(wkeys)], bias=bool(rng.random() < 0.5), **kw)
+        if rng.random() < 0.8:
+            net.bn()
+        return act(a)
+
+    def finish(a=None):
+        """[bn] [clip] behind a dwconv / tconv: each present or absent; without a clip the constants are dyadic."""
+        has_bn, has_clip = rng.random() < 0.7, a is not None or rng.random() < 0.8
+        if has_bn:
+            net.bn() if has_clip else net.dyadic_bn()
+        return act(a) if has_clip else net.cur, has_clip
+
+    def depthwise(src, M=None, k=None, s=None, dil=None, w=None, a=None):
+        left[0] -= 1
+        s = pick((1, 1, 2)) if s is None else s
+        dil = (pick((1, 1, 2)) if s == 1 else 1) if dil is None else dil
+        clip = a is not None or rng.random() < 0.8
+        net.dwconv(pick((1, 1, 2)) if M is None else M, *WEIGHT_OF[w or pick(wkeys)], k=pick((3, 3, (2, 3), 5)) if k is None else k,
+                   s=s, dil=dil, bias=(bool(rng.random() < 0.5) if clip else "dyadic"), src=src)
+        if rng.random() < 0.7:
+            net.bn() if clip else net.dyadic_bn()
+        return act(a) if clip else net.cur
+
+    def separable(cur, **kw):
+        depthwise(cur, **kw)
+        return clipped(pick(small), k=1)
+
+    def encdec(cur, mfma=False):
+        h, w_, c = net.shape[cur]
+        up_kind = "tconv" if mfma else pick(("upsample", "tconv", "tconv"))
+        k, s = (pick((2, 3, 4)), 2) if mfma else pick(((2, 2), (3, 2), (4, 2), (3, 1), (2, 3)))
+        if up_kind == "upsample":
+            s = 2
+        a = pick(("q4", "q8")) if mfma else None
+        if s == 1:
+            mid = clipped(pick(small), src=cur)
+        elif s == 3:
+            net.pool("maxpool", (3, 3), (3, 3), "same", src=cur)
+            mid = clipped(pick(small))
+        elif mfma or rng.random() < 0.5:
+            net.pool("maxpool", (2, 2), (2, 2), "same", src=cur)
+            mid = clipped(64, a, a) if mfma else clipped(pick(small))
+        else:
+            mid = clipped(pick(small), s=2, src=cur)
+        if up_kind == "upsample":
+            up = net.upsample((2, 2))
+        else:
+            left[0] -= 1
+            clip = mfma or rng.random() < 0.85
+            net.tconv(pick((16, 32)) if mfma else pick(small), *WEIGHT_OF[a or pick(wkeys)], k=k, s=s,
+                      bias=(bool(rng.random() < 0.5) if clip else "dyadic"))
+            if rng.random() < 0.7:
+                net.bn() if clip else net.dyadic_bn()
+            up = act(a) if clip else net.cur
+        dh, dw = net.shape[up][0] - h, net.shape[up][1] - w_
+        assert dh >= 0 and dw >= 0, (dh, dw)
+        skip = cur
+        if dh or dw:
+            if rng.random() < 0.5:
+                up = net.crop(((0, dh), (dw, 0)), src=up)
+            else:
+                skip = net.zeropad2(((dh, 0), (0, dw)), src=cur)
+        net.concat([up, skip] if rng.random() < 0.7 else [skip, up])
+        return clipped(pick((16, 32)) if mfma else pick(small), a, a)
+
+    def growth(cur):
+        for _ in range(2):
+            new = clipped(pick((5, 8, 12)), src=cur)
+            cur = net.concat([cur, new])
+        return clipped(pick(small), k=1)
+
+    def inception(cur):
+        outs = []
+        for _ in range(int(rng.integers(2, 5))):
+            b = pick(("1x1", "3x3", "pool", "dw")) if left[0] > 2 else "pool"
+            if b == "1x1":
+                outs.append(clipped(pick((3, 5, 8, 12)), k=1, src=cur))
+            elif b == "3x3":
+                outs.append(clipped(pick((8, 16, 24)), src=cur))
+            elif b == "pool":
+                outs.append(net.pool("maxpool", (3, 3), (1, 1), "same", src=cur))
+            else:
+                outs.append(depthwise(cur, s=1, a=pick(akeys)))
+        net.concat(outs)
+        return clipped(pick(small), k=1)
+
+    stem_a = {"mfma": "q4", "pk16": "q4"}.get(force)
+    cur = clipped(pick((8, 12, 16)) if force is None else 16, stem_a, stem_a)
+    blocks = ([force] if force else []) + [pick(("group", "pool", "identity", "encdec", "encdec", "separable", "separable",
+                                                 "growth", "inception")) for _ in range(int(rng.integers(2, 5)))]
+    for block in blocks:
+        h, w_, c = net.shape[cur]
+        start = cur
+        residual = block in ("separable", "inception", "encdec") and left[0] >= 5 and rng.random() < 0.3
+        if block == "mfma":
+            cur = encdec(cur, mfma=True)
+        elif block == "pk16":
+            cur = separable(cur, M=1, k=3, s=1, dil=1, w="q4", a="q4")
+        elif block == "pool" and min(h, w_) >= 4:
+            cur = net.pool("maxpool", pick(((2, 2), (3, 3), (2, 3))), pick(((2, 2), (1, 1))), pick(("same", "valid")))
+        elif block == "identity" and left[0] >= 2:
+            clipped(c, src=cur)
+            left[0] -= 1
+            net.conv(c, *WEIGHT_OF[pick(wkeys)])
+            main = net.bn()
+            net.add(cur, main)
+            net.scale(0.5)
+            cur = act()
+        elif block == "encdec" and left[0] >= 3 and min(h, w_) >= 4:
+            cur = encdec(cur)
+        elif block == "separable" and left[0] >= 2:
+            cur = separable(cur, s=1 if residual else None)
+        elif block == "growth" and left[0] >= 3:
+            cur = growth(cur)
+        elif block == "inception" and left[0] >= 3:
+            cur = inception(cur)
+        elif left[0] >= 1:
+            cur = clipped(pick(small))
+        if residual and cur != start and net.shape[cur][:2] == net.shape[start][:2] and left[0] >= 1:
+            left[0] -= 1
+            net.conv(c, *WEIGHT_OF[pick(wkeys)], k=1)
+            main = net.bn()
+            net.add(start, main)
+            net.scale(0.5)
+            cur = act()
+    h, w_, c = net.shape[cur]
+    head = pick(("flat", "tail", "global"))
+    if head == "flat":
+        net.flatten()
+    elif head == "tail":
+        net.pool("avgpool", 8 if min(h, w_) >= 8 else 4 if min(h, w_) >= 4 else 2 if min(h, w_) >= 2 else 1)
+        net.flatten()
+    else:
+        net.pool("globalmaxpool")
+    net.dense(10, *WEIGHT_OF[pick(wkeys)], bias=bool(head != "tail" and rng.random() < 0.5))
+    if rng.random() < 0.25:
+        net.softmax()
+    assert left[0] >= 0, left
+    x = (rng.integers(0, 9, (N, net.hw[0], net.hw[1], 3)) / 8.0).astype(F32)
+    return net.spec, x, net.shape["input"]
+
+
+# ---- what the wide lists must cover ----------------------------------------------------------------------------------------
+def categories_wide(spec, image=(8, 8, 3)):
+    c = categories(spec) | plan(spec, image)[2]
+    ops = {op["op"] for op in spec}
+    if any(op["op"] == "zeropad" and spatial_desc(op) is not None for op in spec):
+        c.add("op zeropad (pair form)")
+    new = ops & {"concat", "crop", "upsample", "dwconv", "tconv"} or "op zeropad (pair form)" in c
+    if new and "concat" not in ops and not any(op["op"] in ("conv", "dense") and op["kind"] == "float" for op in spec):
+        c.add("LayerModel chain")
+    return c
+
+
+REQUIRED_OLD = frozenset(REQUIRED)
+REQUIRED_WIDE = (
+    {"op %s" % k for k in ("concat", "crop", "upsample", "zeropad (pair form)", "dwconv", "tconv")} |
+    {"codes through %s: %s" % (o, s) for o in ("crop", "upsample", "zeropad", "concat") for s in ("bin", "i4", "i8", "t2")
+     if (o, s) != ("zeropad", "bin")} |                       # a +-1 code has no zero
+    {"%s codes through a spatial op or concat" % k for k in ("relu", "leaky", "2-bit", "3-bit")} |
+    {"concat join: codes", "concat join: clips", "concat join: float32", "pack_clips join",
+     "packed producer, other store wanted", "dwconv clip in the epilogue", "tconv clip in the epilogue",
+     "BN behind dwconv read twice", "BN behind tconv read twice", "ternary: no common store behind a concat",
+     "tconv matrix-pipe form", "depthwise 16-bit-lane form", "LayerModel chain"} |
+    {"max activation in front of %s" % k for k in ("dwconv", "tconv", "spatial", "concat")})
+REQUIRED = REQUIRED | REQUIRED_WIDE

@@ -149,7 +149,7 @@ def test_every_required_category_appears_twice():
         if S.guard(spec, x) is None:
             for c in S.categories(spec):
                 count[c] = count.get(c, 0) + 1
-    assert not {c: count.get(c, 0) for c in S.REQUIRED if count.get(c, 0) < 2}
+    assert not {c: count.get(c, 0) for c in S.REQUIRED_OLD if count.get(c, 0) < 2}      # (REQUIRED as it was before the wide lists)
     # the generator reaches the int4 strip / fold / projection channel counts
     gen = [S.generate(s)[0] for s in S.SEEDS]
     for cin in (16, 32, 64):
@@ -174,3 +174,219 @@ def test_fusedmodel_group_decision_is_pinned():
     for seed in S.SEEDS:                      # the restatement the categories use is the engine's decision
         spec, _ = S.generate(seed)
         assert S.chain(spec) == (engine.FusedModel._group(spec) is not None), seed
+
+
+# ---- the wide vocabulary: concat, crop / upsample / pair zeropad, dwconv, tconv --------------------------------------------
+import json                               # noqa: E402
+import os                                 # noqa: E402
+
+import concat_cases as CC                 # noqa: E402
+import depthwise_cases as DW              # noqa: E402
+import spatial_cases as SP                # noqa: E402
+import spec_digest as G                   # noqa: E402
+import tconv_cases as TC                  # noqa: E402
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+
+
+def test_old_lists_are_the_parent_commits_lists():
+    """HAND and generate(seed) yield the specs and images they yielded before this file learnt the wide vocabulary:
+    digests of kernels, biases, BN constants, op dicts and images, recorded by golden/make_fixtures_spec_wide.py."""
+    with open(os.path.join(GOLDEN, "spec_graph_parent.json")) as f:
+        want = json.load(f)
+    assert {c["name"]: G.spec_digest(c["spec"], c["x"]) for c in S.HAND} == want["hand"]
+    assert {str(seed): G.spec_digest(*S.generate(seed)) for seed in S.SEEDS} == want["generated"]
+    assert len(want["hand"]) == 85 and len(want["generated"]) == 48
+
+
+def _old_reference_cases():
+    out = [("concat/" + n, net) for n, (net, _) in CC.SPECS.items()]
+    out += [("spatial/" + n, net) for n, (net, _) in SP.SPECS.items()]
+    out += [("chain/" + n, net) for n, (net, _) in SP.CHAINS.items()]
+    return out + [("spatial/binary_pad", SP.binary_pad()), ("spatial/binary_upsample", SP.binary_upsample())]
+
+
+def test_shared_reference_and_guard_equal_the_old_concat_and_spatial_ones():
+    """concat_cases.reference / guard and spatial_cases.reference / guard as they were before they became calls of the
+    shared functions, recorded on every spec they ran: every tensor of every network bit for bit, and the guard's answer."""
+    with open(os.path.join(GOLDEN, "spec_wide_old_reference.json")) as f:
+        meta = json.load(f)
+    last = np.load(os.path.join(GOLDEN, "spec_wide_old_reference.npz"))
+    cases = _old_reference_cases()
+    assert sorted(n for n, _ in cases) == sorted(meta) == sorted(last.files) and len(cases) == 20
+    for name, net in cases:
+        x = net.images()
+        assert G.spec_digest(net.spec, x) == meta[name]["spec"], name
+        for ref, guard in ((S.reference, S.guard), (CC.reference, CC.guard), (SP.reference, SP.guard)):
+            env = ref(net.spec, x, return_all=True)
+            assert {k: G.array_digest(v) for k, v in env.items()} == meta[name]["tensors"], name
+            assert same_bits(env[S.names_of(net.spec)[-1]], last[name]), name
+            assert guard(net.spec, x) == meta[name]["guard"], name
+            assert meta[name]["guard"] is None
+
+
+def test_shared_reference_equals_the_separable_and_unet_references():
+    import test_gpu_depthwise as TDW
+    import test_gpu_tconv as TTC
+    for kind, M in (("quantized", 1), ("quantized", 2), ("binary", 1), ("ternary", 1)):
+        spec = TDW.separable_spec(kind, M=M)
+        for seed in (0, 1):
+            x = TDW._inputs(seed)
+            assert same_bits(S.reference(spec, x), TDW.separable_reference(spec, x)), (kind, M)
+            assert S.guard(spec, x) is None
+    for skip in (True, False):
+        spec = TTC.unet_spec(skip=skip)
+        for seed in (0, 1):
+            x = TTC._images(seed)
+            assert same_bits(S.reference(spec, x), TTC.unet_reference(spec, x)), skip
+            assert S.guard(spec, x) is None
+
+
+_KIND = {DW.W_FLOAT: "float", DW.W_BINARY: "binary", DW.W_QUANT: "quantized", DW.W_TERNARY: "ternary"}
+_FN = {DW.FN_BINARY_TANH: "binary_tanh", DW.FN_QUANTIZED_TANH: "quantized_tanh", DW.FN_QUANTIZED_RELU: "quantized_relu",
+       DW.FN_QUANTIZED_LEAKYRELU: "quantized_leakyrelu", DW.FN_LEAKY_RELU: "leaky_relu"}
+
+
+def _one_op_spec(c, kernel, bias, bn, which):
+    """The case of depthwise_cases / tconv_cases as a spec: dwconv | tconv [-> bn] [-> act], the BN with eps 0, mean 0 and
+    variance 1, so that bn_constants gives the case's (inv, shift) exactly."""
+    op = {"op": which, "kind": _KIND[c["wkind"]], "kernel": kernel, "bias": bias, "strides": (c["stride"], c["stride"]),
+          "padding": "same" if c["same"] else "valid", "H": 1.0}
+    if c["wkind"] == DW.W_QUANT:
+        op["nb"] = c["wbits"]
+    if which == "dwconv":
+        op.update(dilation=c["dil"], depth_multiplier=c["M"])
+    spec = [op]
+    if bn is not None:
+        n = len(bn[0])
+        spec.append({"op": "bn", "eps": 0.0, "gamma": bn[0], "beta": bn[1], "mean": np.zeros(n, F32), "var": np.ones(n, F32)})
+    if c["fn"] != DW.FN_NONE:
+        act = {"op": "act", "fn": _FN[c["fn"]]}
+        if c["fn"] in DW.QACTS:
+            act["nb"] = c["act_bits"]
+        spec.append(act)
+    return spec
+
+
+def _one_op_cases(mod, which):
+    """Every epilogue and weight case whose operands pass guard: (compared, refused by guard)."""
+    done, refused = 0, 0
+    for c in mod.epilogue_cases() + mod.weight_cases():
+        x, kernel, bias, bn = mod.make_inputs(c)
+        xv = x if c["store"] == DW.F32 else DW.values_of(x, c["store"], c["x_bits"])
+        spec = _one_op_spec(c, kernel, bias, bn, which)
+        if S.guard(spec, xv) is not None:
+            refused += 1
+            continue
+        want = mod.reference(c, x, kernel, bias, bn)
+        got = S.reference(spec, xv)
+        what = mod.case_id(c)
+        if c["out_store"] == DW.F32:
+            assert same_bits(got, want), what
+        else:                                # packed: the values of the decoded codes
+            bits = c["act_bits"] if c["fn"] in DW.QACTS else 1
+            vals = DW.values_of(want, c["out_store"], bits)
+            np.testing.assert_array_equal(got, vals, err_msg=what)
+        done += 1
+    return done, refused
+
+
+def test_one_op_dwconv_specs_equal_depthwise_cases_reference():
+    done, refused = _one_op_cases(DW, "dwconv")
+    assert done >= 250 and refused <= 70, (done, refused)          # refused: the float32-store cases (inputs off the grid)
+
+
+def test_one_op_tconv_specs_equal_tconv_cases_reference():
+    done, refused = _one_op_cases(TC, "tconv")
+    assert done >= 200 and refused <= 70, (done, refused)
+
+
+WIDE = [(c["name"], c["spec"], c["x"], c["image"]) for c in S.HAND_WIDE]
+
+
+def test_wide_hand_specs_are_legal_and_exact_by_construction():
+    assert len({n for n, _, _, _ in WIDE}) == len(WIDE)
+    for name, spec, x, image in WIDE:
+        y = S.reference(spec, x)
+        assert y.shape[0] == S.N == x.shape[0] and y.size > 0 and np.all(np.isfinite(y)), name
+        assert S.guard(spec, x) is None, (name, S.guard(spec, x))          # the guard may reject no hand-written spec
+        assert sum(op["op"] in ("conv", "dense", "dwconv", "tconv") for op in spec) <= S.MAX_CONTRACTIONS_WIDE, name
+        assert x.shape[1:] == image and image[:2] in ((8, 8), (9, 7), (4, 4)), name
+    assert set(S.CAPTURED) <= {n for n, _, _, _ in WIDE}
+    for case in S.HAND_WIDE:                  # the logs written out by hand are what the restated planner predicts
+        if case["log"] is not None:
+            assert S.plan(case["spec"], case["image"])[1] == case["log"], case["name"]
+
+
+def test_wide_generated_specs_are_legal_deterministic_and_mostly_exact():
+    rejected, with_max, shapes = [], 0, set()
+    for seed in S.SEEDS_WIDE:
+        spec, x, image = S.generate_wide(seed)
+        again, x2, _ = S.generate_wide(seed)
+        assert _same_spec(spec, again) and np.array_equal(x, x2), seed
+        y = S.reference(spec, x)
+        assert y.shape[0] == S.N == x.shape[0] and y.size > 0 and np.all(np.isfinite(y)), seed
+        assert x.shape[1:] in ((8, 8, 3), (9, 7, 3)) and np.array_equal(x * 8, np.rint(x * 8)), seed
+        shapes.add(x.shape[1:])
+        assert sum(op["op"] in ("conv", "dense", "dwconv", "tconv") for op in spec) <= S.MAX_CONTRACTIONS_WIDE, seed
+        env = S.reference(spec, x, return_all=True)
+        for op, name in zip(spec, S.names_of(spec)):
+            if op["op"] in ("conv", "tconv"):
+                assert env[name].shape[-1] in S.CHANNELS_WIDE, (seed, env[name].shape)
+            if op["op"] == "avgpool":         # averages over power-of-two areas only
+                assert not S.new_pool(op) and op["size"] & (op["size"] - 1) == 0, seed
+        with_max += any(op["op"] == "act" and op["fn"] in S.M.FNS for op in spec)
+        cats = S.categories_wide(spec, image)
+        if seed % 8 == 0:
+            assert "tconv matrix-pipe form" in cats, seed
+            assert any(op["op"] == "tconv" and op["kernel"].shape[3] == 64 and op["kernel"].shape[2] % 16 == 0 for op in spec)
+        if seed % 8 == 1:
+            assert "depthwise 16-bit-lane form" in cats, seed
+        why = S.guard(spec, x)
+        if why is not None:
+            rejected.append((seed, why))
+    assert len(S.SEEDS_WIDE) == 64 and shapes == {(8, 8, 3), (9, 7, 3)}
+    assert len(rejected) <= 8, rejected
+    assert 6 <= with_max <= 20, with_max      # about one network in five
+
+
+def test_all_four_lists_cover_required():
+    count = {}
+    for _, spec, _, image in WIDE:
+        for c in S.categories_wide(spec, image):
+            count[c] = count.get(c, 0) + 1
+    for seed in S.SEEDS_WIDE:
+        spec, x, image = S.generate_wide(seed)
+        if S.guard(spec, x) is None:
+            for c in S.categories_wide(spec, image):
+                count[c] = count.get(c, 0) + 1
+    assert S.REQUIRED == S.REQUIRED_OLD | S.REQUIRED_WIDE and len(S.REQUIRED_WIDE) == 42
+    assert not {c for c in S.REQUIRED_WIDE if count.get(c, 0) < 1}
+    # the decisions the hand-written list visits beyond the required ones
+    for k in ("dwconv", "tconv"):
+        for reader in ("maxpool (new form)", "avgpool (new form)", "globalmaxpool", "crop", "flatten", "add", "conv", "dwconv",
+                       "concat"):
+            assert count.get("packed %s output read by %s" % (k, reader), 0) >= 1, (k, reader)
+        assert count.get("packed %s output is the last tensor" % k, 0) >= 1 and count.get("clip behind %s read twice" % k, 0) >= 1
+    assert count.get("concat: codes meet a clip, joined in float32", 0) >= 1
+
+
+def test_fused_engines_group_takes_no_wide_spec():
+    for name, spec, _, _ in WIDE:
+        assert engine.FusedModel._group(spec) is None and not S.chain(spec), name
+
+
+def test_recorded_coverage_table_is_current():
+    """golden/spec_wide_coverage.json: per category of REQUIRED_WIDE the first two hand-written cases or seeds that cover
+    it, hand-written cases first (the table the pull request's summary points to)."""
+    cover = {}
+    for name, spec, _, image in WIDE:
+        for c in S.categories_wide(spec, image):
+            cover.setdefault(c, []).append(name)
+    for seed in S.SEEDS_WIDE:
+        spec, x, image = S.generate_wide(seed)
+        if S.guard(spec, x) is None:
+            for c in S.categories_wide(spec, image):
+                cover.setdefault(c, []).append("seed %d" % seed)
+    with open(os.path.join(GOLDEN, "spec_wide_coverage.json")) as f:
+        assert json.load(f) == {c: cover[c][:2] for c in sorted(S.REQUIRED_WIDE)}
