@@ -29,6 +29,8 @@ from .layers.depthwise import (DepthwiseConv2D, BinaryDepthwiseConv2D, Quantized
                                TernaryDepthwiseConv2D)
 from .layers.conv_transpose import (Conv2DTranspose, BinaryConv2DTranspose, QuantizedConv2DTranspose,  # noqa: F401
                                     TernaryConv2DTranspose)
+from .layers.grouped import (GroupedConv2D, BinaryGroupedConv2D, QuantizedGroupedConv2D,  # noqa: F401
+                             TernaryGroupedConv2D)
 
 __all__ = [
     "binary_tanh", "binarize", "binary_sigmoid", "quantize", "quantized_tanh", "quantized_relu", "quantized_leakyrelu",
@@ -41,4 +43,5 @@ __all__ = [
     "ZeroPadding2D", "Cropping2D", "UpSampling2D",
     "DepthwiseConv2D", "BinaryDepthwiseConv2D", "QuantizedDepthwiseConv2D", "TernaryDepthwiseConv2D",
     "Conv2DTranspose", "BinaryConv2DTranspose", "QuantizedConv2DTranspose", "TernaryConv2DTranspose",
+    "GroupedConv2D", "BinaryGroupedConv2D", "QuantizedGroupedConv2D", "TernaryGroupedConv2D",
 ]

@@ -1,5 +1,6 @@
 """ctypes binding of include/qnn_abi.h, qnn_abi_dilation.h, qnn_abi_qact.h, qnn_abi_maxact.h, qnn_abi_pool.h,
-qnn_abi_scaled.h, qnn_abi_concat.h, qnn_abi_spatial.h, qnn_abi_depthwise.h and qnn_abi_tconv.h (csrc/libqnn_hip.so).
+qnn_abi_scaled.h, qnn_abi_concat.h, qnn_abi_spatial.h, qnn_abi_depthwise.h, qnn_abi_tconv.h and qnn_abi_gconv.h
+(csrc/libqnn_hip.so).
 
 The library is loaded eagerly and loudly: a missing or unloadable .so raises at
 import time of any op that needs it (there is no CPU implementation to fall back
@@ -74,6 +75,10 @@ DW_MAX_WINDOW = 7
 # include/qnn_abi_tconv.h: Conv2DTranspose with float / binary / quantized / ternary weights on float32 and packed codes
 EXPORTS_TCONV = ["qnn_tconv_prepack", "qnn_tconv_free", "qnn_tconv_dequant", "qnn_tconv_out_hw", "qnn_tconv_forward"]
 TC_MAX_WINDOW, TC_MAX_STRIDE = 8, 4
+
+# include/qnn_abi_gconv.h: Conv2D(groups=g) with float / binary / quantized / ternary weights on float32 and packed codes
+EXPORTS_GCONV = ["qnn_gconv_prepack", "qnn_gconv_free", "qnn_gconv_dequant", "qnn_gconv_out_hw", "qnn_gconv_forward"]
+GC_MAX_WINDOW = 7
 
 
 class Spatial2D(ctypes.Structure):
@@ -211,8 +216,13 @@ def load():
     lib.qnn_tconv_dequant.argtypes = [vp, vp, vp]
     lib.qnn_tconv_out_hw.argtypes = [vp, ci, ci, ctypes.POINTER(ci), ctypes.POINTER(ci)]
     lib.qnn_tconv_forward.argtypes = [vp, vp, ci, ci, ci, ci, ci, ctypes.POINTER(Epilogue), vp, vp]
+    lib.qnn_gconv_prepack.argtypes = [ci, ci, fl, vp, ci, ci, ci, ci, ci, vp, ci, ci, ci, ci, ci, vp, ctypes.POINTER(vp)]
+    lib.qnn_gconv_free.argtypes = [vp]
+    lib.qnn_gconv_dequant.argtypes = [vp, vp, vp]
+    lib.qnn_gconv_out_hw.argtypes = [vp, ci, ci, ctypes.POINTER(ci), ctypes.POINTER(ci)]
+    lib.qnn_gconv_forward.argtypes = [vp, vp, ci, ci, ci, ci, ci, ctypes.POINTER(Epilogue), vp, vp]
     for name in (EXPORTS + EXPORTS_DILATION + EXPORTS_QACT + EXPORTS_MAXACT + EXPORTS_POOL + EXPORTS_SCALED + EXPORTS_CONCAT
-                 + EXPORTS_SPATIAL + EXPORTS_DEPTHWISE + EXPORTS_TCONV):   # every symbol the headers declare must be exported
+                 + EXPORTS_SPATIAL + EXPORTS_DEPTHWISE + EXPORTS_TCONV + EXPORTS_GCONV):   # every symbol the headers declare must be exported
         getattr(lib, name)
     _lib = lib
     return lib
@@ -1079,4 +1089,88 @@ def tconv(w, x, x_store, x_bits, N, H, W, bn_inv=None, bn_shift=None, fn=FN_NONE
     if rc == QNN_EUNSUPPORTED:
         raise QnnUnsupported("qnn_tconv_forward: " + load().qnn_last_error().decode(errors="replace"))
     check(rc, "qnn_tconv_forward")
+    return y, Ho, Wo
+
+
+def gconv_out_hw(size, k, stride, same_pad, dilation=1):
+    """Output size of one axis of a grouped convolution: TensorFlow's rule on the effective window (csrc/qnn_conv_geom.h)."""
+    return out_hw(size, k, stride, same_pad, dilation)
+
+
+class GConvWeights:
+    """Owner of an opaque qnn_gconv_weights_t handle (include/qnn_abi_gconv.h).  kernel: float32 CUDA tensor in Keras'
+    grouped layout (kh, kw, Cin / groups, Cout); bias: (Cout,) or None."""
+
+    def __init__(self, wkind, wbits, H, kernel, bias, groups, stride, same_pad, store, dilation=(1, 1)):
+        kernel = require_cuda(kernel, "gconv prepack kernel")
+        if kernel.dim() != 4:
+            raise QnnError("gconv prepack: the kernel must be (kh, kw, Cin / groups, Cout), got %s" % (tuple(kernel.shape),))
+        kh, kw, cg, cout = kernel.shape
+        groups = int(groups)
+        bias = require_cuda(bias, "gconv prepack bias") if bias is not None else None
+        if bias is not None and bias.numel() != cout:
+            raise QnnError("gconv prepack: bias of %d values for %d filters" % (bias.numel(), cout))
+        self.shape = (kh, kw, cg, cout)
+        self.groups, self.cin, self.cout = groups, cg * groups, cout
+        self.wkind, self.wbits, self.store = wkind, wbits, store
+        self.stride, self.same_pad = int(stride), bool(same_pad)
+        self.dilation = (int(dilation[0]), int(dilation[1]))
+        self.handle = ctypes.c_void_p(None)
+        release_deferred()
+        rc = load().qnn_gconv_prepack(wkind, wbits, float(H), ptr(kernel), kh, kw, self.cin, cout, groups, ptr(bias),
+                                      self.stride, 1 if same_pad else 0, self.dilation[0], self.dilation[1], store,
+                                      stream_ptr(), ctypes.byref(self.handle))
+        if rc == QNN_EUNSUPPORTED:
+            raise QnnUnsupported("qnn_gconv_prepack: " + load().qnn_last_error().decode(errors="replace"))
+        check(rc, "qnn_gconv_prepack")
+        self.device = kernel.device
+
+    def dequant(self):
+        out = torch.empty(self.shape, dtype=torch.float32, device=self.device)
+        check(load().qnn_gconv_dequant(self.handle, ptr(out), stream_ptr()), "qnn_gconv_dequant")
+        return out
+
+    def out_hw(self, H, W):
+        Ho, Wo = ctypes.c_int(0), ctypes.c_int(0)
+        check(load().qnn_gconv_out_hw(self.handle, int(H), int(W), ctypes.byref(Ho), ctypes.byref(Wo)), "qnn_gconv_out_hw")
+        return Ho.value, Wo.value
+
+    def __del__(self):
+        try:
+            _release("qnn_gconv_free", self.handle)
+            self.handle = ctypes.c_void_p(None)
+        except Exception:
+            pass
+
+
+def gconv(w, x, x_store, x_bits, N, H, W, bn_inv=None, bn_shift=None, fn=FN_NONE, act_bits=0, out_store=STORE_F32,
+          out=None, epilogue=None):
+    """qnn_gconv_forward: x is a float32 NHWC CUDA tensor (x_store = STORE_F32) or int32 packed words as pack() writes
+    them.  Returns (y, Ho, Wo): y float32 (N, Ho, Wo, Cout) or int32 (N * Ho * Wo, words).  `epilogue`: a ready Epilogue
+    instead of the keyword fields (tests of the refusals).  A refusal with QNN_EUNSUPPORTED raises QnnUnsupported."""
+    Ho, Wo = w.out_hw(H, W)
+    if Ho <= 0 or Wo <= 0:
+        raise QnnError("gconv: empty output: %dx%d input, %dx%d window dilated %dx%d, stride %d, %s padding"
+                       % (H, W, w.shape[0], w.shape[1], w.dilation[0], w.dilation[1], w.stride,
+                          "same" if w.same_pad else "valid"))
+    if x_store == STORE_F32:
+        x = require_cuda(x, "gconv")
+    elif not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.int32 and x.is_contiguous()):
+        raise QnnError("gconv: a packed input must be a contiguous int32 CUDA tensor")
+    if out_store == STORE_F32:
+        shape, dt = (N, Ho, Wo, w.cout), torch.float32
+    else:
+        shape, dt = (N * Ho * Wo, words(out_store, w.cout)), torch.int32
+    if out is None:
+        y = torch.empty(shape, dtype=dt, device=x.device)
+    else:
+        if tuple(out.shape) != shape or out.dtype != dt or not out.is_contiguous() or out.device != x.device:
+            raise QnnError("gconv: `out` must be a contiguous %s tensor of shape %s on %s" % (dt, shape, x.device))
+        y = out
+    epi = epilogue if epilogue is not None else make_epilogue(bn_inv, bn_shift, fn, act_bits, 1, out_store, flags=0)
+    rc = load().qnn_gconv_forward(w.handle, ptr(x), int(x_store), int(x_bits), int(N), int(H), int(W),
+                                  ctypes.byref(epi), ptr(y), stream_ptr())
+    if rc == QNN_EUNSUPPORTED:
+        raise QnnUnsupported("qnn_gconv_forward: " + load().qnn_last_error().decode(errors="replace"))
+    check(rc, "qnn_gconv_forward")
     return y, Ho, Wo

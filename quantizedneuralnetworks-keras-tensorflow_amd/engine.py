@@ -22,6 +22,8 @@
                       following bn and low-bit activation go into its epilogue and a packed producer into its input, so
                       pack -> dwconv -> 1x1 conv keeps codes throughout.  {"op": "tconv"} (transposed convolution,
                       qnn_tconv_forward) runs under the same rules; the codes it leaves meet a skip as codes in a concat.
+                      {"op": "gconv"} (grouped convolution, qnn_gconv_forward) runs under the rules of tconv: its codes
+                      meet a skip as codes in a concat too.
   LayerModel          the Keras-compatible layer objects called one by one (float32 NHWC in, float32 NHWC out per
                       layer: "M0" traffic model); nets.Model.conv_output reads intermediate tensors through it.
 
@@ -43,6 +45,7 @@ from .layers.depthwise import (DepthwiseConv2D, BinaryDepthwiseConv2D, Quantized
                                TernaryDepthwiseConv2D)
 from .layers.conv_transpose import (Conv2DTranspose, BinaryConv2DTranspose, QuantizedConv2DTranspose,
                                     TernaryConv2DTranspose)
+from .layers.grouped import GroupedConv2D, BinaryGroupedConv2D, QuantizedGroupedConv2D, TernaryGroupedConv2D
 from .layers import binary_ops, quantized_ops, ternary_ops
 
 F32 = np.float32
@@ -175,8 +178,8 @@ def _weights_fit(op, store):
 
 def _dilation(op):
     """dilation_rate of a conv op as a pair ((1, 1) where the spec says nothing: dense ops, ordinary windows); a dwconv op
-    carries it as `dilation`."""
-    d = op.get("dilation", (1, 1)) if op["op"] == "dwconv" else op.get("dilation_rate", (1, 1))
+    and a gconv op carry it as `dilation`."""
+    d = op.get("dilation", (1, 1)) if op["op"] in ("dwconv", "gconv") else op.get("dilation_rate", (1, 1))
     return (int(d), int(d)) if np.isscalar(d) else (int(d[0]), int(d[1]))
 
 
@@ -210,6 +213,12 @@ def _prepack(op, store, device, stride=1, same_pad=True):
             raise ValueError("tconv: kernel %s is not (kh, kw, Cout, Cin)" % (tuple(kernel.shape),))
         return _abi.TConvWeights(_wkind(op), int(op.get("nb", 1)), float(op.get("H", 1.0)), kernel, bias, stride, same_pad,
                                  store)
+    if op["op"] == "gconv":                  # Keras' grouped kernel (kh, kw, Cin / groups, Cout)
+        groups = int(op.get("groups", 1))
+        if kernel.dim() != 4 or groups < 1 or kernel.shape[3] % groups != 0:
+            raise ValueError("gconv: kernel %s is not (kh, kw, Cin / groups, Cout) for groups=%d" % (tuple(kernel.shape), groups))
+        return _abi.GConvWeights(_wkind(op), int(op.get("nb", 1)), float(op.get("H", 1.0)), kernel, bias, groups, stride,
+                                 same_pad, store, dilation=_dilation(op))
     return _abi.Weights(_wkind(op), int(op.get("nb", 1)), float(op.get("H", 1.0)), kernel, bias,
                         stride, same_pad, store, dilation=_dilation(op))
 
@@ -457,6 +466,12 @@ def _refuse_dwconv(spec, who):
         raise _abi.NotFusable("%s: op 'dwconv' (depthwise convolution) is not expressed by this engine; use GraphModel" % who)
 
 
+def _refuse_gconv(spec, who):
+    """The packed engines express a chain of full convolutions; a grouped convolution runs in GraphModel (and LayerModel)."""
+    if any(op["op"] == "gconv" for op in spec):
+        raise _abi.NotFusable("%s: op 'gconv' (grouped convolution) is not expressed by this engine; use GraphModel" % who)
+
+
 def _refuse_tconv(spec, who):
     """The fused engines plan forward convolutions only: a spec that holds a transposed convolution runs on GraphModel."""
     if any(op["op"] == "tconv" for op in spec):
@@ -611,6 +626,7 @@ class FusedModel(_DomainFlag):
         _refuse_concat(spec, "FusedModel")
         _refuse_dwconv(spec, "FusedModel")
         _refuse_tconv(spec, "FusedModel")
+        _refuse_gconv(spec, "FusedModel")
         _refuse_spatial(spec, "FusedModel")
         _refuse_max_acts(spec, "FusedModel")
         groups = self._group(spec)
@@ -1021,7 +1037,7 @@ class GraphModel:
     def _grid_store(self, c):
         """The store at which contraction op `c` reads ternary codes {-1, 0, 1} (_contract), None for float weights."""
         op = self.spec[c]
-        wstore = _wstore(op) if op["op"] in ("conv", "dense", "dwconv", "tconv") else None
+        wstore = _wstore(op) if op["op"] in ("conv", "dense", "dwconv", "tconv", "gconv") else None
         if wstore is None:
             return None
         if op["kind"] == "ternary" and TERNARY_T2:
@@ -1200,6 +1216,11 @@ class GraphModel:
         of the last op fused into it)."""
         return self._dwconv(i, op, src, run=_abi.tconv)
 
+    def _gconv(self, i, op, src):
+        """Grouped-convolution op `i` on `src` (include/qnn_abi_gconv.h) under _dwconv's planner rules: (result, index of
+        the last op fused into it)."""
+        return self._dwconv(i, op, src, run=_abi.gconv)
+
     def _dwconv(self, i, op, src, run=None):
         """Depthwise op `i` on `src` (include/qnn_abi_depthwise.h): (result, index of the last op fused into it).  The
         planner rules of a conv: a following BN that is the tensor's only consumer goes into the epilogue, a packed producer
@@ -1256,7 +1277,7 @@ class GraphModel:
         g, spec = self.graph, self.spec
         env = {"input": _images(x, "GraphModel.forward")}
         skip = set()
-        upsampled = set()                    # tensors a tconv left as packed codes
+        upsampled = set()                    # tensors a tconv or a gconv left as packed codes
         for i, op in enumerate(spec):
             if i in skip:
                 continue
@@ -1275,12 +1296,13 @@ class GraphModel:
                     skip.add(i + 1)
                     name = g.names[i + 1]
                 y = self._contract(i, op, src, inv, shift)
-            elif kind in ("dwconv", "tconv"):
-                y, last = self._dwconv(i, op, src) if kind == "dwconv" else self._tconv(i, op, src)
+            elif kind in ("dwconv", "tconv", "gconv"):
+                y, last = {"dwconv": self._dwconv, "tconv": self._tconv, "gconv": self._gconv}[kind](i, op, src)
                 skip.update(range(i + 1, last + 1))
                 name = g.names[last]
-                if kind == "tconv" and isinstance(y, _Packed):
-                    upsampled.add(name)      # a decoder's codes: the skip they are joined with is packed to meet them
+                if kind in ("tconv", "gconv") and isinstance(y, _Packed):
+                    # a decoder's codes, or a grouped 3x3's: the skip they are joined with is packed to meet them
+                    upsampled.add(name)
             elif kind == "bn":
                 y = _bn_apply(self._plain(src), *g.bn[i])
             elif kind == "add":
@@ -1402,6 +1424,7 @@ class ResidualFusedModel(_DomainFlag):
         _refuse_concat(spec, "ResidualFusedModel")
         _refuse_dwconv(spec, "ResidualFusedModel")
         _refuse_tconv(spec, "ResidualFusedModel")
+        _refuse_gconv(spec, "ResidualFusedModel")
         _refuse_spatial(spec, "ResidualFusedModel")
         _refuse_max_acts(spec, "ResidualFusedModel")
         self.first_layer = first_layer
@@ -1963,9 +1986,28 @@ class LayerModel:
         self.graph = _SpecGraph(spec, device)
         prev_act = {}
         for i, op in enumerate(spec):
-            if op["op"] not in ("conv", "dense", "dwconv", "tconv"):
+            if op["op"] not in ("conv", "dense", "dwconv", "tconv", "gconv"):
                 continue
             kw = dict(use_bias=op.get("bias") is not None, device=device)
+            if op["op"] == "gconv":
+                kh, kw_, cg, cout = op["kernel"].shape
+                groups = int(op.get("groups", 1))
+                kw.update(strides=tuple(op.get("strides", (1, 1))), padding=op.get("padding", "same"),
+                          dilation_rate=_dilation(op), groups=groups)
+                H = float(op.get("H", 1.0))
+                if op["kind"] == "binary":
+                    layer = BinaryGroupedConv2D(cout, (kh, kw_), H=H, **kw)
+                elif op["kind"] == "quantized":
+                    layer = QuantizedGroupedConv2D(cout, (kh, kw_), H=H, nb=op["nb"], **kw)
+                elif op["kind"] == "ternary":
+                    layer = TernaryGroupedConv2D(cout, (kh, kw_), H=H, **kw)
+                else:
+                    layer = GroupedConv2D(cout, (kh, kw_), **kw)
+                layer.build((None, None, None, cg * groups))
+                ws = [op["kernel"]] + ([op["bias"]] if op.get("bias") is not None else [])
+                layer.set_weights(ws)
+                self.layers[i] = layer
+                continue
             if op["op"] == "tconv":
                 kh, kw_, cout, cin = op["kernel"].shape
                 kw.update(strides=tuple(op.get("strides", (1, 1))), padding=op.get("padding", "same"))
@@ -2046,7 +2088,7 @@ class LayerModel:
             src, d = env[sname], None
             if kind == "add":
                 y = _add(src, env[op["b"]])
-            elif kind in ("conv", "dense", "dwconv", "tconv"):
+            elif kind in ("conv", "dense", "dwconv", "tconv", "gconv"):
                 layer = self.layers[i]
                 layer.input_domain = dom.get(sname) if self.fuse_input_activation else None
                 y = layer(src)

@@ -320,11 +320,11 @@ class Model:
                 self.engine = engine.ResidualFusedModel(spec, device,
                                                         first_layer=first_layer if first_layer in ("auto", "image") else "exact")
             except _abi.NotFusable:
-                # only the batch-scaled activations (float32 between the layers), channel concatenation, depthwise and
-                # transposed convolution and the new-form
+                # only the batch-scaled activations (float32 between the layers), channel concatenation, depthwise,
+                # transposed and grouped convolution and the new-form
                 # spatial ops (crop, upsample, pair-form zeropad) are handed on; anything else the residual engine
                 # refuses stays an error
-                if not any((op["op"] == "act" and op["fn"] in BATCH_SCALED_ACTIVATIONS) or op["op"] in ("concat", "dwconv", "tconv") or
+                if not any((op["op"] == "act" and op["fn"] in BATCH_SCALED_ACTIVATIONS) or op["op"] in ("concat", "dwconv", "tconv", "gconv") or
                            (op["op"] in engine._SPATIAL and engine._new_spatial(op)) for op in spec):
                     raise
                 self.engine = engine.GraphModel(spec, device, scaled_codes=scaled_codes)
@@ -517,6 +517,10 @@ def _pool_op(kind, c, name):
 _TCONV_KINDS = {"Conv2DTranspose": "float", "BinaryConv2DTranspose": "binary", "QuantizedConv2DTranspose": "quantized",
                 "TernaryConv2DTranspose": "ternary"}
 
+_GCONV_KINDS = {"GroupedConv2D": "float", "BinaryGroupedConv2D": "binary", "QuantizedGroupedConv2D": "quantized",
+                "TernaryGroupedConv2D": "ternary"}
+_GCONV_OLD_KINDS = {"Conv2D": "float", "BinaryConv2D": "binary", "QuantizedConv2D": "quantized", "TernaryConv2D": "ternary"}
+
 
 def spec_from_keras_npz(path, wbits=None, abits=None):
     """Rebuild a net spec from a Keras 2.1.3 checkpoint converted by tools/import_keras_hdf5.py
@@ -545,7 +549,33 @@ def spec_from_keras_npz(path, wbits=None, abits=None):
         if src == spec_alias:
             src = "input"
         op = None
-        if cls in ("QuantizedConv2D", "BinaryConv2D", "Conv2D"):
+        if cls in _GCONV_KINDS or (cls in _GCONV_OLD_KINDS and int(c.get("groups", 1) or 1) > 1):
+            # keras.layers.Conv2D(groups=g) and the low-bit classes of layers/grouped.py -> gconv.  The kernel is
+            # (kh, kw, Cin / groups, Cout); a config of an old class name without `groups` (or with 1) stays a conv.
+            _spatial_data_format(c, name)
+            if c.get("activation") not in (None, "linear"):
+                raise ValueError("layer %r has activation=%r; only 'linear' is supported in a grouped %s" % (name, c["activation"], cls))
+            groups = int(c.get("groups", 1) or 1)
+            kernel = d[name + "/kernel"]
+            if groups < 1 or kernel.ndim != 4 or kernel.shape[3] % groups != 0 or int(c.get("filters", kernel.shape[3])) % groups != 0:
+                raise ValueError("layer %r has groups=%d, which does not divide its %d filters" % (name, groups, kernel.shape[-1]))
+            cin = c.get("batch_input_shape", (None,))[-1] if c.get("batch_input_shape") else None
+            if cin is not None and (int(cin) % groups != 0 or int(cin) // groups != kernel.shape[2]):
+                raise ValueError("layer %r has groups=%d, which does not divide its %d input channels into the kernel's %d"
+                                 % (name, groups, int(cin), kernel.shape[2]))
+            kind = _GCONV_KINDS.get(cls) or _GCONV_OLD_KINDS[cls]
+            op = {"op": "gconv", "kind": kind, "kernel": kernel,
+                  "bias": d[name + "/bias"] if c.get("use_bias", True) else None, "groups": groups,
+                  "strides": tuple(int(v) for v in c["strides"]), "padding": str(c["padding"]).lower(),
+                  "dilation": tuple(int(v) for v in c.get("dilation_rate", (1, 1))),
+                  "H": float(c.get("H", 1.0)) if kind != "float" else 1.0,
+                  "klm": np.float32(c.get("kernel_lr_multiplier") or 1.0)}
+            if kind == "quantized":
+                nb = c.get("nb") if cls in _GCONV_KINDS else None      # the new class serialises `nb`, the old ones do not
+                if nb is None and wbits is None:
+                    raise ValueError("layer %r is a grouped %s: pass wbits (`nb` is not serialised)" % (name, cls))
+                op["nb"] = int(nb if nb is not None else wbits)
+        elif cls in ("QuantizedConv2D", "BinaryConv2D", "Conv2D"):
             kind = {"QuantizedConv2D": "quantized", "BinaryConv2D": "binary", "Conv2D": "float"}[cls]
             op = {"op": "conv", "kind": kind, "kernel": d[name + "/kernel"],
                   "bias": d[name + "/bias"] if c.get("use_bias", True) else None,
