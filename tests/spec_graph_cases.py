@@ -9,6 +9,8 @@ tests/test_gpu_spec_graph.py runs the engines.  Plain numpy: neither torch nor t
   generate(seed)       random specs over the same vocabulary
   guard(spec, x)       None if every comparison of the case may be bit for bit, else the reason
   categories(spec)     the properties the two lists must keep covering (REQUIRED)
+Further down: the wide vocabulary (concat, the new-form spatial ops, dwconv, tconv: plan, HAND_WIDE, generate_wide) and the
+grouped convolution (gconv: HAND_GROUPED, generate_grouped, REQUIRED_GROUPED).
 
 Exactness by construction: images lie on k / 8, every weight is drawn on its own grid (so the layers' quantizers are
 the identity) and a low-bit activation sits in front of every later contraction, with only max-pools, flattens, zero
@@ -21,6 +23,7 @@ from oracle import qnn_oracle as O
 
 import conv_dilation_cases as D
 import depthwise_cases as DW
+import gconv_cases as GC
 import maxrelu_cases as M
 import pool_cases as P
 import qrelu_cases as Q
@@ -90,20 +93,23 @@ def spatial_desc(op):
 
 
 def dw_dilation(op):
-    """A dwconv op carries its dilation as `dilation`."""
+    """A dwconv op and a gconv op carry their dilation as `dilation`."""
     return P.pair(op.get("dilation", (1, 1)))
 
 
 def _stride(op):
     sh, sw = op.get("strides", (1, 1))
-    assert sh == sw, "dwconv / tconv take one stride for both axes"
+    assert sh == sw, "dwconv / tconv / gconv take one stride for both axes"
     return int(sh)
 
 
-def _depthwise_or_transposed(op, src):
-    """dwconv / tconv: the integer sum (depthwise_cases.dw_sum / tconv_cases.tconv_sum) on the exact integer codes of
-    input and weights, scaled by their power of two, plus the bias in float32.  Operands that are no dyadic numbers
-    (guard refuses such a case) are summed in float64 and rounded once."""
+def _depthwise_transposed_or_grouped(op, src):
+    """dwconv / tconv / gconv: the integer sum (depthwise_cases.dw_sum / tconv_cases.tconv_sum / gconv_cases.gconv_sum) on
+    the exact integer codes of input and weights, scaled by their power of two, plus the bias in float32.  Operands that
+    are no dyadic numbers (guard refuses such a case) are summed in float64 and rounded once.  weights(op) applies the
+    quantizer to the whole kernel as the spec holds it; for a gconv that is Keras' grouped kernel (kh, kw, Cin / groups,
+    Cout), so the ternary cutoff 0.7 mean|w| is taken over that whole kernel and never over a block-diagonal expansion:
+    what the entry promises (include/qnn_abi_gconv.h)."""
     w = weights(op)
     try:
         (xc, a), (wc, b) = _codes(src, "input"), _codes(w, "weights")
@@ -111,6 +117,7 @@ def _depthwise_or_transposed(op, src):
     except ValueError:
         same = op.get("padding", "same") == "same"
         v = (DW.dw_sum(src, w, _stride(op), same, dw_dilation(op), np.float64) if op["op"] == "dwconv" else
+             GC.gconv_sum(src, w, int(op["groups"]), _stride(op), same, dw_dilation(op), np.float64) if op["op"] == "gconv" else
              TC.tconv_sum(src, w, _stride(op), same, np.float64)).astype(F32)
     if op.get("bias") is not None:
         v = (v + np.asarray(op["bias"], dtype=F32)).astype(F32)
@@ -157,8 +164,8 @@ def reference(spec, x, return_all=False):
             elif spatial_desc(op) is not None:
                 import spatial_cases                         # (it imports this module)
                 y = spatial_cases.spatial_array(src, spatial_desc(op))
-            elif kind in ("dwconv", "tconv"):
-                y = _depthwise_or_transposed(op, src)
+            elif kind in ("dwconv", "tconv", "gconv"):
+                y = _depthwise_transposed_or_grouped(op, src)
             else:
                 one = _undilated(op) if kind == "conv" and dilation(op) != (1, 1) else dict(op)
                 e = dict(env)
@@ -191,6 +198,8 @@ def _contract(x, w, op):
         return DW.dw_sum(x, w, _stride(op), op.get("padding", "same") == "same", dw_dilation(op))
     if op["op"] == "tconv":
         return TC.tconv_sum(x, w, _stride(op), op.get("padding", "same") == "same")
+    if op["op"] == "gconv":
+        return GC.gconv_sum(x, w, int(op["groups"]), _stride(op), op.get("padding", "same") == "same", dw_dilation(op))
     dh, dw = dilation(op)
     return O.int_conv2d(x, D.stuff(w, dh, dw), tuple(op.get("strides", (1, 1))), op.get("padding", "same"))
 
@@ -203,7 +212,7 @@ def guard(spec, x):
     env = reference(spec, x, return_all=True)
     for i, (op, ss) in enumerate(zip(spec, sources(spec))):
         src = env[ss[0]]
-        if op["op"] in ("conv", "dense", "dwconv", "tconv"):
+        if op["op"] in ("conv", "dense", "dwconv", "tconv", "gconv"):
             try:
                 xc, a = _codes(src, "input of op %d" % i)
                 wc, b = _codes(weights(op), "weights of op %d" % i)
@@ -218,6 +227,10 @@ def guard(spec, x):
                 kh, kw, _, cin = wc.shape
                 if TC.int32_refused(kh, kw, _stride(op), cin, a + 1, b):
                     return "op %d: the transposed convolution's int32 bound" % i
+            if op["op"] == "gconv":
+                kh, kw, cg, _ = wc.shape
+                if GC.int32_refused(kh, kw, cg, a + 1, b):
+                    return "op %d: the grouped convolution's int32 bound" % i
         elif op["op"] == "act" and op["fn"] == "ternary_tanh":
             t = np.clip(src, F32(-1), F32(1))
             mean = F32(np.mean(np.abs(t), dtype=np.float64))
@@ -422,6 +435,21 @@ class Net:
             op["nb"] = nb
         ho, wo = TC.out_pad(h, kh, s, pad == "same")[0], TC.out_pad(w, kw, s, pad == "same")[0]
         self.fan = -(-kh // s) * -(-kw // s) * cin * _WVAR[kind]
+        return self._put(op, src, (ho, wo, cout), dst)
+
+    def gconv(self, cout, kind="quantized", nb=4, groups=1, k=3, s=1, dil=1, pad="same", bias=False, src=None, dst=None):
+        """Keras' Conv2D(groups=g) as the importer emits it: kernel (kh, kw, Cin / groups, Cout)."""
+        h, w, cin = self.shape[self.cur if src is None else src]
+        (kh, kw), (dh, dw) = P.pair(k), P.pair(dil)
+        assert cin % groups == 0 and cout % groups == 0, (cin, cout, groups)
+        op = {"op": "gconv", "kind": kind, "kernel": _kernel(self.rng, kind, nb, (kh, kw, cin // groups, cout)),
+              "bias": self._bias(cout, bias), "groups": groups, "strides": (s, s), "padding": pad, "dilation": (dh, dw),
+              "H": 1.0}
+        if kind == "quantized":
+            op["nb"] = nb
+        ho, wo = GC.out_pad(h, kh, s, pad == "same", dh)[0], GC.out_pad(w, kw, s, pad == "same", dw)[0]
+        assert ho > 0 and wo > 0
+        self.fan = kh * kw * (cin // groups) * _WVAR[kind]
         return self._put(op, src, (ho, wo, cout), dst)
 
     def dyadic_bn(self, src=None, dst=None):
@@ -1093,7 +1121,7 @@ def _join(bits, wstore):
 
 def _grid_store(op):
     """The store a contraction reads ternary codes {-1, 0, 1} at (engine.GraphModel._grid_store)."""
-    ws = _wstore(op) if op["op"] in ("conv", "dense", "dwconv", "tconv") else None
+    ws = _wstore(op) if op["op"] in ("conv", "dense", "dwconv", "tconv", "gconv") else None
     if ws is None:
         return None
     return 2 if op["kind"] == "ternary" else max(4, ws if ws != 1 else 4)
@@ -1234,7 +1262,17 @@ def plan(spec, image=(8, 8, 3)):
             suffix = "_mfma" if mfma else "_plain"
             if mfma:
                 dec.add("tconv matrix-pipe form")
-        log.append("%s_%s%s" % ("depthwise" if kind == "dwconv" else "tconv", _STORE_NAME[xs], suffix))
+        elif kind == "gconv" and xs in (4, 8):
+            cg, cout = op["kernel"].shape[2:]
+            route = dict(window=(kh, kw), store=xs, out_store=ostore, Cin=cg * int(op["groups"]), Cout=cout,
+                         groups=int(op["groups"]), misalign=False)
+            mfma = GC.takes_mfma(route)
+            suffix = "_mfma" if mfma else "_plain"
+            if mfma:
+                dec.add("gconv matrix-pipe form")
+            elif GC.takes_mfma(dict(route, out_store=xs)):   # the shape is the matrix pipe's, the epilogue leaves another store
+                dec.add("gconv plain form: other out store")
+        log.append("%s_%s%s" % ({"dwconv": "depthwise", "tconv": "tconv", "gconv": "gconv"}[kind], _STORE_NAME[xs], suffix))
         y = _F(4) if out is None else _P(ostore, out[1], 4, False, out)
         return y, last
 
@@ -1245,7 +1283,8 @@ def plan(spec, image=(8, 8, 3)):
         src = env[srcs[i][0]]
         pi = prod.get(srcs[i][0])
         if pi is not None and spec[pi]["op"] == "act" and spec[pi]["fn"] in M.FNS:
-            for tag, hit in (("dwconv", kind == "dwconv"), ("tconv", kind == "tconv"), ("spatial", spatial_desc(op) is not None)):
+            for tag, hit in (("dwconv", kind == "dwconv"), ("tconv", kind == "tconv"), ("gconv", kind == "gconv"),
+                             ("spatial", spatial_desc(op) is not None)):
                 if hit:
                     dec.add("max activation in front of %s" % tag)
         if kind == "concat" and any(prod.get(s) is not None and spec[prod[s]]["op"] == "act" and spec[prod[s]]["fn"] in M.FNS
@@ -1262,11 +1301,11 @@ def plan(spec, image=(8, 8, 3)):
             if src["k"] == "P":
                 read_packed(i, op, src, 4 if kind == "conv" else 2)
             y = _F(4 if kind == "conv" else 2)
-        elif kind in ("dwconv", "tconv"):
+        elif kind in ("dwconv", "tconv", "gconv"):
             y, last = depth(i, op, src)
             skip.update(range(i + 1, last + 1))
             name = names[last]
-            if kind == "tconv" and y["k"] == "P":
+            if kind in ("tconv", "gconv") and y["k"] == "P":
                 upsampled.add(name)
         elif kind == "concat":
             ins = [env[s] for s in srcs[i]]
@@ -1351,7 +1390,7 @@ def _tail_at(spec, names, cons, ap):
 
 
 def _epilogue_of(spec, names, cons, ai):
-    """True if activation op `ai` goes into the epilogue of a dwconv / tconv (alone behind it or behind its BN)."""
+    """True if activation op `ai` goes into the epilogue of a dwconv / tconv / gconv (alone behind it or behind its BN)."""
     srcs = sources(spec)
     prod = {n: i for i, n in enumerate(names)}
     p = prod.get(srcs[ai][0])
@@ -1359,8 +1398,8 @@ def _epilogue_of(spec, names, cons, ai):
         return False
     if spec[p]["op"] == "bn":
         q = prod.get(srcs[p][0])
-        return q == p - 1 and spec[q]["op"] in ("dwconv", "tconv") and cons.get(names[q], []) == [p]
-    return spec[p]["op"] in ("dwconv", "tconv")
+        return q == p - 1 and spec[q]["op"] in ("dwconv", "tconv", "gconv") and cons.get(names[q], []) == [p]
+    return spec[p]["op"] in ("dwconv", "tconv", "gconv")
 
 
 # ---- hand-written specs, one per planner decision ---------------------------------------------------------------------------
@@ -1882,3 +1921,506 @@ REQUIRED_WIDE = (
      "tconv matrix-pipe form", "depthwise 16-bit-lane form", "LayerModel chain"} |
     {"max activation in front of %s" % k for k in ("dwconv", "tconv", "spatial", "concat")})
 REQUIRED = REQUIRED | REQUIRED_WIDE
+
+
+# ============================================================================================================================
+# The grouped convolution: {"op": "gconv"} (Net.gconv) in the reference, the guard and plan() above.
+#
+#   HAND_GROUPED              one spec per planner decision about a gconv, the pivotal ones with the log written out
+#   generate_grouped(seed)    random ResNeXt / ShuffleNet-style networks
+#   categories_grouped(spec)  categories_wide plus the gconv launch names; REQUIRED_GROUPED is what the two lists must cover
+# ============================================================================================================================
+HAND_GROUPED = []
+
+
+def _grouped(name, net, log=None, layer_model=None, same_scaled_log=False):
+    """As _wide.  same_scaled_log: GraphModel(scaled_codes=True) must log what GraphModel() logs although the spec holds a
+    batch-maximum activation."""
+    assert name not in [c["name"] for c in HAND_GROUPED], name
+    HAND_GROUPED.append(dict(name=name, spec=net.spec, x=net.images(), image=net.shape["input"], log=log,
+                             layer_model=layer_model, same_scaled_log=same_scaled_log))
+
+
+def _gstem(name, c=8, w="q4", a="q4", hw=(8, 8)):
+    net = Net(_seed("grouped_" + name), hw=hw)
+    net.clipped(c, w, a, dst="a0")
+    return net
+
+
+def _gclip(net, cout, w="q4", a="q4", groups=2, bn=True, dst=None, **kw):
+    """gconv -> [bn] -> clip; `a`: a key of ACT_OF or (fn, bits)."""
+    net.gconv(cout, *WEIGHT_OF[w], groups=groups, bias=kw.pop("bias", True), **kw)
+    if bn:
+        net.bn()
+    return net.act(*(ACT_OF[a] if isinstance(a, str) else a), dst=dst)
+
+
+_SNAME = {"q4": "i4", "q8": "i8", "bin": "bin", "tern": "t2"}
+
+# -- the ResNeXt bottleneck 1x1 -> gconv -> 1x1 with an identity add, on the matrix pipe: Fg < 16 with t > 1 (Cg = Fg = 4,
+#    g = 4) and Fg = 16 (g = 2 of 32), int4 and int8
+for _a, _c, _g in (("q4", 16, 4), ("q8", 32, 2), ("q4", 32, 2), ("q8", 16, 4)):
+    for _add in (True, False):
+        _n = "bottleneck_%s_c%d_g%d%s" % (_a, _c, _g, "" if _add else "_no_add")
+        if not _add and (_a, _c) not in (("q4", 16), ("q8", 32)):
+            continue
+        net = _gstem(_n, _c, _a, _a)
+        net.clipped(_c, _a, _a, k=1)
+        _gclip(net, _c, _a, _a, _g)
+        net.conv(_c, *WEIGHT_OF[_a], k=1)
+        main = net.bn()
+        if _add:
+            net.add("a0", main)
+            net.scale(0.5)
+        net.act(*ACT_OF[_a])
+        _head(net, _a)
+        _grouped(_n, net, log=["pack", "gconv_%s_mfma" % _SNAME[_a]])
+
+# -- the plain form by shape: 12 -> 12 in three groups, and group edges inside input words (Cg of 5, 3, 33)
+for _n, _w, _cin, _cout, _g, _k in (("12_g3", "q4", 12, 12, 3, "gconv_i4_plain"), ("i4_cg5", "q4", 10, 6, 2, "gconv_i4_plain"),
+                                    ("i8_cg3", "q8", 12, 8, 4, "gconv_i8_plain"), ("bin_cg5", "bin", 10, 6, 2, "gconv_bin"),
+                                    ("bin_cg33", "bin", 66, 10, 2, "gconv_bin"), ("t2_cg33", "tern", 66, 10, 2, "gconv_t2")):
+    _a = _w
+    net = _gstem("plain_" + _n, _cin, _w, _a, hw=(9, 7))
+    _gclip(net, _cout, _w, _a, _g)
+    net.clipped(8, _w, _a)
+    _head(net, _w)
+    _grouped("plain_by_shape_" + _n, net, log=["pack", _k])
+
+# -- the plain form by epilogue on a matrix-pipe shape (16 -> 16, g = 4): q4 codes in, an 8-bit clip, no clip, a 1-bit clip
+for _n, _a in (("q8_clip", "q8"), ("binary_clip", "bin")):
+    net = _gstem("epi_" + _n, 16)
+    _gclip(net, 16, "q4", _a, 4)
+    net.clipped(8, "q8" if _a == "q8" else "bin", "q4")
+    _head(net)
+    _grouped("plain_by_epilogue_" + _n, net, log=["pack", "gconv_i4_plain"])
+net = _gstem("epi_none", 16)
+net.gconv(16, groups=4, bias=True)
+b = net.bn()
+net.add("a0", b)
+net.scale(0.5)
+net.act()
+_head(net)
+_grouped("plain_by_epilogue_no_clip", net, log=["pack", "gconv_i4_plain"])
+
+# -- every clip function at 2, 3, 4 and 8 bits in the epilogue (and binary_tanh), read by a conv of the matching store
+for _fn in ("quantized_tanh", "quantized_relu", "quantized_leakyrelu"):
+    for _nb in (2, 3, 4, 8):
+        _n = "epilogue_%s_%d" % (_fn, _nb)
+        net = _gstem(_n, 8, hw=(9, 7) if _nb in (3, 8) else (8, 8))
+        _gclip(net, 8, "q4", (_fn, _nb), 2, bn=_nb != 3)
+        net.clipped(8, "q8" if _nb == 8 else "q4", "q4")
+        _head(net)
+        _grouped(_n, net)
+net = _gstem("epilogue_bin", 8, "bin", "bin")
+_gclip(net, 8, "bin", "bin", 4)
+net.clipped(8, "bin", "bin")
+_head(net, "bin")
+_grouped("epilogue_binary_tanh", net, log=["pack", "gconv_bin"])
+
+# -- BN absent, BN read twice, a second reader beside the BN, the clip read twice, the packed output as the last tensor
+net = _gstem("no_bn")
+_gclip(net, 8, bn=False)
+net.clipped(8)
+_head(net)
+_grouped("gconv_without_bn", net, log=["pack", "gconv_i4_plain"])
+net = _gstem("bn_twice")
+net.gconv(8, groups=2, bias=True)
+b = net.bn(dst="b")
+a1 = net.act(src=b, dst="a1")
+net.clipped(8, src=a1, dst="a2")
+net.act("quantized_tanh", 8, src=b, dst="a3")
+net.concat(["a2", "a3"])
+net.clipped(8)
+_head(net)
+_grouped("gconv_bn_read_twice", net, log=["pack", "gconv_i4_plain", "concat_f32"])
+net = _gstem("beside_bn")
+y = net.gconv(8, groups=2, bias=True, dst="y")
+net.bn()
+a1 = net.act(dst="a1")
+net.act("quantized_relu", 4, src=y, dst="a2")
+net.clipped(8, src=a1, dst="c1")
+net.clipped(8, src="a2", dst="c2")
+net.add("c1", "c2")
+net.act()
+_head(net)
+_grouped("gconv_second_reader_beside_bn", net, log=["pack", "gconv_i4_plain"])
+net = _gstem("clip_twice")
+y = _gclip(net, 8)
+net.pool("maxpool", (2, 2), (2, 2), "valid", src=y, dst="p")
+net.clipped(8, s=2, src=y, dst="c")
+net.concat(["p", "c"])
+net.clipped(8)
+_head(net)
+_grouped("gconv_clip_read_twice", net)
+net = _gstem("last")
+_gclip(net, 8, a="leaky4")
+_grouped("gconv_clip_is_last", net, log=["pack", "gconv_i4_plain"])
+
+# -- who reads the packed output: (conv: above) dense behind flatten, dwconv, tconv, another gconv, add, the new-form pools,
+#    crop / upsample / pair zeropad, concat
+net = _gstem("r_flat", hw=(4, 4))
+_gclip(net, 8)
+_head(net)
+_grouped("gconv_then_flatten_dense", net)
+net = _gstem("r_dw")
+_gclip(net, 8)
+net.dwconv(1, bias=True)
+net.bn()
+net.act()
+net.clipped(8, k=1)
+_head(net)
+_grouped("gconv_then_dwconv", net, log=["pack", "gconv_i4_plain", "depthwise_i4"])
+net = _gstem("r_tc", hw=(4, 4))
+_gclip(net, 8)
+net.tconv(8, k=2, s=2, bias=True)
+net.bn()
+net.act()
+net.clipped(8)
+_head(net, flat=False)
+_grouped("gconv_then_tconv", net, log=["pack", "gconv_i4_plain", "tconv_i4_plain", "pool_max_i4"])
+net = _gstem("r_gc", 16)
+_gclip(net, 16, groups=4)
+_gclip(net, 12, groups=2)
+net.clipped(8)
+_head(net)
+_grouped("gconv_then_gconv", net, log=["pack", "gconv_i4_mfma", "gconv_i4_plain"])
+net = _gstem("r_add")
+y = _gclip(net, 8)
+net.add("a0", y)
+net.scale(0.5)
+net.act()
+_head(net)
+_grouped("gconv_then_add", net)
+net = _gstem("r_maxpool", hw=(9, 7))
+_gclip(net, 8)
+net.pool("maxpool", (3, 3), (2, 2), "same")
+net.clipped(8)
+_head(net)
+_grouped("gconv_then_new_maxpool", net, log=["pack", "gconv_i4_plain", "pool_max_i4"])
+net = _gstem("r_avgpool")
+_gclip(net, 8)
+net.pool("avgpool", (2, 2), (2, 2), "valid")
+_head(net)
+_grouped("gconv_then_new_avgpool", net, log=["pack", "gconv_i4_plain", "pool_avg_i4"])
+net = _gstem("r_gpool", a="q8", w="q8")
+_gclip(net, 8, "q8", "q8")
+_head(net, "q8", flat=False)
+_grouped("gconv_then_global_maxpool", net, log=["pack", "gconv_i8_plain", "pool_max_i8"])
+net = _gstem("r_spatial", hw=(9, 7))
+_gclip(net, 8, a="relu4")
+net.crop(((0, 1), (1, 0)))
+net.upsample((1, 2))
+net.clipped(8)
+_head(net)
+_grouped("gconv_then_crop_upsample", net, log=["pack", "gconv_i4_plain", "spatial_i4", "spatial_i4"])
+net = _gstem("r_up")
+_gclip(net, 8, a="q2", w="q2")
+net.upsample((2, 1))
+net.clipped(8, s=2)
+_head(net)
+_grouped("gconv_then_upsample", net)
+net = _gstem("r_pad", hw=(9, 7))
+_gclip(net, 8, a="q3")
+net.zeropad2(((1, 0), (0, 2)))
+net.clipped(8, pad="valid")
+_head(net)
+_grouped("gconv_then_pair_zeropad", net, log=["pack", "gconv_i4_plain", "spatial_i4"])
+
+# -- the join with the skip (the `upsampled` set of forward: the concat packs the skip to meet the gconv's codes): the skip
+#    first and second, int4, int8 and 1-bit codes
+for _a, _c, _g in (("q4", 16, 4), ("q8", 16, 4), ("bin", 12, 3), ("q4", 12, 3)):
+    for _first in (False, True):
+        _n = "join_%s_c%d_skip_%s" % (_a, _c, "first" if _first else "second")
+        net = _gstem(_n, _c, _a, _a, hw=(9, 7) if _first else (8, 8))
+        _gclip(net, _c, _a, _a, _g, dst="b")
+        net.concat(["a0", "b"] if _first else ["b", "a0"])
+        net.clipped(16, _a, _a, k=1)
+        _head(net, _a)
+        _s = _SNAME[_a]
+        _k = "gconv_" + (_s if _a == "bin" else _s + ("_mfma" if _c == 16 else "_plain"))
+        _grouped(_n, net, log=["pack", _k, "concat_" + _s])
+# a skip of another width: the codes meet a clip they cannot be joined with, the join runs in float32
+net = _gstem("join_width", 16)
+_gclip(net, 16, "q4", "q2", 4, dst="b")
+net.concat(["b", "a0"])
+net.clipped(8)
+_head(net)
+_grouped("join_skip_of_another_width", net, log=["pack", "gconv_i4_mfma", "concat_f32"])
+# a ternary gconv on grid codes; its ternary activation travels as planes and meets the ternary skip as planes
+net = _gstem("join_tern", 8, "tern", "tern")
+net.gconv(8, "ternary", 1, groups=2, bias=True, src="a0")
+net.bn()
+net.act("ternary_tanh", dst="t")
+net.upsample((1, 1), dst="u")
+net.concat(["u", "a0"], dst="cat")
+net.gconv(8, "ternary", 1, groups=4, k=(2, 3))
+net.bn()
+net.act("ternary_tanh")
+_head(net, "tern")
+_grouped("join_ternary_planes", net, log=["pack", "gconv_t2", "spatial_t2", "concat_t2", "gconv_t2"])
+
+# -- weight kinds on q4 codes, the re-clip branch (a packed producer of another store), grid codes read by binary weights
+for _w in ("bin", "tern", "q2", "q3", "q8"):
+    net = _gstem("w_" + _w, 12, hw=(9, 7))
+    _gclip(net, 8, _w, "q4", 4)
+    net.clipped(8)
+    _head(net)
+    _grouped("weights_%s_on_q4_codes" % _w, net, log=["pack", "gconv_i8_plain" if _w == "q8" else "gconv_i4_plain"])
+net = _gstem("reclip", 8)
+_gclip(net, 8, "q4", "bin", 2)                                        # 1-bit codes ...
+_gclip(net, 8, "q8", "q8", 2)                                         # ... read by 8-bit weights: another store
+_head(net, "q8")
+_grouped("gconv_other_store_wanted", net, log=["pack", "gconv_i4_plain", "pack", "gconv_i8_plain"])
+net = _gstem("grid_bin", 10, "tern", "tern")
+_gclip(net, 6, "bin", "bin", 2)
+net.clipped(8, "bin", "bin")
+_head(net, "bin")
+_grouped("binary_gconv_on_grid_codes", net, log=["pack", "gconv_i4_plain"])
+# float weights: behind a clip, and behind a packed tensor (read as float32 without an `unpack` launch)
+net = _gstem("float_clip")
+net.gconv(8, "float", 0, groups=2, s=2, pad="valid", bias="dyadic")
+net.act()
+net.clipped(8)
+_head(net)
+_grouped("float_gconv_behind_a_clip", net, log=["gconv_f32"])
+net = _gstem("float_packed")
+net.pool("maxpool", (2, 2), (2, 2), "valid")
+net.gconv(8, "float", 0, groups=4, bias="dyadic")
+net.bn()
+net.act()
+_head(net)
+_grouped("float_gconv_behind_packed_codes", net, log=["pool_max_i4", "gconv_f32"])
+
+# -- geometry on the 9 x 7 maps: stride 2 ('same' and 'valid'), dilation 2, windows 1 x 1, 5 x 5, 2 x 3
+for _n, _kw in (("s2_same", dict(s=2)), ("s2_valid", dict(s=2, pad="valid")), ("dil2", dict(dil=2)), ("k1", dict(k=1)),
+                ("k5", dict(k=5)), ("k2x3", dict(k=(2, 3), pad="valid")), ("k5_dil2_mfma", dict(k=5, dil=(1, 2)))):
+    _mf = _n.endswith("mfma")
+    net = _gstem("geom_" + _n, 16 if _mf else 12, hw=(9, 7))
+    _gclip(net, 16 if _mf else 12, groups=4 if _mf else 3, **_kw)
+    net.clipped(8)
+    _head(net)
+    _grouped("geometry_" + _n, net, log=["pack", "gconv_i4_mfma" if _mf else "gconv_i4_plain"])
+
+# -- a gconv as the first layer, on the images: g = 3 and g = 1 with low-bit weights, float weights
+for _n, _w, _g, _c in (("g3_q4", "q4", 3, 6), ("g1_bin", "bin", 1, 8), ("g3_tern", "tern", 3, 12)):
+    net = Net(_seed("first_" + _n), hw=(8, 8))
+    _gclip(net, _c, _w, "q4", _g)
+    net.clipped(8)
+    _head(net)
+    _grouped("first_layer_" + _n, net, log=["gconv_f32"])
+net = Net(_seed("first_float"), hw=(9, 7))
+net.gconv(6, "float", 0, groups=3, bias="dyadic")
+net.act()
+net.clipped(8)
+_head(net)
+_grouped("first_layer_float", net, log=["gconv_f32"])
+
+# -- a batch-maximum activation in front: read as float32, with and without scaled codes
+net = Net(_seed("grouped_max"), hw=(8, 8))
+net.conv(8, bias=True)
+net.act("quantized_maxrelu", 4)
+_gclip(net, 8)
+net.clipped(8)
+_head(net)
+_grouped("gconv_behind_max_activation", net, log=["gconv_f32"], same_scaled_log=True)
+
+# -- groups = 1 and groups = Cin (test_spec_graph_cpu.py: the reference equals that of the conv / dwconv twin)
+for _n, _w, _a in (("q4", "q4", "q4"), ("tern", "tern", "tern"), ("bin", "bin", "bin")):
+    net = _gstem("g1_" + _n, 8, _w, _a, hw=(9, 7))
+    _gclip(net, 12, _w, _a, 1, s=2)
+    net.clipped(8, _w, _a)
+    _head(net, _w)
+    _grouped("groups_1_" + _n, net)
+    net = _gstem("gcin_" + _n, 8, _w, _a, hw=(9, 7))
+    _gclip(net, 16, _w, _a, 8, dil=2)
+    net.clipped(8, _w, _a)
+    _head(net, _w)
+    _grouped("groups_cin_" + _n, net)
+GROUPS_ONE = tuple("groups_1_" + n for n in ("q4", "tern", "bin"))
+GROUPS_CIN = tuple("groups_cin_" + n for n in ("q4", "tern", "bin"))
+
+CAPTURED_GROUPED = ("bottleneck_q4_c16_g4", "join_q4_c16_skip_second")
+
+
+def conv_twin(spec):
+    """The spec with every gconv of groups = 1 written as a conv."""
+    out = []
+    for op in spec:
+        if op["op"] == "gconv":
+            assert op["groups"] == 1
+            op = {k: v for k, v in op.items() if k not in ("groups", "dilation", "H")}
+            op.update(op="conv", dilation_rate=dw_dilation(spec[len(out)]))
+        out.append(op)
+    return out
+
+
+def dwconv_twin(spec):
+    """The spec with every gconv of groups = Cin written as a dwconv: M = Fg, kernel (kh, kw, 1, C * M) -> (kh, kw, C, M)."""
+    out = []
+    for op in spec:
+        if op["op"] == "gconv":
+            kh, kw, cg, cout = op["kernel"].shape
+            assert cg == 1 and cout % op["groups"] == 0
+            M = cout // op["groups"]
+            op = {k: v for k, v in op.items() if k != "groups"}
+            op.update(op="dwconv", kernel=op["kernel"].reshape(kh, kw, cout // M, M), depth_multiplier=M)
+        out.append(op)
+    return out
+
+
+# ---- the third generator -----------------------------------------------------------------------------------------------------
+SEEDS_GROUPED = range(32)
+GROUPED_BASE = 110000
+WKEYS_WIDE = ("bin", "tern", "q2", "q3", "q4", "q4", "q8")                # generate_wide's key lists
+AKEYS_WIDE = ("bin", "q2", "q3", "q4", "q4", "q8", "relu4", "relu8", "leaky4", "leaky2", "tern")
+
+
+def _divisors(cin, cout):
+    return [d for d in range(1, cin + 1) if cin % d == 0 and cout % d == 0]
+
+
+def generate_grouped(seed):
+    """(spec, images, image shape) of a random network around grouped convolutions: a stem, 2 to 4 blocks out of {ResNeXt
+    bottleneck with or without the add, ShuffleNet-style branch concatenated with its skip, grouped stem, gconv -> new-form
+    pool, inception branches with a gconv beside a dwconv, plain group} and a head of generate_wide; `groups` is drawn from
+    the common divisors of the two channel counts, weights and activations per op.  Seeds 0 mod 4 hold a matrix-pipe
+    gconv (16 or 32 channels, q4 or q8 throughout), seeds 1 mod 4 a plain-form gconv on packed input."""
+    rng = np.random.default_rng(GROUPED_BASE + seed)
+    force = {0: "mfma", 1: "plain"}.get(seed % 4)
+    net = Net(GROUPED_BASE + 10000 + seed, hw=(8, 8) if rng.random() < 0.5 else (9, 7))
+    pick = lambda seq: seq[int(rng.integers(len(seq)))]      # noqa: E731
+    use_max = force is None and rng.random() < 0.25
+    through = pick(("q4", "q8")) if force == "mfma" else None
+    left = [MAX_CONTRACTIONS_WIDE - 1]                       # (the head's dense is one)
+    small = tuple(c for c in CHANNELS_WIDE if c <= 33)
+    last_a = [None]
+
+    def act(a=None):
+        if a is None and use_max and rng.random() < 0.4:
+            last_a[0] = None
+            return net.act(pick(("quantized_maxrelu", "quantized_leakymaxrelu")), pick((3, 4)))
+        last_a[0] = a or through or pick(AKEYS_WIDE)
+        return net.act(*ACT_OF[last_a[0]])
+
+    def clipped(cout, w=None, a=None, **kw):
+        left[0] -= 1
+        net.conv(cout, *WEIGHT_OF[w or through or pick(WKEYS_WIDE)], bias=bool(rng.random() < 0.5), **kw)
+        if rng.random() < 0.8:
+            net.bn()
+        return act(a)
+
+    def grouped(cout, src=None, g=None, w=None, a=None, clip=None, free=False):
+        """gconv -> [bn] -> [clip]; free: window, stride, dilation and padding are drawn too."""
+        left[0] -= 1
+        h, w_, cin = net.shape[net.cur if src is None else src]
+        k, s, dil, pad = 3, 1, 1, "same"
+        if free:
+            k, s, pad = pick((3, 3, 1, (2, 3), 5)), pick((1, 1, 2)), pick(("same", "same", "valid"))
+            dil = pick((1, 1, 2)) if s == 1 and k != 1 else 1
+            if pad == "valid" and min(h, w_) < D.effective(max(P.pair(k)), dil):
+                pad = "same"
+        clip = (a is not None or rng.random() < 0.85) if clip is None else clip
+        net.gconv(cout, *WEIGHT_OF[w or through or pick(WKEYS_WIDE)], groups=pick(_divisors(cin, cout)) if g is None else g, k=k,
+                  s=s, dil=dil, pad=pad, bias=(bool(rng.random() < 0.5) if clip else "dyadic"), src=src)
+        if rng.random() < 0.7:
+            net.bn() if clip else net.dyadic_bn()
+        return act(a) if clip else net.cur
+
+    def bottleneck(cur, mfma=False):
+        c = net.shape[cur][2]
+        mid = pick((16, 32)) if mfma else pick((8, 12, 16, 24, 32))
+        clipped(mid, k=1, src=cur)
+        g = pick([d for d in _divisors(mid, mid) if GC.plan(3, 3, mid, mid, d) is not None]) if mfma else None
+        grouped(mid, g=g, a=through, clip=True if mfma else None)
+        left[0] -= 1
+        net.conv(c, *WEIGHT_OF[through or pick(WKEYS_WIDE)], k=1)
+        main = net.bn()
+        if rng.random() < 0.6:
+            net.add(cur, main) if rng.random() < 0.5 else net.add(main, cur)
+            net.scale(0.5)
+        return act()
+
+    def shuffle(cur):
+        c, skip_a = net.shape[cur][2], last_a[0]
+        src = cur
+        if left[0] >= 4 and rng.random() < 0.4:
+            src = clipped(pick((8, 12, 16)), k=1, src=cur)
+        b = grouped(pick((8, 12, 16, c)), src=src, a=skip_a if rng.random() < 0.6 else None, clip=True)
+        net.concat([b, cur] if rng.random() < 0.5 else [cur, b])
+        return clipped(pick(small), k=1)
+
+    def inception(cur):
+        outs = [grouped(pick((8, 12, 16)), src=cur, clip=True)]
+        left[0] -= 1
+        net.dwconv(1, *WEIGHT_OF[pick(WKEYS_WIDE)], bias=bool(rng.random() < 0.5), src=cur)
+        net.bn()
+        outs.append(act())
+        if rng.random() < 0.5:
+            outs.append(net.pool("maxpool", (3, 3), (1, 1), "same", src=cur))
+        net.concat(outs)
+        return clipped(pick(small), k=1)
+
+    if force == "plain":
+        cur = clipped(pick((12, 16)), "q4", "q4")
+    else:
+        cur = clipped(pick((16, 32)) if force else pick((8, 12, 16)), through, through)
+    blocks = ([force] if force else []) + [pick(("bottleneck", "bottleneck", "shuffle", "shuffle", "gstem", "gpool", "inception",
+                                                 "group")) for _ in range(int(rng.integers(2, 5)))]
+    for block in blocks:
+        h, w_, c = net.shape[cur]
+        if block == "mfma":
+            cur = bottleneck(cur, mfma=True)
+        elif block == "plain":                               # by shape (12 in 3 groups) or by epilogue (16 in 4, an 8-bit clip)
+            cur = grouped(c, src=cur, g=3 if c == 12 else 4, w="q4", a="q4" if c == 12 else "q8")
+        elif block == "bottleneck" and left[0] >= 3:
+            cur = bottleneck(cur)
+        elif block == "shuffle" and left[0] >= 2:
+            cur = shuffle(cur)
+        elif block == "gpool" and left[0] >= 1 and min(h, w_) >= 4:
+            grouped(pick(small), src=cur, clip=True)
+            cur = net.pool("maxpool", pick(((2, 2), (3, 3), (2, 3))), pick(((2, 2), (1, 1))), pick(("same", "valid")))
+        elif block == "inception" and left[0] >= 3:
+            cur = inception(cur)
+        elif block == "group" and left[0] >= 1:
+            cur = clipped(pick(small))
+        elif left[0] >= 1:                                   # the grouped stem (and whatever found no room)
+            cur = grouped(pick(small), src=cur, free=True)
+    h, w_, c = net.shape[cur]
+    head = pick(("flat", "tail", "global"))
+    if head == "flat":
+        net.flatten()
+    elif head == "tail":
+        net.pool("avgpool", 8 if min(h, w_) >= 8 else 4 if min(h, w_) >= 4 else 2 if min(h, w_) >= 2 else 1)
+        net.flatten()
+    else:
+        net.pool("globalmaxpool")
+    net.dense(10, *WEIGHT_OF[through or pick(WKEYS_WIDE)], bias=bool(head != "tail" and rng.random() < 0.5))
+    if rng.random() < 0.25:
+        net.softmax()
+    assert left[0] >= 0, left
+    x = (rng.integers(0, 9, (N, net.hw[0], net.hw[1], 3)) / 8.0).astype(F32)
+    return net.spec, x, net.shape["input"]
+
+
+# ---- what the grouped lists must cover -------------------------------------------------------------------------------------
+GCONV_LAUNCHES = ("gconv_f32", "gconv_bin", "gconv_t2", "gconv_i4_mfma", "gconv_i4_plain", "gconv_i8_mfma", "gconv_i8_plain")
+GCONV_READERS = ("conv", "flatten", "dwconv", "tconv", "gconv", "add", "maxpool (new form)", "avgpool (new form)",
+                 "globalmaxpool", "crop", "upsample", "zeropad", "concat")
+
+
+def categories_grouped(spec, image=(8, 8, 3)):
+    c = categories_wide(spec, image)
+    c |= {"launch %s" % k for k in plan(spec, image)[1] if k.startswith("gconv_")}
+    if any(op["op"] == "gconv" for op in spec) and not any(op["op"] == "concat" for op in spec) and \
+            not any(op["op"] in ("conv", "dense") and op["kind"] == "float" for op in spec):
+        c.add("LayerModel chain")
+    return c
+
+
+REQUIRED_GROUPED = (
+    {"op gconv", "gconv clip in the epilogue", "BN behind gconv read twice", "a second reader beside the BN behind gconv",
+     "clip behind gconv read twice", "packed gconv output is the last tensor", "gconv matrix-pipe form",
+     "gconv plain form: other out store", "packed producer, other store wanted", "pack_clips join",
+     "concat: codes meet a clip, joined in float32", "max activation in front of gconv", "LayerModel chain"} |
+    {"launch %s" % k for k in GCONV_LAUNCHES} | {"packed gconv output read by %s" % k for k in GCONV_READERS})

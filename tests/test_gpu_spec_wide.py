@@ -18,8 +18,9 @@ import spec_graph_cases as S
 
 pytestmark = pytest.mark.gpu
 SEEN = set()             # every name a GraphModel.kernel_log of this file held (test_zz_every_kernel_family_was_reached)
-POOLED_BEHIND = set()    # pool_max_* names met behind a dwconv / tconv
-LAUNCHERS = ("conv2d", "conv2d_f32in", "dense", "pool2d", "depthwise", "tconv", "spatial2d", "concat", "pack", "unpack")
+POOLED_BEHIND = set()    # pool_max_* names met behind a dwconv / tconv / gconv
+LAUNCHERS = ("conv2d", "conv2d_f32in", "dense", "pool2d", "depthwise", "tconv", "gconv", "spatial2d", "concat", "pack",
+             "unpack")
 WIDE = {c["name"]: c for c in S.HAND_WIDE}
 
 
@@ -74,16 +75,19 @@ def compare(got, want, spec, what):
         np.testing.assert_array_equal(bits(got), bits(want), err_msg=what)
 
 
-def check(spec, x, image, what, hand_log=None, layer_model=None):
+def check(spec, x, image, what, hand_log=None, layer_model=None, same_scaled_log=False):
+    """same_scaled_log: the two logs are equal although the spec holds a batch-maximum activation.  Returns the two logs,
+    one after the other."""
     want, xd = S.reference(spec, x), dev(x)
     has_max = any(op["op"] == "act" and op["fn"] in S.M.FNS for op in spec)
-    has_new = any(op["op"] in ("concat", "crop", "upsample", "dwconv", "tconv") or S.spatial_desc(op) is not None for op in spec)
+    has_new = any(op["op"] in ("concat", "crop", "upsample", "dwconv", "tconv", "gconv") or S.spatial_desc(op) is not None
+                  for op in spec)
     plain, log = graph(spec, xd, False)
     scaled, log_scaled = graph(spec, xd, True)
     compare(plain, want, spec, "%s GraphModel %s" % (what, log))
     compare(scaled, want, spec, "%s GraphModel scaled_codes %s" % (what, log_scaled))
-    if not has_max:
-        assert log == log_scaled, what
+    if not has_max or same_scaled_log:
+        assert log == log_scaled, (what, log, log_scaled)
     SEEN.update(log)
     SEEN.update(log_scaled)
     # the planner's decisions: which launches, in which order, "pack" / "unpack" between them
@@ -91,7 +95,7 @@ def check(spec, x, image, what, hand_log=None, layer_model=None):
     if hand_log is not None:
         assert log == hand_log, (what, log)
     for a, b in zip(log, log[1:]):
-        if a.startswith(("depthwise_", "tconv_")) and b.startswith("pool_max_"):
+        if a.startswith(("depthwise_", "tconv_", "gconv_")) and b.startswith("pool_max_"):
             POOLED_BEHIND.add(b)
     # LayerModel: the same bits where the spec has no concat
     with counting() as n:
@@ -114,7 +118,8 @@ def check(spec, x, image, what, hand_log=None, layer_model=None):
         # (a generated network that drew none of the new ops is one the fused engines take: nets.Model picks them)
         assert isinstance(nets.Model(None, spec).engine, engine.GraphModel), what
     if spec[-1]["op"] == "softmax":          # ... and the logits in front of it, bit for bit
-        check(spec[:-1], x, image, what + " logits")
+        check(spec[:-1], x, image, what + " logits", same_scaled_log=same_scaled_log)
+    return log + log_scaled
 
 
 @pytest.mark.parametrize("name", list(WIDE))

@@ -248,14 +248,16 @@ _FN = {DW.FN_BINARY_TANH: "binary_tanh", DW.FN_QUANTIZED_TANH: "quantized_tanh",
 
 
 def _one_op_spec(c, kernel, bias, bn, which):
-    """The case of depthwise_cases / tconv_cases as a spec: dwconv | tconv [-> bn] [-> act], the BN with eps 0, mean 0 and
-    variance 1, so that bn_constants gives the case's (inv, shift) exactly."""
+    """The case of depthwise_cases / tconv_cases / gconv_cases as a spec: dwconv | tconv | gconv [-> bn] [-> act], the BN
+    with eps 0, mean 0 and variance 1, so that bn_constants gives the case's (inv, shift) exactly."""
     op = {"op": which, "kind": _KIND[c["wkind"]], "kernel": kernel, "bias": bias, "strides": (c["stride"], c["stride"]),
           "padding": "same" if c["same"] else "valid", "H": 1.0}
     if c["wkind"] == DW.W_QUANT:
         op["nb"] = c["wbits"]
     if which == "dwconv":
         op.update(dilation=c["dil"], depth_multiplier=c["M"])
+    if which == "gconv":
+        op.update(dilation=c["dil"], groups=c["groups"])
     spec = [op]
     if bn is not None:
         n = len(bn[0])
@@ -268,15 +270,17 @@ def _one_op_spec(c, kernel, bias, bn, which):
     return spec
 
 
-def _one_op_cases(mod, which):
-    """Every epilogue and weight case whose operands pass guard: (compared, refused by guard)."""
+def _one_op_cases(mod, which, lists=("epilogue_cases", "weight_cases"), refused_cases=None):
+    """Every case of the lists (the epilogue and weight cases) whose operands pass guard: (compared, refused by guard)."""
     done, refused = 0, 0
-    for c in mod.epilogue_cases() + mod.weight_cases():
+    for c in [c for name in lists for c in getattr(mod, name)()]:
         x, kernel, bias, bn = mod.make_inputs(c)
         xv = x if c["store"] == DW.F32 else DW.values_of(x, c["store"], c["x_bits"])
         spec = _one_op_spec(c, kernel, bias, bn, which)
         if S.guard(spec, xv) is not None:
             refused += 1
+            if refused_cases is not None:
+                refused_cases.append(c)
             continue
         want = mod.reference(c, x, kernel, bias, bn)
         got = S.reference(spec, xv)
@@ -390,3 +394,158 @@ def test_recorded_coverage_table_is_current():
                 cover.setdefault(c, []).append("seed %d" % seed)
     with open(os.path.join(GOLDEN, "spec_wide_coverage.json")) as f:
         assert json.load(f) == {c: cover[c][:2] for c in sorted(S.REQUIRED_WIDE)}
+
+
+# ---- the grouped convolution: gconv in the shared reference, guard and plan(); HAND_GROUPED, generate_grouped ---------------
+import gconv_cases as GC                  # noqa: E402
+
+CONTRACTIONS = ("conv", "dense", "dwconv", "tconv", "gconv")
+GROUPED = [(c["name"], c["spec"], c["x"], c["image"]) for c in S.HAND_GROUPED]
+
+
+def test_all_four_old_lists_are_the_parent_commits_lists():
+    """HAND, generate, HAND_WIDE and generate_wide yield what they yielded before this file learnt the gconv op: the
+    digests golden/make_fixtures_spec_grouped.py recorded from the parent commit."""
+    with open(os.path.join(GOLDEN, "spec_grouped_parent.json")) as f:
+        want = json.load(f)
+    assert {c["name"]: G.spec_digest(c["spec"], c["x"]) for c in S.HAND} == want["hand"]
+    assert {str(seed): G.spec_digest(*S.generate(seed)) for seed in S.SEEDS} == want["generated"]
+    assert {c["name"]: G.spec_digest(c["spec"], c["x"]) for c in S.HAND_WIDE} == want["hand_wide"]
+    assert {str(seed): G.spec_digest(*S.generate_wide(seed)[:2]) for seed in S.SEEDS_WIDE} == want["generated_wide"]
+    assert [len(want[k]) for k in ("hand", "generated", "hand_wide", "generated_wide")] == [85, 48, 58, 64]
+
+
+def test_one_op_gconv_specs_equal_gconv_cases_reference():
+    """Every plain, weight, epilogue and matrix-pipe case of gconv_cases as a one-op spec.  The guard refuses one case, of
+    the float32 store: the 16-bit weights of weight_cases on float32 inputs (units of 2^-21, where a 3 x 3 x 3 window of
+    magnitudes up to 1 may pass 2^24 units).  No packed case is refused."""
+    refused = []
+    done, n = _one_op_cases(GC, "gconv", ("plain_cases", "weight_cases", "epilogue_cases", "mfma_cases"), refused)
+    assert done >= 200 and n == len(refused) == 1, (done, n)          # (200: what the tconv test demands)
+    assert [(c["store"], c["wkind"], c["wbits"]) for c in refused] == [(GC.F32, GC.W_QUANT, 16)]
+    assert done == 491
+
+
+def test_grouped_hand_specs_are_legal_and_exact_by_construction():
+    assert len({n for n, _, _, _ in GROUPED}) == len(GROUPED)
+    for name, spec, x, image in GROUPED:
+        y = S.reference(spec, x)
+        assert y.shape[0] == S.N == x.shape[0] and y.size > 0 and np.all(np.isfinite(y)), name
+        assert S.guard(spec, x) is None, (name, S.guard(spec, x))          # the guard may reject no hand-written spec
+        assert any(op["op"] == "gconv" for op in spec), name
+        assert sum(op["op"] in CONTRACTIONS for op in spec) <= S.MAX_CONTRACTIONS_WIDE, name
+        assert x.shape[1:] == image and image[:2] in ((8, 8), (9, 7), (4, 4)), name
+    assert set(S.CAPTURED_GROUPED) <= {n for n, _, _, _ in GROUPED}
+    logs = 0
+    for case in S.HAND_GROUPED:               # the logs written out by hand are what the restated planner predicts
+        if case["log"] is not None:
+            assert S.plan(case["spec"], case["image"])[1] == case["log"], case["name"]
+            logs += 1
+    assert logs >= 50
+
+
+def test_grouped_generated_specs_are_legal_deterministic_and_mostly_exact():
+    rejected, shapes, groups = [], set(), set()
+    for seed in S.SEEDS_GROUPED:
+        spec, x, image = S.generate_grouped(seed)
+        again, x2, _ = S.generate_grouped(seed)
+        assert _same_spec(spec, again) and np.array_equal(x, x2), seed
+        y = S.reference(spec, x)
+        assert y.shape[0] == S.N == x.shape[0] and y.size > 0 and np.all(np.isfinite(y)), seed
+        assert x.shape[1:] in ((8, 8, 3), (9, 7, 3)) and np.array_equal(x * 8, np.rint(x * 8)), seed
+        shapes.add(x.shape[1:])
+        assert sum(op["op"] in CONTRACTIONS for op in spec) <= S.MAX_CONTRACTIONS_WIDE, seed
+        assert any(op["op"] == "gconv" for op in spec), seed
+        for op in spec:
+            if op["op"] == "gconv":
+                kh, kw, cg, cout = op["kernel"].shape
+                assert cout % op["groups"] == 0 and cout in S.CHANNELS_WIDE and cg * op["groups"] in S.CHANNELS_WIDE, seed
+                groups.add(op["groups"])
+        log = S.plan(spec, image)[1]
+        if seed % 4 == 0:                     # every forced form appears in its seed's log
+            assert "gconv_i4_mfma" in log or "gconv_i8_mfma" in log, (seed, log)
+            assert all(op["kind"] == "quantized" and op["nb"] in (4, 8) for op in spec if op["op"] in CONTRACTIONS), seed
+        if seed % 4 == 1:
+            i = min(log.index(k) for k in ("gconv_i4_plain", "gconv_i8_plain") if k in log)
+            assert i > 0 and log[i - 1] == "pack", (seed, log)
+        why = S.guard(spec, x)
+        if why is not None:
+            rejected.append((seed, why))
+    assert len(S.SEEDS_GROUPED) == 32 and shapes == {(8, 8, 3), (9, 7, 3)}
+    assert len(rejected) <= 4, rejected
+    assert {1, 2, 3, 4, 8} <= groups, groups
+
+
+def _grouped_cover():
+    cover = {}
+    for name, spec, _, image in GROUPED:
+        for c in S.categories_grouped(spec, image):
+            cover.setdefault(c, []).append(name)
+    for seed in S.SEEDS_GROUPED:
+        spec, x, image = S.generate_grouped(seed)
+        if S.guard(spec, x) is None:
+            for c in S.categories_grouped(spec, image):
+                cover.setdefault(c, []).append("seed %d" % seed)
+    return cover
+
+
+def test_grouped_lists_cover_required_and_the_recorded_table_is_current():
+    """golden/spec_grouped_coverage.json: per category of REQUIRED_GROUPED the first two hand-written cases or unrejected
+    seeds that cover it, hand-written cases first."""
+    cover = _grouped_cover()
+    need = ({"op gconv", "max activation in front of gconv", "LayerModel chain", "gconv clip in the epilogue",
+             "BN behind gconv read twice", "gconv matrix-pipe form", "gconv plain form: other out store"} |
+            {"launch %s" % k for k in S.GCONV_LAUNCHES} | {"packed gconv output read by %s" % k for k in S.GCONV_READERS})
+    assert need <= S.REQUIRED_GROUPED and len(S.GCONV_LAUNCHES) == 7 and len(S.REQUIRED_GROUPED) == 33
+    assert not {c for c in S.REQUIRED_GROUPED if not cover.get(c)}
+    with open(os.path.join(GOLDEN, "spec_grouped_coverage.json")) as f:
+        assert json.load(f) == {c: cover[c][:2] for c in sorted(S.REQUIRED_GROUPED)}
+    # the generator reaches both forms and the join on its own
+    for c in ("launch gconv_i4_mfma", "launch gconv_i8_mfma", "launch gconv_i4_plain", "launch gconv_i8_plain", "pack_clips join"):
+        assert any(n.startswith("seed") for n in cover[c]), c
+    assert S.REQUIRED == S.REQUIRED_OLD | S.REQUIRED_WIDE and len(S.REQUIRED_WIDE) == 42
+
+
+def test_groups_one_and_groups_cin_equal_the_conv_and_dwconv_twins():
+    """The gconv branch of the reference against the conv branch (groups = 1) and the dwconv branch (groups = Cin, M = Fg,
+    kernel reshaped): every tensor of the network bit for bit, and the guard agrees."""
+    by_name = {c["name"]: c for c in S.HAND_GROUPED}
+    for names, twin, kind in ((S.GROUPS_ONE, S.conv_twin, "conv"), (S.GROUPS_CIN, S.dwconv_twin, "dwconv")):
+        assert len(names) == 3
+        for name in names:
+            c = by_name[name]
+            other = twin(c["spec"])
+            assert not any(op["op"] == "gconv" for op in other) and sum(op["op"] == "gconv" for op in c["spec"]) == 1
+            assert [op["op"] for op in other] == [kind if op["op"] == "gconv" else op["op"] for op in c["spec"]]
+            got, want = S.reference(c["spec"], c["x"], return_all=True), S.reference(other, c["x"], return_all=True)
+            assert set(got) == set(want)
+            for k in want:
+                assert same_bits(got[k], want[k]), (name, k)
+            assert S.guard(other, c["x"]) is None
+    # ... and the grouped sum itself against the block-diagonal ordinary convolution, groups in between
+    rng = np.random.default_rng(5)
+    for g, cg, fg, k, s, same, dil in ((2, 3, 5, (3, 3), 1, True, (1, 1)), (3, 5, 1, (2, 3), 2, False, (1, 1)),
+                                       (4, 4, 4, (3, 3), 1, True, (2, 2))):
+        x = rng.integers(-8, 8, (2, 9, 7, g * cg))
+        w = rng.integers(-8, 8, k + (cg, g * fg))
+        full = O.int_conv2d(x, D.stuff(GC.expand_block_diagonal(w, g), *dil), (s, s), "same" if same else "valid")
+        np.testing.assert_array_equal(GC.gconv_sum(x, w, g, s, same, dil), full)
+
+
+def test_shared_reference_equals_the_resnext_reference():
+    import test_gpu_gconv as TG
+    for skip in (True, False):
+        spec = TG.resnext_spec(skip=skip)
+        for seed in (0, 1):
+            x = TG._features(seed)
+            assert same_bits(S.reference(spec, x), TG.resnext_reference(spec, x)), skip
+            assert S.guard(spec, x) is None
+            assert S.plan(spec, x.shape[1:])[1] == ["pack", "gconv_i4_mfma"]
+
+
+def test_fused_engines_group_takes_no_grouped_spec():
+    for name, spec, _, _ in GROUPED:
+        assert engine.FusedModel._group(spec) is None and not S.chain(spec), name
+    for seed in S.SEEDS_GROUPED:
+        spec = S.generate_grouped(seed)[0]
+        assert engine.FusedModel._group(spec) is None and not S.chain(spec), seed
