@@ -23,7 +23,7 @@ from .layers.quantized_layers import (QuantizedConv2D, QuantizedDense,  # noqa: 
 from .layers.ternary_layers import TernaryConv2D, TernaryDense, TernaryConvolution2D  # noqa: F401
 from .layers.pooling import (MaxPooling2D, AveragePooling2D, GlobalAveragePooling2D,  # noqa: F401
                              GlobalMaxPooling2D)
-from .layers.merge import Concatenate  # noqa: F401
+from .layers.merge import Concatenate, Add, Subtract, Multiply, Average, Maximum, Minimum  # noqa: F401
 from .layers.spatial import ZeroPadding2D, Cropping2D, UpSampling2D  # noqa: F401
 from .layers.depthwise import (DepthwiseConv2D, BinaryDepthwiseConv2D, QuantizedDepthwiseConv2D,  # noqa: F401
                                TernaryDepthwiseConv2D)
@@ -39,7 +39,7 @@ __all__ = [
     "QuantizedConv2D", "QuantizedDense", "QuantizedConvolution2D",
     "TernaryConv2D", "TernaryDense", "TernaryConvolution2D",
     "MaxPooling2D", "AveragePooling2D", "GlobalAveragePooling2D", "GlobalMaxPooling2D",
-    "Concatenate",
+    "Concatenate", "Add", "Subtract", "Multiply", "Average", "Maximum", "Minimum",
     "ZeroPadding2D", "Cropping2D", "UpSampling2D",
     "DepthwiseConv2D", "BinaryDepthwiseConv2D", "QuantizedDepthwiseConv2D", "TernaryDepthwiseConv2D",
     "Conv2DTranspose", "BinaryConv2DTranspose", "QuantizedConv2DTranspose", "TernaryConv2DTranspose",

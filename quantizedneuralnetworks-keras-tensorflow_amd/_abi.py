@@ -1,6 +1,6 @@
 """ctypes binding of include/qnn_abi.h, qnn_abi_dilation.h, qnn_abi_qact.h, qnn_abi_maxact.h, qnn_abi_pool.h,
-qnn_abi_scaled.h, qnn_abi_concat.h, qnn_abi_spatial.h, qnn_abi_depthwise.h, qnn_abi_tconv.h and qnn_abi_gconv.h
-(csrc/libqnn_hip.so).
+qnn_abi_scaled.h, qnn_abi_concat.h, qnn_abi_spatial.h, qnn_abi_depthwise.h, qnn_abi_tconv.h, qnn_abi_gconv.h and
+qnn_abi_merge.h (csrc/libqnn_hip.so).
 
 The library is loaded eagerly and loudly: a missing or unloadable .so raises at
 import time of any op that needs it (there is no CPU implementation to fall back
@@ -80,10 +80,21 @@ TC_MAX_WINDOW, TC_MAX_STRIDE = 8, 4
 EXPORTS_GCONV = ["qnn_gconv_prepack", "qnn_gconv_free", "qnn_gconv_dequant", "qnn_gconv_out_hw", "qnn_gconv_forward"]
 GC_MAX_WINDOW = 7
 
+# include/qnn_abi_merge.h: Add / Subtract / Multiply / Average / Maximum / Minimum on float32 and on packed codes
+EXPORTS_MERGE = ["qnn_merge_out_store", "qnn_merge_forward"]
+MERGE_MAX = 8
+MERGE_ADD, MERGE_SUB, MERGE_MUL, MERGE_AVG, MERGE_MAXIMUM, MERGE_MINIMUM = range(6)
+MERGE_OPS = {"add": MERGE_ADD, "sub": MERGE_SUB, "mul": MERGE_MUL, "avg": MERGE_AVG, "max": MERGE_MAXIMUM, "min": MERGE_MINIMUM}
+
 
 class Spatial2D(ctypes.Structure):
     """qnn_spatial2d_t"""
     _fields_ = [("crop", ctypes.c_int32 * 4), ("up", ctypes.c_int32 * 2), ("pad", ctypes.c_int32 * 4)]
+
+
+class Merge(ctypes.Structure):
+    """qnn_merge_t"""
+    _fields_ = [("n", ctypes.c_int32), ("op", ctypes.c_int32), ("x", ctypes.c_void_p * MERGE_MAX)]
 
 
 class Concat(ctypes.Structure):
@@ -221,8 +232,10 @@ def load():
     lib.qnn_gconv_dequant.argtypes = [vp, vp, vp]
     lib.qnn_gconv_out_hw.argtypes = [vp, ci, ci, ctypes.POINTER(ci), ctypes.POINTER(ci)]
     lib.qnn_gconv_forward.argtypes = [vp, vp, ci, ci, ci, ci, ci, ctypes.POINTER(Epilogue), vp, vp]
+    lib.qnn_merge_out_store.argtypes = [ci, ci]
+    lib.qnn_merge_forward.argtypes = [ctypes.POINTER(Merge), ci, ci, sz, ci, ci, vp, vp]
     for name in (EXPORTS + EXPORTS_DILATION + EXPORTS_QACT + EXPORTS_MAXACT + EXPORTS_POOL + EXPORTS_SCALED + EXPORTS_CONCAT
-                 + EXPORTS_SPATIAL + EXPORTS_DEPTHWISE + EXPORTS_TCONV + EXPORTS_GCONV):   # every symbol the headers declare must be exported
+                 + EXPORTS_SPATIAL + EXPORTS_DEPTHWISE + EXPORTS_TCONV + EXPORTS_GCONV + EXPORTS_MERGE):   # every symbol the headers declare must be exported
         getattr(lib, name)
     _lib = lib
     return lib
@@ -553,6 +566,59 @@ def concat(tensors, channels, store, bits, pixels):
         raise QnnUnsupported("qnn_concat_forward: " + load().qnn_last_error().decode(errors="replace"))
     check(rc, "qnn_concat_forward")
     return y
+
+
+def merge_out_store(op, store):
+    """qnn_merge_out_store: the store the merge `op` ("add" | "sub" | "mul" | "avg" | "max" | "min", or a MERGE_* number)
+    of inputs of `store` is written in: `store` itself where the result is again a code, else STORE_F32."""
+    if isinstance(op, str) and op not in MERGE_OPS:
+        raise QnnError("merge: fn=%r (one of %s)" % (op, ", ".join(MERGE_OPS)))
+    rc = load().qnn_merge_out_store(MERGE_OPS[op] if isinstance(op, str) else int(op), int(store))
+    if rc < 0:
+        check(rc, "qnn_merge_out_store")
+    return rc
+
+
+def merge(xs, op, store, bits, pixels, channels):
+    """qnn_merge_forward: the element-wise merge `op` ("add" | "sub" | "mul" | "avg" | "max" | "min", or a MERGE_* number)
+    of 2 .. MERGE_MAX tensors of one shape, `pixels` rows of `channels` values: float32 (store = STORE_F32), or int32 packed
+    words (STORE_BIN / _I4 / _I8 at `bits`, STORE_T2) as pack() writes them.  Returns (tensor, out_store): the packed words
+    of the result where it is again a code (max / min; mul of BIN and T2), spare bits zero, else float32 (pixels, channels).
+    CUDA tensors only: there is no CPU path."""
+    xs = list(xs)
+    out_store = merge_out_store(op, store)
+    opn = MERGE_OPS[op] if isinstance(op, str) else int(op)
+    if not 2 <= len(xs) <= MERGE_MAX:
+        raise QnnError("merge: %d inputs (qnn_merge_forward takes 2 .. %d)" % (len(xs), MERGE_MAX))
+    if opn == MERGE_SUB and len(xs) != 2:
+        raise QnnError("merge: a subtraction takes exactly 2 inputs, got %d" % len(xs))
+    pixels, channels = int(pixels), int(channels)
+    if channels < 1:
+        raise QnnError("merge: channels=%d" % channels)
+    cols = channels if store == STORE_F32 else words(store, channels)
+    ts = []
+    for i, t in enumerate(xs):
+        if store == STORE_F32:
+            t = require_cuda(t, "merge")
+        elif not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int32 and t.is_contiguous()):
+            raise QnnError("merge: a packed input must be a contiguous int32 CUDA tensor")
+        if t.numel() != pixels * cols:
+            raise QnnError("merge: input %d holds %d elements, %d pixels of %d channels are %d"
+                           % (i, t.numel(), pixels, channels, pixels * cols))
+        ts.append(t)
+    desc = Merge()
+    desc.n, desc.op = len(ts), opn
+    for i, t in enumerate(ts):
+        desc.x[i] = t.data_ptr()
+    if out_store == STORE_F32:
+        y = torch.empty((pixels, channels), dtype=torch.float32, device=ts[0].device)
+    else:
+        y = torch.empty((pixels, cols), dtype=torch.int32, device=ts[0].device)
+    rc = load().qnn_merge_forward(ctypes.byref(desc), int(store), int(bits), pixels, channels, out_store, ptr(y), stream_ptr())
+    if rc == QNN_EUNSUPPORTED:
+        raise QnnUnsupported("qnn_merge_forward: " + load().qnn_last_error().decode(errors="replace"))
+    check(rc, "qnn_merge_forward")
+    return y, out_store
 
 
 def softmax(x, out=None):

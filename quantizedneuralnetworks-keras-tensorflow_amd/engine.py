@@ -14,6 +14,8 @@
   GraphModel          general interpreter, one launch per contraction with the activation clip fused into its
                       pack-on-load and BN into its epilogue; the stock Keras layers around it are float32 torch ops.
                       The plain counterpart the tests hold the fused engines against, and the one engine that runs
+                      {"op": "merge", "fn": "add|sub|mul|avg|max|min", "srcs": [...]} (Keras' element-wise merge layers,
+                      qnn_merge_forward: on the codes where every branch hands codes of one store and width) and
                       {"op": "concat", "srcs": [...]} (channel concatenation, qnn_concat_forward: on packed codes
                       where every branch hands codes of one store) and the new-form spatial ops {"op": "crop"},
                       {"op": "upsample"} and {"op": "zeropad", "pad": ((t, b), (l, r))} (qnn_spatial2d_forward: behind
@@ -238,8 +240,9 @@ class _SpecGraph:
         self.spec, self.device = spec, torch.device(device)
         self.names = [op.get("dst", "t%d" % i) for i, op in enumerate(spec)]
         self.prod = {n: i for i, n in enumerate(self.names)}
-        # the tensors op i reads: add -> a, b; concat -> its srcs; a named `src`; else the previous op's output; else the images
-        self.srcs = [[op["a"], op["b"]] if op["op"] == "add" else list(op["srcs"]) if op["op"] == "concat" else
+        # the tensors op i reads: add -> a, b; concat, merge -> their srcs; a named `src`; else the previous op's output; else
+        # the images
+        self.srcs = [[op["a"], op["b"]] if op["op"] == "add" else list(op["srcs"]) if op["op"] in ("concat", "merge") else
                      [op["src"] if "src" in op else self.names[i - 1] if i > 0 else "input"] for i, op in enumerate(spec)]
         self.cons = {}
         for i, ss in enumerate(self.srcs):
@@ -460,6 +463,41 @@ def _concat_f32(tensors, log=None):
     return y.reshape(shape)
 
 
+def _merge_shape(shapes, op):
+    """The one shape of the tensors a merge op reads (QnnError naming the shapes unless they are identical: Keras would
+    broadcast) after the checks on their number."""
+    fn = op.get("fn")
+    if fn not in _abi.MERGE_OPS:
+        raise ValueError("merge: fn=%r (one of %s)" % (fn, ", ".join(_abi.MERGE_OPS)))
+    shapes = [tuple(int(d) for d in s) for s in shapes]
+    if not 2 <= len(shapes) <= _abi.MERGE_MAX or (fn == "sub" and len(shapes) != 2):
+        raise ValueError("merge %r: %d sources (2 .. %d; 'sub': exactly 2)" % (fn, len(shapes), _abi.MERGE_MAX))
+    if len(set(shapes)) != 1:
+        raise _abi.QnnError("merge %r: sources of shapes %s; only identical shapes are supported (no broadcasting)" % (fn, shapes))
+    return shapes[0]
+
+
+def _merge_f32(tensors, op, log=None):
+    """A merge op on float32 tensors (merge_f32): Keras' left-to-right chain."""
+    shape = _merge_shape([t.shape for t in tensors], op)
+    y = _abi.merge([t.contiguous() for t in tensors], op["fn"], _abi.STORE_F32, 0, math.prod(shape[:-1]), shape[-1])[0]
+    if log is not None:
+        log.append(_abi.last_kernel())
+    return y.reshape(shape)
+
+
+# Packed forms that GraphModel sends through float32 instead (unpack -> merge_f32): the ones measured slower than that
+# route beyond its own spread (profiles/merge/README.md).  (fn, store) pairs.
+_MERGE_F32_ROUTE = frozenset()
+
+
+def _refuse_merge(spec, who):
+    """The fused engines plan one tensor per op (an add: two, as the ResNet shortcut); GraphModel (and LayerModel) run a
+    spec whose branches meet in a Keras merge layer."""
+    if any(op["op"] == "merge" for op in spec):
+        raise _abi.NotFusable("%s: op 'merge' (element-wise merge of branches) is not expressed by this engine; use GraphModel" % who)
+
+
 def _refuse_dwconv(spec, who):
     """The fused engines plan full convolutions only: a spec that holds a depthwise convolution runs on GraphModel."""
     if any(op["op"] == "dwconv" for op in spec):
@@ -624,6 +662,7 @@ class FusedModel(_DomainFlag):
         self.steps = []
         self._keep = []
         _refuse_concat(spec, "FusedModel")
+        _refuse_merge(spec, "FusedModel")
         _refuse_dwconv(spec, "FusedModel")
         _refuse_tconv(spec, "FusedModel")
         _refuse_gconv(spec, "FusedModel")
@@ -1122,6 +1161,33 @@ class GraphModel:
             return _Virtual(_concat_f32([t.pre for t in srcs], self.kernel_log), first.fn, first.nb, first.op)
         return _concat_f32([self._plain(t) for t in srcs], self.kernel_log)
 
+    def _merge(self, srcs, op):
+        """A merge op on the evaluated tensors `srcs` (include/qnn_abi_merge.h).  Where every source is packed codes of one
+        store, width, meaning (a clip's codes or ternary values) and shape, the op runs on the codes: max / min, and mul
+        of +-1 or ternary codes, leave codes that stay packed for the next contraction, the other ops decode in registers
+        and leave float32.  A clip that is not materialised yet is packed first, as its consumers would pack it on load.
+        Everything else (different stores or widths, ternary values beside a clip's codes, a batch-scaled activation, a
+        plain tensor among the sources) is made plain and merged in float32."""
+        shape = _merge_shape([t.shape if isinstance(t, (_Packed, _Scaled)) else t.pre.shape if isinstance(t, _Virtual) else t.shape
+                              for t in srcs], op)
+        packs = [None]
+        if all(isinstance(t, (_Packed, _Virtual)) for t in srcs):
+            packs = [t if isinstance(t, _Packed) else self._pack_clip(t) for t in srcs]
+        if all(p is not None for p in packs) and len({(p.store, p.bits, p.grid) for p in packs}) == 1 and \
+                (op["fn"], packs[0].store) not in _MERGE_F32_ROUTE:
+            first = packs[0]
+            y, out_store = _abi.merge([p.t for p in packs], op["fn"], first.store, first.bits, math.prod(shape[:-1]), shape[-1])
+            if self.kernel_log is not None:
+                self.kernel_log.append(_abi.last_kernel())
+            if out_store == _abi.STORE_F32:
+                return y.reshape(shape)
+            out = _Packed(y, first.store, first.bits, shape)
+            out.grid = first.grid
+            return out
+        if self.kernel_log is not None and any(isinstance(t, _Packed) for t in srcs):
+            self.kernel_log.append("unpack")
+        return _merge_f32([self._plain(t) for t in srcs], op, self.kernel_log)
+
     @staticmethod
     def _pack_grid_like(v, like):
         """Ternary clip `v` packed on the store of `like`, ternary codes themselves; else None."""
@@ -1311,6 +1377,8 @@ class GraphModel:
                 y = self._concat([env[s] for s in g.srcs[i]],
                                  pack_clips=any(s in upsampled or (s in g.prod and spec[g.prod[s]]["op"] in _SPATIAL and
                                                                    _new_spatial(spec[g.prod[s]])) for s in g.srcs[i]))
+            elif kind == "merge":
+                y = self._merge([env[s] for s in g.srcs[i]], op)
             elif kind in _SPATIAL and _new_spatial(op):
                 y = self._spatial(src, op, name)
             elif kind == "act" and _act_code(op) is not None:
@@ -1422,6 +1490,7 @@ class ResidualFusedModel(_DomainFlag):
         if first_layer not in ("auto", "exact", "image"):
             raise ValueError("first_layer must be 'auto', 'exact' or 'image', got %r" % (first_layer,))
         _refuse_concat(spec, "ResidualFusedModel")
+        _refuse_merge(spec, "ResidualFusedModel")
         _refuse_dwconv(spec, "ResidualFusedModel")
         _refuse_tconv(spec, "ResidualFusedModel")
         _refuse_gconv(spec, "ResidualFusedModel")
@@ -2088,6 +2157,8 @@ class LayerModel:
             src, d = env[sname], None
             if kind == "add":
                 y = _add(src, env[op["b"]])
+            elif kind == "merge":
+                y = _merge_f32([env[s] for s in g.srcs[i]], op)
             elif kind in ("conv", "dense", "dwconv", "tconv", "gconv"):
                 layer = self.layers[i]
                 layer.input_domain = dom.get(sname) if self.fuse_input_activation else None

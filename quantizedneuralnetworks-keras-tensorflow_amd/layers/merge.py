@@ -58,3 +58,88 @@ class Concatenate:
     @classmethod
     def from_config(cls, config):
         return cls(**config)
+
+
+class _Merge:
+    """keras.layers.merge._Merge for tensors of one shape: a list of float32 tensors in, `fn` of them out, element by
+    element, through qnn_merge_forward (include/qnn_abi_merge.h): Keras' own left-to-right chain, one rounding per step.
+    Keras broadcasts inputs of different shapes; this port does not (QnnError naming the shapes)."""
+
+    fn = None
+
+    def __init__(self, name=None, **kwargs):
+        kwargs.pop("input_shape", None)
+        kwargs.pop("trainable", None)
+        if kwargs:
+            raise TypeError("unexpected keyword arguments: %s" % sorted(kwargs))
+        self.name = name or type(self).__name__.lower()
+
+    def _check(self, shapes):
+        """Keras' own checks (merge.py:_Merge.build), then the one shape this port has a kernel for."""
+        if not isinstance(shapes, (list, tuple)) or (shapes and not all(isinstance(s, (list, tuple)) for s in shapes)):
+            raise ValueError("A merge layer should be called on a list of inputs.")
+        if len(shapes) < 2:
+            raise ValueError("A merge layer should be called on a list of at least 2 inputs. Got %d inputs." % len(shapes))
+        if self.fn == "sub" and len(shapes) != 2:
+            raise ValueError("A `Subtract` layer should be called on exactly 2 inputs")
+        shapes = [tuple(s) for s in shapes]
+        if len(set(shapes)) != 1:
+            raise _abi.QnnError("%s: inputs of shapes %s; only identical shapes are supported (no broadcasting)"
+                                % (self.name, shapes))
+        if len(shapes) > _abi.MERGE_MAX:
+            raise _abi.QnnError("%s: %d inputs (at most %d)" % (self.name, len(shapes), _abi.MERGE_MAX))
+        return shapes
+
+    def compute_output_shape(self, input_shape):
+        return self._check(input_shape)[0]
+
+    def call(self, inputs):
+        if not isinstance(inputs, (list, tuple)):
+            raise ValueError("A merge layer should be called on a list of inputs.")
+        shape = self._check([tuple(x.shape) for x in inputs])[0]      # the shapes first: these answers need no device
+        xs = [_abi.require_cuda(x, self.name) for x in inputs]
+        if not shape:
+            raise _abi.QnnError("%s: scalar inputs" % self.name)
+        pixels = 1
+        for d in shape[:-1]:
+            pixels *= d
+        return _abi.merge(xs, self.fn, _abi.STORE_F32, 0, pixels, shape[-1])[0].reshape(shape)
+
+    __call__ = call
+
+    def get_config(self):
+        return {"name": self.name, "trainable": True}
+
+    @classmethod
+    def from_config(cls, config):
+        return cls(**config)
+
+
+class Add(_Merge):
+    """keras.layers.Add: x0 + x1 + ... left to right."""
+    fn = "add"
+
+
+class Subtract(_Merge):
+    """keras.layers.Subtract: x0 - x1, exactly two inputs."""
+    fn = "sub"
+
+
+class Multiply(_Merge):
+    """keras.layers.Multiply: x0 * x1 * ... left to right."""
+    fn = "mul"
+
+
+class Average(_Merge):
+    """keras.layers.Average: the sum chain of Add, then one division by the number of inputs."""
+    fn = "avg"
+
+
+class Maximum(_Merge):
+    """keras.layers.Maximum: element-wise maximum; NaN where any input is NaN."""
+    fn = "max"
+
+
+class Minimum(_Merge):
+    """keras.layers.Minimum: element-wise minimum; NaN where any input is NaN."""
+    fn = "min"

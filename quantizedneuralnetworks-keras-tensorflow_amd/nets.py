@@ -320,11 +320,11 @@ class Model:
                 self.engine = engine.ResidualFusedModel(spec, device,
                                                         first_layer=first_layer if first_layer in ("auto", "image") else "exact")
             except _abi.NotFusable:
-                # only the batch-scaled activations (float32 between the layers), channel concatenation, depthwise,
+                # only the batch-scaled activations (float32 between the layers), channel concatenation, the merge layers, depthwise,
                 # transposed and grouped convolution and the new-form
                 # spatial ops (crop, upsample, pair-form zeropad) are handed on; anything else the residual engine
                 # refuses stays an error
-                if not any((op["op"] == "act" and op["fn"] in BATCH_SCALED_ACTIVATIONS) or op["op"] in ("concat", "dwconv", "tconv", "gconv") or
+                if not any((op["op"] == "act" and op["fn"] in BATCH_SCALED_ACTIVATIONS) or op["op"] in ("concat", "merge", "dwconv", "tconv", "gconv") or
                            (op["op"] in engine._SPATIAL and engine._new_spatial(op)) for op in spec):
                     raise
                 self.engine = engine.GraphModel(spec, device, scaled_codes=scaled_codes)
@@ -522,6 +522,9 @@ _GCONV_KINDS = {"GroupedConv2D": "float", "BinaryGroupedConv2D": "binary", "Quan
 _GCONV_OLD_KINDS = {"Conv2D": "float", "BinaryConv2D": "binary", "QuantizedConv2D": "quantized", "TernaryConv2D": "ternary"}
 
 
+_MERGE_FNS = {"Add": "add", "Subtract": "sub", "Multiply": "mul", "Average": "avg", "Maximum": "max", "Minimum": "min"}
+
+
 def spec_from_keras_npz(path, wbits=None, abits=None):
     """Rebuild a net spec from a Keras 2.1.3 checkpoint converted by tools/import_keras_hdf5.py
     (counterpart of test_resnet.py:44-66 build + load_weights).  The topology comes from the
@@ -658,8 +661,14 @@ def spec_from_keras_npz(path, wbits=None, abits=None):
                 raise ValueError("unsupported activation %r" % fn)
         elif cls == "LeakyReLU":
             op = {"op": "act", "fn": "leaky_relu", "alpha": float(c.get("alpha", 0.3))}
-        elif cls == "Add":
+        elif cls == "Add" and len(inbound) == 2:
             op = {"op": "add", "a": "input" if inbound[0] == spec_alias else inbound[0], "b": inbound[1]}
+            src = None
+        elif cls in _MERGE_FNS:
+            # keras.layers.Subtract / Multiply / Average / Maximum / Minimum, and Add of three tensors or more -> merge
+            if len(inbound) < 2 or (cls == "Subtract" and len(inbound) != 2):
+                raise ValueError("%s layer %r has %d inbound tensors" % (cls, name, len(inbound)))
+            op = {"op": "merge", "fn": _MERGE_FNS[cls], "srcs": ["input" if ib == spec_alias else ib for ib in inbound]}
             src = None
         elif cls == "Concatenate":
             axis = int(c.get("axis", -1))
