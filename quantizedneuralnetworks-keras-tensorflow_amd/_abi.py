@@ -995,66 +995,57 @@ def dense(w, x, x_store, x_bits, N, bn_inv=None, bn_shift=None, fn=FN_NONE, act_
     return y
 
 
-class DepthwiseWeights:
-    """Owner of an opaque qnn_dw_weights_t handle (include/qnn_abi_depthwise.h).  kernel: float32 CUDA tensor in Keras'
-    depthwise layout (kh, kw, C, depth_multiplier); bias: (C * depth_multiplier,) or None."""
+class _SideWeights:
+    """What DepthwiseWeights, TConvWeights and GConvWeights share: the owner of a handle behind the C symbols
+    <_prefix>_prepack / _dequant / _out_hw / _free.  A subclass checks its kernel layout and bias size and hands _prepack
+    the arguments its entry takes between the kernel pointer and the stream."""
+    _prefix = _what = None
 
-    def __init__(self, wkind, wbits, H, kernel, bias, stride, same_pad, store, dilation=(1, 1)):
-        kernel = require_cuda(kernel, "depthwise prepack kernel")
+    def _tensors(self, layout, kernel, bias):
+        kernel = require_cuda(kernel, self._what + " prepack kernel")
         if kernel.dim() != 4:
-            raise QnnError("depthwise prepack: the kernel must be (kh, kw, C, depth_multiplier), got %s" % (tuple(kernel.shape),))
-        kh, kw, C, M = kernel.shape
-        bias = require_cuda(bias, "depthwise prepack bias") if bias is not None else None
-        if bias is not None and bias.numel() != C * M:
-            raise QnnError("depthwise prepack: bias of %d values for %d x %d channels" % (bias.numel(), C, M))
-        self.shape = (kh, kw, C, M)
-        self.cout = C * M
+            raise QnnError("%s prepack: the kernel must be %s, got %s" % (self._what, layout, tuple(kernel.shape)))
+        return kernel, (require_cuda(bias, self._what + " prepack bias") if bias is not None else None)
+
+    def _prepack(self, wkind, wbits, H, kernel, stride, same_pad, store, *args):
+        self.shape = tuple(kernel.shape)
         self.wkind, self.wbits, self.store = wkind, wbits, store
         self.stride, self.same_pad = int(stride), bool(same_pad)
-        self.dilation = (int(dilation[0]), int(dilation[1]))
         self.handle = ctypes.c_void_p(None)
         release_deferred()
-        rc = load().qnn_depthwise_prepack(wkind, wbits, float(H), ptr(kernel), kh, kw, C, M, ptr(bias), self.stride,
-                                          1 if same_pad else 0, self.dilation[0], self.dilation[1], store, stream_ptr(),
-                                          ctypes.byref(self.handle))
+        name = self._prefix + "_prepack"
+        rc = getattr(load(), name)(wkind, wbits, float(H), ptr(kernel), *args, stream_ptr(), ctypes.byref(self.handle))
         if rc == QNN_EUNSUPPORTED:
-            raise QnnUnsupported("qnn_depthwise_prepack: " + load().qnn_last_error().decode(errors="replace"))
-        check(rc, "qnn_depthwise_prepack")
+            raise QnnUnsupported(name + ": " + load().qnn_last_error().decode(errors="replace"))
+        check(rc, name)
         self.device = kernel.device
 
     def dequant(self):
         out = torch.empty(self.shape, dtype=torch.float32, device=self.device)
-        check(load().qnn_depthwise_dequant(self.handle, ptr(out), stream_ptr()), "qnn_depthwise_dequant")
+        check(getattr(load(), self._prefix + "_dequant")(self.handle, ptr(out), stream_ptr()), self._prefix + "_dequant")
         return out
 
     def out_hw(self, H, W):
         Ho, Wo = ctypes.c_int(0), ctypes.c_int(0)
-        check(load().qnn_depthwise_out_hw(self.handle, int(H), int(W), ctypes.byref(Ho), ctypes.byref(Wo)),
-              "qnn_depthwise_out_hw")
+        check(getattr(load(), self._prefix + "_out_hw")(self.handle, int(H), int(W), ctypes.byref(Ho), ctypes.byref(Wo)),
+              self._prefix + "_out_hw")
         return Ho.value, Wo.value
 
     def __del__(self):
         try:
-            _release("qnn_depthwise_free", self.handle)
+            _release(self._prefix + "_free", self.handle)
             self.handle = ctypes.c_void_p(None)
         except Exception:
             pass
 
 
-def depthwise(w, x, x_store, x_bits, N, H, W, bn_inv=None, bn_shift=None, fn=FN_NONE, act_bits=0, out_store=STORE_F32,
-              out=None, epilogue=None):
-    """qnn_depthwise_forward: x is a float32 NHWC CUDA tensor (x_store = STORE_F32) or int32 packed words as pack()
-    writes them.  Returns (y, Ho, Wo): y float32 (N, Ho, Wo, C * M) or int32 (N * Ho * Wo, words).  `epilogue`: a ready
-    Epilogue instead of the keyword fields (tests of the refusals).  A refusal with QNN_EUNSUPPORTED raises QnnUnsupported."""
-    Ho, Wo = w.out_hw(H, W)
-    if Ho <= 0 or Wo <= 0:
-        raise QnnError("depthwise: empty output: %dx%d input, %dx%d window dilated %dx%d, stride %d, %s padding"
-                       % (H, W, w.shape[0], w.shape[1], w.dilation[0], w.dilation[1], w.stride,
-                          "same" if w.same_pad else "valid"))
+def _side_forward(prefix, what, w, x, x_store, x_bits, N, H, W, Ho, Wo, bn_inv, bn_shift, fn, act_bits, out_store, out,
+                  epilogue):
+    """The body depthwise(), tconv() and gconv() share, from the input check to <prefix>_forward."""
     if x_store == STORE_F32:
-        x = require_cuda(x, "depthwise")
+        x = require_cuda(x, what)
     elif not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.int32 and x.is_contiguous()):
-        raise QnnError("depthwise: a packed input must be a contiguous int32 CUDA tensor")
+        raise QnnError("%s: a packed input must be a contiguous int32 CUDA tensor" % what)
     if out_store == STORE_F32:
         shape, dt = (N, Ho, Wo, w.cout), torch.float32
     else:
@@ -1063,15 +1054,50 @@ def depthwise(w, x, x_store, x_bits, N, H, W, bn_inv=None, bn_shift=None, fn=FN_
         y = torch.empty(shape, dtype=dt, device=x.device)
     else:
         if tuple(out.shape) != shape or out.dtype != dt or not out.is_contiguous() or out.device != x.device:
-            raise QnnError("depthwise: `out` must be a contiguous %s tensor of shape %s on %s" % (dt, shape, x.device))
+            raise QnnError("%s: `out` must be a contiguous %s tensor of shape %s on %s" % (what, dt, shape, x.device))
         y = out
     epi = epilogue if epilogue is not None else make_epilogue(bn_inv, bn_shift, fn, act_bits, 1, out_store, flags=0)
-    rc = load().qnn_depthwise_forward(w.handle, ptr(x), int(x_store), int(x_bits), int(N), int(H), int(W),
-                                      ctypes.byref(epi), ptr(y), stream_ptr())
+    name = prefix + "_forward"
+    rc = getattr(load(), name)(w.handle, ptr(x), int(x_store), int(x_bits), int(N), int(H), int(W), ctypes.byref(epi), ptr(y),
+                               stream_ptr())
     if rc == QNN_EUNSUPPORTED:
-        raise QnnUnsupported("qnn_depthwise_forward: " + load().qnn_last_error().decode(errors="replace"))
-    check(rc, "qnn_depthwise_forward")
+        raise QnnUnsupported(name + ": " + load().qnn_last_error().decode(errors="replace"))
+    check(rc, name)
     return y, Ho, Wo
+
+
+def _refuse_empty(what, w, H, W, Ho, Wo):
+    if Ho <= 0 or Wo <= 0:
+        raise QnnError("%s: empty output: %dx%d input, %dx%d window dilated %dx%d, stride %d, %s padding"
+                       % (what, H, W, w.shape[0], w.shape[1], w.dilation[0], w.dilation[1], w.stride,
+                          "same" if w.same_pad else "valid"))
+
+
+class DepthwiseWeights(_SideWeights):
+    """Owner of an opaque qnn_dw_weights_t handle (include/qnn_abi_depthwise.h).  kernel: float32 CUDA tensor in Keras'
+    depthwise layout (kh, kw, C, depth_multiplier); bias: (C * depth_multiplier,) or None."""
+    _prefix, _what = "qnn_depthwise", "depthwise"
+
+    def __init__(self, wkind, wbits, H, kernel, bias, stride, same_pad, store, dilation=(1, 1)):
+        kernel, bias = self._tensors("(kh, kw, C, depth_multiplier)", kernel, bias)
+        kh, kw, C, M = kernel.shape
+        if bias is not None and bias.numel() != C * M:
+            raise QnnError("depthwise prepack: bias of %d values for %d x %d channels" % (bias.numel(), C, M))
+        self.cout = C * M
+        self.dilation = (int(dilation[0]), int(dilation[1]))
+        self._prepack(wkind, wbits, H, kernel, stride, same_pad, store, kh, kw, C, M, ptr(bias), int(stride),
+                      1 if same_pad else 0, self.dilation[0], self.dilation[1], store)
+
+
+def depthwise(w, x, x_store, x_bits, N, H, W, bn_inv=None, bn_shift=None, fn=FN_NONE, act_bits=0, out_store=STORE_F32,
+              out=None, epilogue=None):
+    """qnn_depthwise_forward: x is a float32 NHWC CUDA tensor (x_store = STORE_F32) or int32 packed words as pack()
+    writes them.  Returns (y, Ho, Wo): y float32 (N, Ho, Wo, C * M) or int32 (N * Ho * Wo, words).  `epilogue`: a ready
+    Epilogue instead of the keyword fields (tests of the refusals).  A refusal with QNN_EUNSUPPORTED raises QnnUnsupported."""
+    Ho, Wo = w.out_hw(H, W)
+    _refuse_empty("depthwise", w, H, W, Ho, Wo)
+    return _side_forward("qnn_depthwise", "depthwise", w, x, x_store, x_bits, N, H, W, Ho, Wo, bn_inv, bn_shift, fn, act_bits,
+                         out_store, out, epilogue)
 
 
 def tconv_out_hw(size, k, stride, same_pad):
@@ -1086,47 +1112,19 @@ def tconv_takes_mfma(kh, kw, stride, store, cout, cin, out_store):
             cin % 64 == 0 and cin <= 16384 and cout % 16 == 0)
 
 
-class TConvWeights:
+class TConvWeights(_SideWeights):
     """Owner of an opaque qnn_tconv_weights_t handle (include/qnn_abi_tconv.h).  kernel: float32 CUDA tensor in Keras'
     Conv2DTranspose layout (kh, kw, Cout, Cin); bias: (Cout,) or None."""
+    _prefix, _what = "qnn_tconv", "tconv"
 
     def __init__(self, wkind, wbits, H, kernel, bias, stride, same_pad, store):
-        kernel = require_cuda(kernel, "tconv prepack kernel")
-        if kernel.dim() != 4:
-            raise QnnError("tconv prepack: the kernel must be (kh, kw, Cout, Cin), got %s" % (tuple(kernel.shape),))
+        kernel, bias = self._tensors("(kh, kw, Cout, Cin)", kernel, bias)
         kh, kw, cout, cin = kernel.shape
-        bias = require_cuda(bias, "tconv prepack bias") if bias is not None else None
         if bias is not None and bias.numel() != cout:
             raise QnnError("tconv prepack: bias of %d values for %d filters" % (bias.numel(), cout))
-        self.shape = (kh, kw, cout, cin)
         self.cout, self.cin = cout, cin
-        self.wkind, self.wbits, self.store = wkind, wbits, store
-        self.stride, self.same_pad = int(stride), bool(same_pad)
-        self.handle = ctypes.c_void_p(None)
-        release_deferred()
-        rc = load().qnn_tconv_prepack(wkind, wbits, float(H), ptr(kernel), kh, kw, cout, cin, ptr(bias), self.stride,
-                                      1 if same_pad else 0, store, stream_ptr(), ctypes.byref(self.handle))
-        if rc == QNN_EUNSUPPORTED:
-            raise QnnUnsupported("qnn_tconv_prepack: " + load().qnn_last_error().decode(errors="replace"))
-        check(rc, "qnn_tconv_prepack")
-        self.device = kernel.device
-
-    def dequant(self):
-        out = torch.empty(self.shape, dtype=torch.float32, device=self.device)
-        check(load().qnn_tconv_dequant(self.handle, ptr(out), stream_ptr()), "qnn_tconv_dequant")
-        return out
-
-    def out_hw(self, H, W):
-        Ho, Wo = ctypes.c_int(0), ctypes.c_int(0)
-        check(load().qnn_tconv_out_hw(self.handle, int(H), int(W), ctypes.byref(Ho), ctypes.byref(Wo)), "qnn_tconv_out_hw")
-        return Ho.value, Wo.value
-
-    def __del__(self):
-        try:
-            _release("qnn_tconv_free", self.handle)
-            self.handle = ctypes.c_void_p(None)
-        except Exception:
-            pass
+        self._prepack(wkind, wbits, H, kernel, stride, same_pad, store, kh, kw, cout, cin, ptr(bias), int(stride),
+                      1 if same_pad else 0, store)
 
 
 def tconv(w, x, x_store, x_bits, N, H, W, bn_inv=None, bn_shift=None, fn=FN_NONE, act_bits=0, out_store=STORE_F32,
@@ -1135,27 +1133,8 @@ def tconv(w, x, x_store, x_bits, N, H, W, bn_inv=None, bn_shift=None, fn=FN_NONE
     them.  Returns (y, Ho, Wo): y float32 (N, Ho, Wo, Cout) or int32 (N * Ho * Wo, words).  `epilogue`: a ready Epilogue
     instead of the keyword fields (tests of the refusals).  A refusal with QNN_EUNSUPPORTED raises QnnUnsupported."""
     Ho, Wo = w.out_hw(H, W)
-    if x_store == STORE_F32:
-        x = require_cuda(x, "tconv")
-    elif not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.int32 and x.is_contiguous()):
-        raise QnnError("tconv: a packed input must be a contiguous int32 CUDA tensor")
-    if out_store == STORE_F32:
-        shape, dt = (N, Ho, Wo, w.cout), torch.float32
-    else:
-        shape, dt = (N * Ho * Wo, words(out_store, w.cout)), torch.int32
-    if out is None:
-        y = torch.empty(shape, dtype=dt, device=x.device)
-    else:
-        if tuple(out.shape) != shape or out.dtype != dt or not out.is_contiguous() or out.device != x.device:
-            raise QnnError("tconv: `out` must be a contiguous %s tensor of shape %s on %s" % (dt, shape, x.device))
-        y = out
-    epi = epilogue if epilogue is not None else make_epilogue(bn_inv, bn_shift, fn, act_bits, 1, out_store, flags=0)
-    rc = load().qnn_tconv_forward(w.handle, ptr(x), int(x_store), int(x_bits), int(N), int(H), int(W),
-                                  ctypes.byref(epi), ptr(y), stream_ptr())
-    if rc == QNN_EUNSUPPORTED:
-        raise QnnUnsupported("qnn_tconv_forward: " + load().qnn_last_error().decode(errors="replace"))
-    check(rc, "qnn_tconv_forward")
-    return y, Ho, Wo
+    return _side_forward("qnn_tconv", "tconv", w, x, x_store, x_bits, N, H, W, Ho, Wo, bn_inv, bn_shift, fn, act_bits,
+                         out_store, out, epilogue)
 
 
 def gconv_out_hw(size, k, stride, same_pad, dilation=1):
@@ -1163,50 +1142,21 @@ def gconv_out_hw(size, k, stride, same_pad, dilation=1):
     return out_hw(size, k, stride, same_pad, dilation)
 
 
-class GConvWeights:
+class GConvWeights(_SideWeights):
     """Owner of an opaque qnn_gconv_weights_t handle (include/qnn_abi_gconv.h).  kernel: float32 CUDA tensor in Keras'
     grouped layout (kh, kw, Cin / groups, Cout); bias: (Cout,) or None."""
+    _prefix, _what = "qnn_gconv", "gconv"
 
     def __init__(self, wkind, wbits, H, kernel, bias, groups, stride, same_pad, store, dilation=(1, 1)):
-        kernel = require_cuda(kernel, "gconv prepack kernel")
-        if kernel.dim() != 4:
-            raise QnnError("gconv prepack: the kernel must be (kh, kw, Cin / groups, Cout), got %s" % (tuple(kernel.shape),))
+        kernel, bias = self._tensors("(kh, kw, Cin / groups, Cout)", kernel, bias)
         kh, kw, cg, cout = kernel.shape
         groups = int(groups)
-        bias = require_cuda(bias, "gconv prepack bias") if bias is not None else None
         if bias is not None and bias.numel() != cout:
             raise QnnError("gconv prepack: bias of %d values for %d filters" % (bias.numel(), cout))
-        self.shape = (kh, kw, cg, cout)
         self.groups, self.cin, self.cout = groups, cg * groups, cout
-        self.wkind, self.wbits, self.store = wkind, wbits, store
-        self.stride, self.same_pad = int(stride), bool(same_pad)
         self.dilation = (int(dilation[0]), int(dilation[1]))
-        self.handle = ctypes.c_void_p(None)
-        release_deferred()
-        rc = load().qnn_gconv_prepack(wkind, wbits, float(H), ptr(kernel), kh, kw, self.cin, cout, groups, ptr(bias),
-                                      self.stride, 1 if same_pad else 0, self.dilation[0], self.dilation[1], store,
-                                      stream_ptr(), ctypes.byref(self.handle))
-        if rc == QNN_EUNSUPPORTED:
-            raise QnnUnsupported("qnn_gconv_prepack: " + load().qnn_last_error().decode(errors="replace"))
-        check(rc, "qnn_gconv_prepack")
-        self.device = kernel.device
-
-    def dequant(self):
-        out = torch.empty(self.shape, dtype=torch.float32, device=self.device)
-        check(load().qnn_gconv_dequant(self.handle, ptr(out), stream_ptr()), "qnn_gconv_dequant")
-        return out
-
-    def out_hw(self, H, W):
-        Ho, Wo = ctypes.c_int(0), ctypes.c_int(0)
-        check(load().qnn_gconv_out_hw(self.handle, int(H), int(W), ctypes.byref(Ho), ctypes.byref(Wo)), "qnn_gconv_out_hw")
-        return Ho.value, Wo.value
-
-    def __del__(self):
-        try:
-            _release("qnn_gconv_free", self.handle)
-            self.handle = ctypes.c_void_p(None)
-        except Exception:
-            pass
+        self._prepack(wkind, wbits, H, kernel, stride, same_pad, store, kh, kw, self.cin, cout, groups, ptr(bias),
+                      int(stride), 1 if same_pad else 0, self.dilation[0], self.dilation[1], store)
 
 
 def gconv(w, x, x_store, x_bits, N, H, W, bn_inv=None, bn_shift=None, fn=FN_NONE, act_bits=0, out_store=STORE_F32,
@@ -1215,28 +1165,7 @@ def gconv(w, x, x_store, x_bits, N, H, W, bn_inv=None, bn_shift=None, fn=FN_NONE
     them.  Returns (y, Ho, Wo): y float32 (N, Ho, Wo, Cout) or int32 (N * Ho * Wo, words).  `epilogue`: a ready Epilogue
     instead of the keyword fields (tests of the refusals).  A refusal with QNN_EUNSUPPORTED raises QnnUnsupported."""
     Ho, Wo = w.out_hw(H, W)
-    if Ho <= 0 or Wo <= 0:
-        raise QnnError("gconv: empty output: %dx%d input, %dx%d window dilated %dx%d, stride %d, %s padding"
-                       % (H, W, w.shape[0], w.shape[1], w.dilation[0], w.dilation[1], w.stride,
-                          "same" if w.same_pad else "valid"))
-    if x_store == STORE_F32:
-        x = require_cuda(x, "gconv")
-    elif not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.int32 and x.is_contiguous()):
-        raise QnnError("gconv: a packed input must be a contiguous int32 CUDA tensor")
-    if out_store == STORE_F32:
-        shape, dt = (N, Ho, Wo, w.cout), torch.float32
-    else:
-        shape, dt = (N * Ho * Wo, words(out_store, w.cout)), torch.int32
-    if out is None:
-        y = torch.empty(shape, dtype=dt, device=x.device)
-    else:
-        if tuple(out.shape) != shape or out.dtype != dt or not out.is_contiguous() or out.device != x.device:
-            raise QnnError("gconv: `out` must be a contiguous %s tensor of shape %s on %s" % (dt, shape, x.device))
-        y = out
-    epi = epilogue if epilogue is not None else make_epilogue(bn_inv, bn_shift, fn, act_bits, 1, out_store, flags=0)
-    rc = load().qnn_gconv_forward(w.handle, ptr(x), int(x_store), int(x_bits), int(N), int(H), int(W),
-                                  ctypes.byref(epi), ptr(y), stream_ptr())
-    if rc == QNN_EUNSUPPORTED:
-        raise QnnUnsupported("qnn_gconv_forward: " + load().qnn_last_error().decode(errors="replace"))
-    check(rc, "qnn_gconv_forward")
-    return y, Ho, Wo
+    _refuse_empty("gconv", w, H, W, Ho, Wo)
+    return _side_forward("qnn_gconv", "gconv", w, x, x_store, x_bits, N, H, W, Ho, Wo, bn_inv, bn_shift, fn, act_bits,
+                         out_store, out, epilogue)
+

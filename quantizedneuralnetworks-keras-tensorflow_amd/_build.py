@@ -20,7 +20,7 @@ OBJDIR = os.path.join(CSRC, "build")
 SOURCES = ["qnn_api.hip", "qnn_elementwise.hip", "qnn_conv.hip", "qnn_mfma.hip", "qnn_mfma_areg.hip",
            "qnn_mfma_small.hip", "qnn_route_strip.hip", "qnn_mfma_strip.hip", "qnn_mfma_strip16.hip", "qnn_mfma_strip_i8.hip", "qnn_mfma_strip_dil.hip", "qnn_first.hip", "qnn_first_fixed.hip", "qnn_first_u8.hip", "qnn_stem.hip", "qnn_fold.hip",
            "qnn_f32act.hip", "qnn_tail.hip", "qnn_maxact.hip", "qnn_maxact_pack.hip", "qnn_pool.hip", "qnn_concat.hip",
-           "qnn_spatial.hip", "qnn_depthwise.hip", "qnn_tconv.hip", "qnn_gconv.hip", "qnn_merge.hip"]
+           "qnn_spatial.hip", "qnn_sideconv.hip", "qnn_depthwise.hip", "qnn_tconv.hip", "qnn_gconv.hip", "qnn_merge.hip"]
 CFLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-Wno-cuda-compat",
           "-I" + os.path.join(ROOT, "include"), "-I" + CSRC]
 LDFLAGS = ["--offload-arch=gfx950", "-shared", "-fPIC"]

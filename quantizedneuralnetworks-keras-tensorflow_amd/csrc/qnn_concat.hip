@@ -20,7 +20,7 @@
 //                        runs the mask and the sign plane of QNN_STORE_T2 through the same steps.
 #include <stdio.h>
 
-#include "qnn_common.h"
+#include "qnn_sideconv.h"
 #include "qnn_abi_concat.h"
 
 namespace {
@@ -38,10 +38,6 @@ struct CatArgs {
     uint32_t total;
     FastDiv fd;                        // by `items`
 };
-
-template <int V> struct Words;
-template <> struct Words<1> { typedef uint32_t type; };
-template <> struct Words<4> { typedef uint4 type; };
 
 template <int V>
 __global__ __launch_bounds__(kBlock) void k_concat_words(uint32_t* __restrict__ y, const CatArgs a) {
@@ -167,7 +163,8 @@ extern "C" int qnn_concat_forward(const qnn_concat_t* c, int store, int x_bits, 
     else if (planes == 2) hipLaunchKernelGGL((k_concat_funnel<2>), grid, block, 0, s, yu, a);
     else hipLaunchKernelGGL((k_concat_funnel<1>), grid, block, 0, s, yu, a);
     QNN_HIP(hipGetLastError());
-    qnn_set_kernel_name(store == QNN_STORE_F32 ? "concat_f32" : store == QNN_STORE_BIN ? "concat_bin" :
-                        store == QNN_STORE_I4 ? "concat_i4" : store == QNN_STORE_I8 ? "concat_i8" : "concat_t2");
+    char name[16];
+    snprintf(name, sizeof(name), "concat_%s", store_name(store));
+    qnn_set_kernel_name(name);
     return QNN_OK;
 }

@@ -25,6 +25,7 @@
 #include "qnn_common.h"
 #include "qnn_fold.h"
 #include "qnn_mfma_common.h"
+#include "qnn_sideconv.h"
 
 #ifndef QNN_XNOR_U
 #define QNN_XNOR_U 16
@@ -38,35 +39,6 @@ constexpr int kBlock = 256;
 // ---------------------------------------------------------------------------
 // weights: quantize + pack on device (once per set_weights)
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ float quantize_weight(float w, int wkind, float H, float m, float cutoff) {
-    if (wkind == QNN_W_BINARY) return __fmul_rn(H, qnn_binary_tanh(__fdiv_rn(w, H)));
-    if (wkind == QNN_W_QUANT) return qnn_quantized_tanh(w, m);
-    if (wkind == QNN_W_TERNARY) {
-        // ternary_ops.py:21-27: W/H > cutoff -> 1, W/H <= -cutoff -> -1, else 0; times H.
-        // ("exact" mode: the straight-through W + (Wt - W) of ternary_ops.py:41 is taken as Wt.)
-        const float u = __fdiv_rn(w, H);
-        const float t = u > cutoff ? 1.0f : (u <= -cutoff ? -1.0f : 0.0f);
-        return __fmul_rn(t, H);
-    }
-    return w;
-}
-
-// ternary_ops.py:15-30: cutoff = 0.7 * mean(|W / H|) over the WHOLE kernel.  One block,
-// fixed reduction order (deterministic), double accumulation.
-__global__ __launch_bounds__(1024) void k_tern_cutoff(const float* __restrict__ kernel, int n, float H,
-                                                      float* __restrict__ cutoff) {
-    __shared__ double part[1024];
-    double s = 0.0;
-    for (int i = threadIdx.x; i < n; i += 1024) s += (double)fabsf(__fdiv_rn(kernel[i], H));
-    part[threadIdx.x] = s;
-    __syncthreads();
-    for (int off = 512; off > 0; off >>= 1) {
-        if ((int)threadIdx.x < off) part[threadIdx.x] += part[threadIdx.x + off];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) cutoff[0] = __fmul_rn(0.7f, (float)(part[0] / (double)n));
-}
-
 // d_wq[c][t][ci] = quantizer(kernel_hwio[t][ci][c])
 __global__ __launch_bounds__(kBlock) void k_prepack_float(const float* __restrict__ kernel,
                                                           float* __restrict__ wq, int taps,
@@ -78,7 +50,7 @@ __global__ __launch_bounds__(kBlock) void k_prepack_float(const float* __restric
         const int ci = i % cin;
         const int t = (i / cin) % taps;
         const int c = i / (cin * taps);
-        wq[i] = quantize_weight(kernel[((size_t)t * cin + ci) * cout + c], wkind, H, m, cutoff);
+        wq[i] = qnn_quantize_weight(kernel[((size_t)t * cin + ci) * cout + c], wkind, H, m, cutoff);
     }
 }
 
@@ -1604,7 +1576,7 @@ extern "C" int qnn_prepack_weights_dilated(int wkind, int wbits, float H, const 
     if (grid > 4096) grid = 4096;
     if (wkind == QNN_W_TERNARY) {
         PREPACK_HIP(hipMalloc(&w->d_aux, 16));
-        hipLaunchKernelGGL(k_tern_cutoff, dim3(1), dim3(1024), 0, s, kernel, (int)nq, H, (float*)w->d_aux);
+        qnn_launch_tern_cutoff(kernel, (int)nq, H, (float*)w->d_aux, s);
     }
     hipLaunchKernelGGL(k_prepack_float, dim3(grid), dim3(kBlock), 0, s, kernel, w->d_wq, taps, cin,
                        cout, wkind, H, m, (const float*)w->d_aux);

@@ -18,26 +18,15 @@
 //
 // Index arithmetic in 32 bits by multiply-high (the entry refuses 2^31 output words), tensor offsets in 64 bits.  Taps
 // outside the image are not loaded.
-#include <stdio.h>
-
 #include <new>
 
-#include "qnn_common.h"
+#include "qnn_sideconv.h"
 #include "qnn_abi_depthwise.h"
 
-struct qnn_dw_weights {
-    int wkind, wbits;
-    float H;
+struct qnn_dw_weights : SideWeights {      // d_wq, d_wcode: [kh*kw][cout], Keras' (kh, kw, C, M) order
     int kh, kw, C, M, cout;
     int stride, same_pad, dil_h, dil_w;
-    int store;
-    int wshift;              // quantized value = code * 2^-wshift
-    int xcw;                 // words per input pixel on the handle's packed store (F32: 0)
-    float* d_wq;             // [kh*kw][cout] quantized values: Keras' (kh, kw, C, M) order
-    int32_t* d_wcode;        // [kh*kw][cout] integer codes (packed stores) or nullptr
     uint32_t* d_wpk;         // [9][xcw][pairs per word] 16-bit code pairs in k_dw_pk16's order, or nullptr
-    float* d_bias;           // [cout] or nullptr
-    float* d_aux;            // ternary: the cutoff (1 float), else nullptr
 };
 
 namespace {
@@ -45,40 +34,6 @@ namespace {
 constexpr int kBlock = 256;
 
 // ---- weights ----------------------------------------------------------------------------------------------------------
-// ternary_ops.py:15-30: cutoff = 0.7 * mean(|W / H|) over the whole kernel.  One block, fixed order, float64 sums.
-__global__ __launch_bounds__(1024) void k_dw_tern_cutoff(const float* __restrict__ kernel, int n, float H,
-                                                         float* __restrict__ cutoff) {
-    __shared__ double part[1024];
-    double s = 0.0;
-    for (int i = threadIdx.x; i < n; i += 1024) s += (double)fabsf(__fdiv_rn(kernel[i], H));
-    part[threadIdx.x] = s;
-    __syncthreads();
-    for (int off = 512; off > 0; off >>= 1) {
-        if ((int)threadIdx.x < off) part[threadIdx.x] += part[threadIdx.x + off];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) cutoff[0] = __fmul_rn(0.7f, (float)(part[0] / (double)n));
-}
-
-// binarize (binary_ops.py:54-64), quantize (quantized_ops.py:49-66), ternarize (ternary_ops.py:21-41), elementwise; the
-// codes are value * 2^wshift (binary / ternary on a packed store have H = 1: the value itself)
-__global__ __launch_bounds__(kBlock) void k_dw_quantize(const float* __restrict__ kernel, float* __restrict__ wq,
-                                                        int32_t* __restrict__ wcode, int n, int wkind, float H, float m,
-                                                        const float* __restrict__ cutoff_p) {
-    const int i = blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
-    const float w = kernel[i];
-    float q = w;
-    if (wkind == QNN_W_BINARY) q = __fmul_rn(H, qnn_binary_tanh(__fdiv_rn(w, H)));
-    else if (wkind == QNN_W_QUANT) q = qnn_quantized_tanh(w, m);
-    else if (wkind == QNN_W_TERNARY) {
-        const float u = __fdiv_rn(w, H), cutoff = cutoff_p[0];
-        q = __fmul_rn(u > cutoff ? 1.0f : (u <= -cutoff ? -1.0f : 0.0f), H);
-    }
-    wq[i] = q;
-    if (wcode) wcode[i] = (int)__fmul_rn(q, m);
-}
-
 // 16-bit code pairs: word (t, w, p) = code of channel w*PW + p (low half) and of channel w*PW + p + PW/2 (high half)
 __global__ __launch_bounds__(kBlock) void k_dw_pairs(const int32_t* __restrict__ wcode, uint32_t* __restrict__ wpk, int C,
                                                      int xcw, int pw) {
@@ -119,22 +74,6 @@ __device__ __forceinline__ Item decode(uint32_t i, const DwGeom& p) {
     return it;
 }
 
-template <int V> struct Words;
-template <> struct Words<1> { typedef uint32_t type; };
-template <> struct Words<4> { typedef uint4 type; };
-
-template <int V>
-__device__ __forceinline__ void load_words(const uint32_t* p, uint32_t (&w)[V]) {
-    const typename Words<V>::type v = *reinterpret_cast<const typename Words<V>::type*>(p);
-    __builtin_memcpy(w, &v, sizeof(v));
-}
-template <int V>
-__device__ __forceinline__ void store_words(uint32_t* p, const uint32_t (&w)[V]) {
-    typename Words<V>::type v;
-    __builtin_memcpy(&v, w, sizeof(v));
-    *reinterpret_cast<typename Words<V>::type*>(p) = v;
-}
-
 // the code of channel c of the packed pixel at `px`
 template <int XS>
 __device__ __forceinline__ int load_code(const uint32_t* __restrict__ px, int c) {
@@ -149,14 +88,6 @@ __device__ __forceinline__ int load_code(const uint32_t* __restrict__ px, int c)
     } else {
         return (int)(px[c >> 2] << (24 - 8 * (c & 3))) >> 24;
     }
-}
-
-// value behind the chain -> what a float32 output stores (k_conv_generic's order)
-__device__ __forceinline__ float act_value(float v, const EpiArgs& e) {
-    if (e.fn == QNN_FN_BINARY_TANH) return qnn_binary_tanh(v);
-    if (qnn_is_qact(e.fn)) return qnn_qact(e.fn, v, e.act_m);
-    if (e.fn == QNN_FN_LEAKY_RELU) return qnn_leaky_relu(v);
-    return v;
 }
 
 // ---- the plain form ---------------------------------------------------------------------------------------------------
@@ -335,14 +266,6 @@ __global__ __launch_bounds__(kBlock) void k_dw_pk16(const uint32_t* __restrict__
     }
 }
 
-const char* store_name(int store) {
-    return store == QNN_STORE_BIN  ? "bin"
-           : store == QNN_STORE_I4 ? "i4"
-           : store == QNN_STORE_I8 ? "i8"
-           : store == QNN_STORE_T2 ? "t2"
-                                   : "f32";
-}
-
 bool pk16_ok(const qnn_dw_weights* w, int x_bits) {
     if (w->M != 1 || w->kh != 3 || w->kw != 3 || w->dil_h != 1 || w->dil_w != 1 || w->stride != 1 || !w->d_wpk) return false;
     if (x_bits < 1 || x_bits > w->store) return false;
@@ -376,6 +299,18 @@ void out_hw(const qnn_dw_weights* w, int H, int W, DwGeom* g) {
     qnn_same_pad_dilated(W, w->kw, w->stride, w->dil_w, w->same_pad, &g->Wo, &g->pl);
 }
 
+// prepack: the operand image of k_dw_pk16, where the shape can take that form
+int pack_pairs(qnn_dw_weights* w, hipStream_t s) {
+    if ((w->store != QNN_STORE_I4 && w->store != QNN_STORE_I8) || w->M != 1 || w->kh != 3 || w->kw != 3 || w->dil_h != 1 ||
+        w->dil_w != 1)
+        return QNN_OK;
+    const int pw = qnn_per_word(w->store), pairs = 9 * w->xcw * (pw / 2);
+    QNN_SIDE_HIP(hipMalloc(&w->d_wpk, (size_t)pairs * sizeof(uint32_t)));
+    hipLaunchKernelGGL(k_dw_pairs, dim3((pairs + kBlock - 1) / kBlock), dim3(kBlock), 0, s, w->d_wcode, w->d_wpk, w->C, w->xcw,
+                       pw);
+    return QNN_OK;
+}
+
 }  // namespace
 
 extern "C" int qnn_depthwise_prepack(int wkind, int wbits, float H, const float* kernel, int kh, int kw, int C,
@@ -396,87 +331,32 @@ extern "C" int qnn_depthwise_prepack(int wkind, int wbits, float H, const float*
     QNN_REQUIRE(kh <= QNN_DW_MAX_WINDOW && kw <= QNN_DW_MAX_WINDOW, QNN_EUNSUPPORTED,
                 "%s: kernel %dx%d larger than %dx%d is not supported", who, kh, kw, QNN_DW_MAX_WINDOW, QNN_DW_MAX_WINDOW);
     QNN_REQUIRE((double)C * M * kh * kw < 1.0e9, QNN_EUNSUPPORTED, "%s: %d x %d channels", who, C, M);
-    QNN_REQUIRE(wkind == QNN_W_FLOAT || wkind == QNN_W_BINARY || wkind == QNN_W_QUANT || wkind == QNN_W_TERNARY,
-                QNN_EINVAL, "%s: wkind=%d not supported", who, wkind);
-    QNN_REQUIRE(H > 0.0f, QNN_EINVAL, "%s: H=%g", who, (double)H);
-    int wshift = 0;
-    float m = 1.0f;
-    if (wkind == QNN_W_QUANT) {
-        QNN_REQUIRE(wbits >= 2 && wbits <= 24, QNN_EINVAL, "%s: wbits=%d", who, wbits);
-        wshift = wbits - 1;
-        m = (float)(1u << wshift);
-    }
-    switch (store) {
-        case QNN_STORE_F32:
-            break;
-        case QNN_STORE_BIN:
-            QNN_REQUIRE(wkind == QNN_W_BINARY && H == 1.0f, QNN_EINVAL, "%s: BIN storage needs binary weights with H=1", who);
-            break;
-        case QNN_STORE_I4:
-        case QNN_STORE_I8:
-            QNN_REQUIRE(((wkind == QNN_W_BINARY || wkind == QNN_W_TERNARY) && H == 1.0f) ||
-                            (wkind == QNN_W_QUANT && wbits <= store),
-                        QNN_EINVAL, "%s: wkind=%d wbits=%d does not fit %d-bit storage", who, wkind, wbits, store);
-            break;
-        case QNN_STORE_T2:
-            QNN_REQUIRE((wkind == QNN_W_BINARY || wkind == QNN_W_TERNARY) && H == 1.0f, QNN_EINVAL,
-                        "%s: sign / mask storage needs ternary (or binary) weights with H=1", who);
-            break;
-        default:
-            qnn_set_error("%s: store=%d", who, store);
-            return QNN_EINVAL;
-    }
+    SideWeights common{};
+    int rc = qnn_side_weights_check(who, wkind, wbits, H, store, &common);
+    if (rc != QNN_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
     qnn_dw_weights* w = new (std::nothrow) qnn_dw_weights();
     QNN_REQUIRE(w, QNN_ENOMEM, "%s: host allocation failed", who);
-    *w = qnn_dw_weights{};
-    w->wkind = wkind; w->wbits = wbits; w->H = H;
+    *static_cast<SideWeights*>(w) = common;
     w->kh = kh; w->kw = kw; w->C = C; w->M = M; w->cout = C * M;
     w->stride = stride; w->same_pad = same_pad ? 1 : 0;
     w->dil_h = dil_h; w->dil_w = dil_w;
-    w->store = store; w->wshift = wshift;
     w->xcw = store == QNN_STORE_F32 ? 0 : qnn_words(store, C);
-    const int n = kh * kw * w->cout;
-#define DW_HIP(expr)                                                           \
-    do {                                                                       \
-        hipError_t _e = (expr);                                                \
-        if (_e != hipSuccess) {                                                \
-            qnn_set_error("%s failed: %s", #expr, hipGetErrorString(_e));      \
-            qnn_depthwise_free(w);                                             \
-            return _e == hipErrorOutOfMemory ? QNN_ENOMEM : QNN_EHIP;          \
-        }                                                                      \
-    } while (0)
-    DW_HIP(hipMalloc(&w->d_wq, (size_t)n * sizeof(float)));
-    if (store != QNN_STORE_F32) DW_HIP(hipMalloc(&w->d_wcode, (size_t)n * sizeof(int32_t)));
-    if (wkind == QNN_W_TERNARY) {
-        DW_HIP(hipMalloc(&w->d_aux, 16));
-        hipLaunchKernelGGL(k_dw_tern_cutoff, dim3(1), dim3(1024), 0, s, kernel, n, H, w->d_aux);
+    rc = qnn_side_quantize(w, kernel, kh * kw * w->cout, bias, w->cout, s);
+    if (rc == QNN_OK) rc = pack_pairs(w, s);
+    if (rc == QNN_OK) rc = qnn_side_hip(hipGetLastError(), "hipGetLastError()");
+    if (rc != QNN_OK) {
+        qnn_depthwise_free(w);
+        return rc;
     }
-    hipLaunchKernelGGL(k_dw_quantize, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, kernel, w->d_wq, w->d_wcode, n,
-                       wkind, H, m, (const float*)w->d_aux);
-    if (bias) {
-        DW_HIP(hipMalloc(&w->d_bias, (size_t)w->cout * sizeof(float)));
-        DW_HIP(hipMemcpyAsync(w->d_bias, bias, (size_t)w->cout * sizeof(float), hipMemcpyDeviceToDevice, s));
-    }
-    if ((store == QNN_STORE_I4 || store == QNN_STORE_I8) && M == 1 && kh == 3 && kw == 3 && dil_h == 1 && dil_w == 1) {
-        const int pw = qnn_per_word(store), pairs = 9 * w->xcw * (pw / 2);
-        DW_HIP(hipMalloc(&w->d_wpk, (size_t)pairs * sizeof(uint32_t)));
-        hipLaunchKernelGGL(k_dw_pairs, dim3((pairs + kBlock - 1) / kBlock), dim3(kBlock), 0, s, w->d_wcode, w->d_wpk, C,
-                           w->xcw, pw);
-    }
-    DW_HIP(hipGetLastError());
-#undef DW_HIP
     *out = w;
     return QNN_OK;
 }
 
 extern "C" int qnn_depthwise_free(qnn_dw_weights_t* w) {
     if (!w) return QNN_OK;
-    if (w->d_wq) (void)hipFree(w->d_wq);
-    if (w->d_wcode) (void)hipFree(w->d_wcode);
     if (w->d_wpk) (void)hipFree(w->d_wpk);
-    if (w->d_bias) (void)hipFree(w->d_bias);
-    if (w->d_aux) (void)hipFree(w->d_aux);
+    qnn_side_free(w);
     delete w;
     return QNN_OK;
 }
@@ -503,45 +383,11 @@ extern "C" int qnn_depthwise_forward(const qnn_dw_weights_t* w, const void* x, i
     const char* who = "qnn_depthwise_forward";
     QNN_REQUIRE(w && epi, QNN_EINVAL, "%s: null handle or epilogue", who);
     QNN_REQUIRE(N >= 0 && H > 0 && W > 0, QNN_EINVAL, "%s: N=%d H=%d W=%d", who, N, H, W);
-    QNN_REQUIRE(x_store != QNN_STORE_U8 && x_store != QNN_STORE_F32_IMAGE && x_store != QNN_STORE_F32_UNIT,
-                QNN_EUNSUPPORTED, "%s: x_store=%d (QNN_STORE_U8 and the typed float32 stores are first-layer inputs of "
-                "qnn_conv2d_forward)", who, x_store);
+    int xshift;
+    EpiArgs e;
+    int rc = qnn_side_forward_check(who, w, w->cout, x_store, x_bits, epi, "a depthwise layer", &xshift, &e);
+    if (rc != QNN_OK) return rc;
     const bool packed = x_store != QNN_STORE_F32;
-    int xshift = 0;
-    if (packed) {
-        QNN_REQUIRE(x_store == QNN_STORE_BIN || x_store == QNN_STORE_T2 || x_store == QNN_STORE_I4 || x_store == QNN_STORE_I8,
-                    QNN_EINVAL, "%s: x_store=%d", who, x_store);
-        QNN_REQUIRE(x_store == w->store, QNN_EINVAL, "%s: x_store=%d but the weights were prepacked for store=%d", who,
-                    x_store, w->store);
-        if (x_store == QNN_STORE_I4 || x_store == QNN_STORE_I8) {
-            QNN_REQUIRE(x_bits >= 1 && x_bits <= x_store, QNN_EINVAL, "%s: x_bits=%d does not fit %d-bit storage", who,
-                        x_bits, x_store);
-            xshift = x_bits - 1;
-        }
-    }
-    // ---- the epilogue subset ----
-    QNN_REQUIRE(epi->pool == 1, QNN_EUNSUPPORTED, "%s: epilogue field pool=%d (no pooling behind a depthwise layer)", who,
-                epi->pool);
-    QNN_REQUIRE(!epi->res, QNN_EUNSUPPORTED, "%s: epilogue field res (no residual input)", who);
-    QNN_REQUIRE(!epi->fold, QNN_EUNSUPPORTED, "%s: epilogue field fold (no folded epilogue)", who);
-    QNN_REQUIRE(!epi->proj, QNN_EUNSUPPORTED, "%s: epilogue field proj (no in-launch projection)", who);
-    QNN_REQUIRE(epi->trick_s == 0.0f, QNN_EUNSUPPORTED, "%s: epilogue field trick_s=%g (no identity trick)", who,
-                (double)epi->trick_s);
-    QNN_REQUIRE(epi->flags == 0u, QNN_EUNSUPPORTED, "%s: epilogue field flags=%u (no kernel-selection bits)", who, epi->flags);
-    QNN_REQUIRE((epi->bn_inv == nullptr) == (epi->bn_shift == nullptr), QNN_EINVAL,
-                "%s: bn_inv and bn_shift must both be set or both be NULL", who);
-    QNN_REFUSE_MAXACT(epi->fn, who);
-    const int fn = epi->fn, os = epi->out_store;
-    QNN_REQUIRE(fn == QNN_FN_NONE || fn == QNN_FN_BINARY_TANH || qnn_is_qact(fn) || fn == QNN_FN_LEAKY_RELU, QNN_EINVAL,
-                "%s: fn=%d cannot be fused", who, fn);
-    QNN_REQUIRE(fn != QNN_FN_LEAKY_RELU || os == QNN_STORE_F32, QNN_EINVAL, "%s: leaky_relu needs a float32 output", who);
-    if (qnn_is_qact(fn)) QNN_REQUIRE(epi->act_bits >= 2 && epi->act_bits <= 24, QNN_EINVAL, "%s: act_bits=%d", who, epi->act_bits);
-    QNN_REQUIRE(os == QNN_STORE_F32 || os == QNN_STORE_BIN || os == QNN_STORE_I4 || os == QNN_STORE_I8, QNN_EINVAL,
-                "%s: out_store=%d", who, os);
-    QNN_REQUIRE(os != QNN_STORE_BIN || fn == QNN_FN_BINARY_TANH, QNN_EINVAL, "%s: BIN output needs fn=binary_tanh", who);
-    QNN_REQUIRE(!(os == QNN_STORE_I4 || os == QNN_STORE_I8) || fn == QNN_FN_BINARY_TANH ||
-                    (qnn_is_qact(fn) && epi->act_bits <= os),
-                QNN_EINVAL, "%s: fn=%d act_bits=%d does not fit %d-bit output", who, fn, epi->act_bits, os);
     // ---- geometry ----
     DwGeom g;
     out_hw(w, H, W, &g);
@@ -550,28 +396,13 @@ extern "C" int qnn_depthwise_forward(const qnn_dw_weights_t* w, const void* x, i
     g.H = H; g.W = W; g.C = w->C; g.M = w->M; g.cout = w->cout;
     g.kh = w->kh; g.kw = w->kw; g.stride = w->stride; g.dil_h = w->dil_h; g.dil_w = w->dil_w;
     g.xcw = packed ? w->xcw : w->C;
-    g.ocw = os == QNN_STORE_F32 ? w->cout : qnn_words(os, w->cout);
-    const size_t owords = (size_t)N * g.Ho * g.Wo * (size_t)g.ocw;
-    QNN_REQUIRE(owords < ((size_t)1 << 31), QNN_EUNSUPPORTED, "%s: %zu output words (2^31 or more)", who, owords);
-    if (N == 0) return QNN_OK;
-    QNN_REQUIRE(x && y, QNN_EINVAL, "%s: null pointer", who);
-    const size_t xbytes = (size_t)N * H * W * g.xcw * 4, ybytes = owords * 4;
-    const uintptr_t xa = (uintptr_t)x, ya = (uintptr_t)y;
-    QNN_REQUIRE(xa + xbytes <= ya || ya + ybytes <= xa, QNN_EINVAL, "%s: x and y overlap", who);
+    g.ocw = e.ocw;
+    bool run;
+    rc = qnn_side_io_check(who, N, (size_t)N * g.Ho * g.Wo * (size_t)g.ocw, x, (size_t)N * H * W * g.xcw * 4, y, &run);
+    if (!run) return rc;
 
-    EpiArgs e{};
-    e.bias = w->d_bias;
-    e.bn_inv = epi->bn_inv;
-    e.bn_shift = epi->bn_shift;
-    e.scale = packed ? ldexpf(1.0f, -(w->wshift + xshift)) : 1.0f;
-    e.act_m = qnn_is_qact(fn) ? (float)(1u << (epi->act_bits - 1)) : 1.0f;
-    e.fn = fn;
-    e.out_store = os;
-    e.ocw = g.ocw;
-    e.post_scale = 1.0f;
-
-    const bool fast = packed && os == x_store && pk16_ok(w, x_bits);
-    const bool aligned = xa % 16 == 0 && ya % 16 == 0;
+    const bool fast = packed && e.out_store == x_store && pk16_ok(w, x_bits);
+    const bool aligned = (uintptr_t)x % 16 == 0 && (uintptr_t)y % 16 == 0;
     // the 16-bit-lane form: one word per lane and kRows output rows per item; the plain form: V words of one pixel
     const bool v4 = !fast && aligned && g.ocw % 4 == 0;
     g.groups = fast ? g.ocw : v4 ? g.ocw / 4 : g.ocw;
@@ -583,17 +414,12 @@ extern "C" int qnn_depthwise_forward(const qnn_dw_weights_t* w, const void* x, i
     const uint32_t total = (uint32_t)((size_t)N * yblocks * g.Wo * (size_t)g.groups);
     hipStream_t s = (hipStream_t)stream;
     if (fast) {
-        if (x_store == QNN_STORE_I4) launch_pk16<QNN_STORE_I4>(fn, x, w, y, g, e, total, s);
-        else launch_pk16<QNN_STORE_I8>(fn, x, w, y, g, e, total, s);
-    } else if (x_store == QNN_STORE_F32) launch_plain<QNN_STORE_F32>(v4, x, w, y, g, e, total, s);
-    else if (x_store == QNN_STORE_BIN) launch_plain<QNN_STORE_BIN>(v4, x, w, y, g, e, total, s);
-    else if (x_store == QNN_STORE_T2) launch_plain<QNN_STORE_T2>(v4, x, w, y, g, e, total, s);
-    else if (x_store == QNN_STORE_I4) launch_plain<QNN_STORE_I4>(v4, x, w, y, g, e, total, s);
-    else launch_plain<QNN_STORE_I8>(v4, x, w, y, g, e, total, s);
+        if (x_store == QNN_STORE_I4) launch_pk16<QNN_STORE_I4>(e.fn, x, w, y, g, e, total, s);
+        else launch_pk16<QNN_STORE_I8>(e.fn, x, w, y, g, e, total, s);
+    } else {
+        qnn_side_for_store(x_store, [&](auto xs) { launch_plain<decltype(xs)::value>(v4, x, w, y, g, e, total, s); });
+    }
     QNN_HIP(hipGetLastError());
-    char name[40];
-    const bool has_fast = x_store == QNN_STORE_I4 || x_store == QNN_STORE_I8;
-    snprintf(name, sizeof(name), "depthwise_%s%s", store_name(x_store), has_fast && !fast ? "_plain" : "");
-    qnn_set_kernel_name(name);
+    qnn_side_kernel_name("depthwise", x_store, fast ? "" : "_plain");
     return QNN_OK;
 }

@@ -25,30 +25,20 @@
 // pixel groups (one cross-lane move per pair of groups) and every lane stores one whole word.  No LDS, no scratch.
 //
 // Index arithmetic in 32 bits by multiply-high (the entry refuses 2^31 output words), tensor offsets in 64 bits.
-#include <stdio.h>
-
 #include <new>
 
+#include "qnn_sideconv.h"
 #include "qnn_strip_device.h"
 #include "qnn_abi_gconv.h"
 #include "qnn_gconv_plan.h"
 
-struct qnn_gconv_weights {
-    int wkind, wbits;
-    float H;
+struct qnn_gconv_weights : SideWeights {   // d_wq, d_wcode: [kh*kw][Cg][cout], Keras' (kh, kw, Cin / g, Cout) order
     int kh, kw, cin, cout, groups, Cg, Fg;
     int stride, same_pad, dil_h, dil_w;
-    int store;
-    int wshift;              // quantized value = code * 2^-wshift
-    int xcw;                 // words per input pixel on the handle's packed store (F32: 0)
     int gw;                  // words of an input pixel that one group can touch (the most over the groups)
-    float* d_wq;             // [kh*kw][Cg][cout] quantized values: Keras' (kh, kw, Cin / g, Cout) order
-    int32_t* d_wcode;        // the same order, integer codes (packed stores) or nullptr
     uint32_t* d_wpk;         // [kh*kw][cout][gw] the filter's codes in the word layout of an input pixel, or nullptr
     uint8_t* d_wm;           // matrix-pipe image [tile][K-step][lane 64][16 bytes], or nullptr
     int2* d_slots;           // matrix-pipe slot table [K-step][kq 4]: {dy | dx << 16, byte offset in the run or -1}
-    float* d_bias;           // [cout] or nullptr
-    float* d_aux;            // ternary: the cutoff (1 float), else nullptr
 };
 
 namespace {
@@ -57,40 +47,6 @@ constexpr int kBlock = 256;
 constexpr int kPG = 4;       // 16-pixel groups a wave of k_gc_mfma takes per filter load (even: int4 pairs them)
 
 // ---- weights ----------------------------------------------------------------------------------------------------------
-// ternary_ops.py:15-30: cutoff = 0.7 * mean(|W / H|) over the whole kernel.  One block, fixed order, float64 sums.
-__global__ __launch_bounds__(1024) void k_gc_tern_cutoff(const float* __restrict__ kernel, int n, float H,
-                                                         float* __restrict__ cutoff) {
-    __shared__ double part[1024];
-    double s = 0.0;
-    for (int i = threadIdx.x; i < n; i += 1024) s += (double)fabsf(__fdiv_rn(kernel[i], H));
-    part[threadIdx.x] = s;
-    __syncthreads();
-    for (int off = 512; off > 0; off >>= 1) {
-        if ((int)threadIdx.x < off) part[threadIdx.x] += part[threadIdx.x + off];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) cutoff[0] = __fmul_rn(0.7f, (float)(part[0] / (double)n));
-}
-
-// binarize (binary_ops.py:54-64), quantize (quantized_ops.py:49-66), ternarize (ternary_ops.py:21-41), elementwise; the
-// codes are value * 2^wshift (binary / ternary on a packed store have H = 1: the value itself)
-__global__ __launch_bounds__(kBlock) void k_gc_quantize(const float* __restrict__ kernel, float* __restrict__ wq,
-                                                        int32_t* __restrict__ wcode, int n, int wkind, float H, float m,
-                                                        const float* __restrict__ cutoff_p) {
-    const int i = blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
-    const float w = kernel[i];
-    float q = w;
-    if (wkind == QNN_W_BINARY) q = __fmul_rn(H, qnn_binary_tanh(__fdiv_rn(w, H)));
-    else if (wkind == QNN_W_QUANT) q = qnn_quantized_tanh(w, m);
-    else if (wkind == QNN_W_TERNARY) {
-        const float u = __fdiv_rn(w, H), cutoff = cutoff_p[0];
-        q = __fmul_rn(u > cutoff ? 1.0f : (u <= -cutoff ? -1.0f : 0.0f), H);
-    }
-    wq[i] = q;
-    if (wcode) wcode[i] = (int)__fmul_rn(q, m);
-}
-
 // channels per word unit of a packed store and words per unit (T2: 32 channels in a (mask, sign) pair)
 __host__ __device__ inline int gc_unit_channels(int store) { return store == QNN_STORE_T2 ? 32 : qnn_per_word(store); }
 __host__ __device__ inline int gc_unit_words(int store) { return store == QNN_STORE_T2 ? 2 : 1; }
@@ -125,17 +81,9 @@ __global__ __launch_bounds__(kBlock) void k_gc_pack_words(const int32_t* __restr
     wpk[i] = word;
 }
 
-// the channel (0 .. 15 of the lane's 16) that byte j of a B operand carries: in order for int8; for int4 the order
-// strip_widen leaves (even nibbles of a word, then odd ones)
-__host__ __device__ inline int tc_operand_channel(int store, int j) {
-    if (store == QNN_STORE_I8) return j;
-    const int wd = j >> 2, b = j & 3;
-    return (wd >> 1) * 8 + 2 * b + (wd & 1);
-}
-
 // One byte per thread of the image [tile][K-step][lane][16]: lane (r = lane & 15, kq = lane >> 4) of K-step k holds slot
 // 4 k + kq = (tap, chunk) of filter 16 tile + r: the weight code (int8) at channel c0(tile) + 16 chunk +
-// tc_operand_channel(j) where that channel lies in the filter's group; zero elsewhere and in a padding slot.
+// qnn_operand_channel(j) where that channel lies in the filter's group; zero elsewhere and in a padding slot.
 __global__ __launch_bounds__(kBlock) void k_gc_mfma_image(const int32_t* __restrict__ wcode, uint8_t* __restrict__ wm,
                                                           const GcPlan p, int cout, int store, uint32_t total) {
     const uint32_t i = blockIdx.x * (uint32_t)kBlock + threadIdx.x;
@@ -148,7 +96,7 @@ __global__ __launch_bounds__(kBlock) void k_gc_mfma_image(const int32_t* __restr
     int tap, chunk, code = 0;
     if (qnn_gc_slot(&p, 4 * step + kq, &tap, &chunk)) {
         const int f = 16 * tile + r;
-        const int c = qnn_gc_tile_channel(&p, tile) + 16 * chunk + tc_operand_channel(store, j) - (f / p.Fg) * p.Cg;
+        const int c = qnn_gc_tile_channel(&p, tile) + 16 * chunk + qnn_operand_channel(store, j) - (f / p.Fg) * p.Cg;
         if (c >= 0 && c < p.Cg) code = wcode[((size_t)tap * p.Cg + c) * cout + f];
     }
     wm[i] = (uint8_t)(int8_t)code;
@@ -180,17 +128,6 @@ struct GcGeom {
     FastDiv fd_g, fd_wo, fd_ho, fd_fg;
 };
 
-template <int V> struct Words;
-template <> struct Words<1> { typedef uint32_t type; };
-template <> struct Words<4> { typedef uint4 type; };
-
-template <int V>
-__device__ __forceinline__ void store_words(uint32_t* p, const uint32_t (&w)[V]) {
-    typename Words<V>::type v;
-    __builtin_memcpy(&v, w, sizeof(v));
-    *reinterpret_cast<typename Words<V>::type*>(p) = v;
-}
-
 // sum over the channels [clo, clo + Cg) of one packed pixel: `px` points at the group's first word (index w0 of the
 // pixel), `wr` at the filter's nw words (zero outside the group)
 template <int XS>
@@ -212,14 +149,6 @@ __device__ __forceinline__ int dot_group(const uint32_t* __restrict__ px, const 
         for (int wi = 0; wi < nw; ++wi) acc = qnn_dot<XS>(px[wi], wr[wi], acc);
     }
     return acc;
-}
-
-// value behind the chain -> what a float32 output stores (k_conv_generic's order)
-__device__ __forceinline__ float act_value(float v, const EpiArgs& e) {
-    if (e.fn == QNN_FN_BINARY_TANH) return qnn_binary_tanh(v);
-    if (qnn_is_qact(e.fn)) return qnn_qact(e.fn, v, e.act_m);
-    if (e.fn == QNN_FN_LEAKY_RELU) return qnn_leaky_relu(v);
-    return v;
 }
 
 // ---- the plain form ---------------------------------------------------------------------------------------------------
@@ -405,14 +334,6 @@ __global__ __launch_bounds__(kBlock) void k_gc_mfma(const uint8_t* __restrict__ 
     }
 }
 
-const char* store_name(int store) {
-    return store == QNN_STORE_BIN  ? "bin"
-           : store == QNN_STORE_I4 ? "i4"
-           : store == QNN_STORE_I8 ? "i8"
-           : store == QNN_STORE_T2 ? "t2"
-                                   : "f32";
-}
-
 template <int XS>
 void launch_plain(bool v4, const void* x, const qnn_gconv_weights* w, void* y, const GcGeom& g, const EpiArgs& e,
                   uint32_t total, hipStream_t s) {
@@ -424,6 +345,28 @@ void launch_plain(bool v4, const void* x, const qnn_gconv_weights* w, void* y, c
 void out_hw(const qnn_gconv_weights* w, int H, int W, GcGeom* g) {
     qnn_same_pad_dilated(H, w->kh, w->stride, w->dil_h, w->same_pad, &g->Ho, &g->pt);
     qnn_same_pad_dilated(W, w->kw, w->stride, w->dil_w, w->same_pad, &g->Wo, &g->pl);
+}
+
+// prepack: the filter rows of the plain form on a packed store, and the operand image and slot table where the shape takes
+// the matrix pipe
+int pack_images(qnn_gconv_weights* w, hipStream_t s) {
+    if (w->store != QNN_STORE_F32) {
+        const int rows = w->kh * w->kw * w->cout, nw = rows * w->gw;      // below 2^31: checked with gw by the entry
+        QNN_SIDE_HIP(hipMalloc(&w->d_wpk, (size_t)nw * sizeof(uint32_t)));
+        hipLaunchKernelGGL(k_gc_pack_words, dim3((nw + kBlock - 1) / kBlock), dim3(kBlock), 0, s, w->d_wcode, w->d_wpk, rows,
+                           w->cout, w->Cg, w->Fg, w->gw, w->store);
+    }
+    GcPlan plan;
+    if (qnn_gc_mfma_ok(&plan, w->store, w->store, w->store, w->kh, w->kw, w->cin, w->cout, w->groups, 0, 0, 0)) {
+        const size_t total = (size_t)plan.tiles * plan.steps * 64 * 16;      // below 2^31: qnn_gc_plan
+        QNN_SIDE_HIP(hipMalloc(&w->d_wm, total));
+        QNN_SIDE_HIP(hipMalloc(&w->d_slots, (size_t)plan.steps * 4 * sizeof(int2)));
+        hipLaunchKernelGGL(k_gc_mfma_image, dim3((uint32_t)((total + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, w->d_wcode,
+                           w->d_wm, plan, w->cout, w->store, (uint32_t)total);
+        hipLaunchKernelGGL(k_gc_slot_table, dim3((plan.steps * 4 + kBlock - 1) / kBlock), dim3(kBlock), 0, s, w->d_slots, plan,
+                           w->kw, w->dil_h, w->dil_w, w->store == QNN_STORE_I4 ? 8 : 16);
+    }
+    return QNN_OK;
 }
 
 }  // namespace
@@ -450,45 +393,16 @@ extern "C" int qnn_gconv_prepack(int wkind, int wbits, float H, const float* ker
     const int Cg = Cin / groups, Fg = Cout / groups;
     QNN_REQUIRE((double)Cout * Cg * kh * kw < 1073741824.0, QNN_EUNSUPPORTED,
                 "%s: the kernel has kh * kw * (Cin / groups) * Cout = %.0f values (2^30 or more)", who, (double)Cout * Cg * kh * kw);
-    QNN_REQUIRE(wkind == QNN_W_FLOAT || wkind == QNN_W_BINARY || wkind == QNN_W_QUANT || wkind == QNN_W_TERNARY,
-                QNN_EINVAL, "%s: wkind=%d not supported", who, wkind);
-    QNN_REQUIRE(H > 0.0f, QNN_EINVAL, "%s: H=%g", who, (double)H);
-    int wshift = 0;
-    float m = 1.0f;
-    if (wkind == QNN_W_QUANT) {
-        QNN_REQUIRE(wbits >= 2 && wbits <= 24, QNN_EINVAL, "%s: wbits=%d", who, wbits);
-        wshift = wbits - 1;
-        m = (float)(1u << wshift);
-    }
-    switch (store) {
-        case QNN_STORE_F32:
-            break;
-        case QNN_STORE_BIN:
-            QNN_REQUIRE(wkind == QNN_W_BINARY && H == 1.0f, QNN_EINVAL, "%s: BIN storage needs binary weights with H=1", who);
-            break;
-        case QNN_STORE_I4:
-        case QNN_STORE_I8:
-            QNN_REQUIRE(((wkind == QNN_W_BINARY || wkind == QNN_W_TERNARY) && H == 1.0f) ||
-                            (wkind == QNN_W_QUANT && wbits <= store),
-                        QNN_EINVAL, "%s: wkind=%d wbits=%d does not fit %d-bit storage", who, wkind, wbits, store);
-            break;
-        case QNN_STORE_T2:
-            QNN_REQUIRE((wkind == QNN_W_BINARY || wkind == QNN_W_TERNARY) && H == 1.0f, QNN_EINVAL,
-                        "%s: sign / mask storage needs ternary (or binary) weights with H=1", who);
-            break;
-        default:
-            qnn_set_error("%s: store=%d", who, store);
-            return QNN_EINVAL;
-    }
+    SideWeights common{};
+    int rc = qnn_side_weights_check(who, wkind, wbits, H, store, &common);
+    if (rc != QNN_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
     qnn_gconv_weights* w = new (std::nothrow) qnn_gconv_weights();
     QNN_REQUIRE(w, QNN_ENOMEM, "%s: host allocation failed", who);
-    *w = qnn_gconv_weights{};
-    w->wkind = wkind; w->wbits = wbits; w->H = H;
+    *static_cast<SideWeights*>(w) = common;
     w->kh = kh; w->kw = kw; w->cin = Cin; w->cout = Cout; w->groups = groups; w->Cg = Cg; w->Fg = Fg;
     w->stride = stride; w->same_pad = same_pad ? 1 : 0;
     w->dil_h = dil_h; w->dil_w = dil_w;
-    w->store = store; w->wshift = wshift;
     if (store != QNN_STORE_F32) {
         w->xcw = qnn_words(store, Cin);
         // the most words of a pixel one group touches: the span from its first channel's word to its last channel's
@@ -504,59 +418,23 @@ extern "C" int qnn_gconv_prepack(int wkind, int wbits, float H, const float* ker
             return QNN_EUNSUPPORTED;
         }
     }
-    const int n = kh * kw * Cg * Cout;
-#define GC_HIP(expr)                                                           \
-    do {                                                                       \
-        hipError_t _e = (expr);                                                \
-        if (_e != hipSuccess) {                                                \
-            qnn_set_error("%s failed: %s", #expr, hipGetErrorString(_e));      \
-            qnn_gconv_free(w);                                                 \
-            return _e == hipErrorOutOfMemory ? QNN_ENOMEM : QNN_EHIP;          \
-        }                                                                      \
-    } while (0)
-    GC_HIP(hipMalloc(&w->d_wq, (size_t)n * sizeof(float)));
-    if (store != QNN_STORE_F32) GC_HIP(hipMalloc(&w->d_wcode, (size_t)n * sizeof(int32_t)));
-    if (wkind == QNN_W_TERNARY) {
-        GC_HIP(hipMalloc(&w->d_aux, 16));
-        hipLaunchKernelGGL(k_gc_tern_cutoff, dim3(1), dim3(1024), 0, s, kernel, n, H, w->d_aux);
+    rc = qnn_side_quantize(w, kernel, kh * kw * Cg * Cout, bias, Cout, s);
+    if (rc == QNN_OK) rc = pack_images(w, s);
+    if (rc == QNN_OK) rc = qnn_side_hip(hipGetLastError(), "hipGetLastError()");
+    if (rc != QNN_OK) {
+        qnn_gconv_free(w);
+        return rc;
     }
-    hipLaunchKernelGGL(k_gc_quantize, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, kernel, w->d_wq, w->d_wcode, n,
-                       wkind, H, m, (const float*)w->d_aux);
-    if (bias) {
-        GC_HIP(hipMalloc(&w->d_bias, (size_t)Cout * sizeof(float)));
-        GC_HIP(hipMemcpyAsync(w->d_bias, bias, (size_t)Cout * sizeof(float), hipMemcpyDeviceToDevice, s));
-    }
-    if (store != QNN_STORE_F32) {
-        const int rows = kh * kw * Cout, nw = rows * w->gw;      // below 2^31: checked with gw above
-        GC_HIP(hipMalloc(&w->d_wpk, (size_t)nw * sizeof(uint32_t)));
-        hipLaunchKernelGGL(k_gc_pack_words, dim3((nw + kBlock - 1) / kBlock), dim3(kBlock), 0, s, w->d_wcode, w->d_wpk, rows,
-                           Cout, Cg, Fg, w->gw, store);
-    }
-    GcPlan plan;
-    if (qnn_gc_mfma_ok(&plan, store, store, store, kh, kw, Cin, Cout, groups, 0, 0, 0)) {
-        const size_t total = (size_t)plan.tiles * plan.steps * 64 * 16;      // below 2^31: qnn_gc_plan
-        GC_HIP(hipMalloc(&w->d_wm, total));
-        GC_HIP(hipMalloc(&w->d_slots, (size_t)plan.steps * 4 * sizeof(int2)));
-        hipLaunchKernelGGL(k_gc_mfma_image, dim3((uint32_t)((total + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, w->d_wcode,
-                           w->d_wm, plan, Cout, store, (uint32_t)total);
-        hipLaunchKernelGGL(k_gc_slot_table, dim3((plan.steps * 4 + kBlock - 1) / kBlock), dim3(kBlock), 0, s, w->d_slots, plan,
-                           kw, dil_h, dil_w, store == QNN_STORE_I4 ? 8 : 16);
-    }
-    GC_HIP(hipGetLastError());
-#undef GC_HIP
     *out = w;
     return QNN_OK;
 }
 
 extern "C" int qnn_gconv_free(qnn_gconv_weights_t* w) {
     if (!w) return QNN_OK;
-    if (w->d_wq) (void)hipFree(w->d_wq);
-    if (w->d_wcode) (void)hipFree(w->d_wcode);
     if (w->d_wpk) (void)hipFree(w->d_wpk);
     if (w->d_wm) (void)hipFree(w->d_wm);
     if (w->d_slots) (void)hipFree(w->d_slots);
-    if (w->d_bias) (void)hipFree(w->d_bias);
-    if (w->d_aux) (void)hipFree(w->d_aux);
+    qnn_side_free(w);
     delete w;
     return QNN_OK;
 }
@@ -584,45 +462,11 @@ extern "C" int qnn_gconv_forward(const qnn_gconv_weights_t* w, const void* x, in
     const char* who = "qnn_gconv_forward";
     QNN_REQUIRE(w && epi, QNN_EINVAL, "%s: null handle or epilogue", who);
     QNN_REQUIRE(N >= 0 && H > 0 && W > 0 && H < (1 << 26) && W < (1 << 26), QNN_EINVAL, "%s: N=%d H=%d W=%d", who, N, H, W);
-    QNN_REQUIRE(x_store != QNN_STORE_U8 && x_store != QNN_STORE_F32_IMAGE && x_store != QNN_STORE_F32_UNIT,
-                QNN_EUNSUPPORTED, "%s: x_store=%d (QNN_STORE_U8 and the typed float32 stores are first-layer inputs of "
-                "qnn_conv2d_forward)", who, x_store);
+    int xshift;
+    EpiArgs e;
+    int rc = qnn_side_forward_check(who, w, w->cout, x_store, x_bits, epi, "a grouped convolution", &xshift, &e);
+    if (rc != QNN_OK) return rc;
     const bool packed = x_store != QNN_STORE_F32;
-    int xshift = 0;
-    if (packed) {
-        QNN_REQUIRE(x_store == QNN_STORE_BIN || x_store == QNN_STORE_T2 || x_store == QNN_STORE_I4 || x_store == QNN_STORE_I8,
-                    QNN_EINVAL, "%s: x_store=%d", who, x_store);
-        QNN_REQUIRE(x_store == w->store, QNN_EINVAL, "%s: x_store=%d but the weights were prepacked for store=%d", who,
-                    x_store, w->store);
-        if (x_store == QNN_STORE_I4 || x_store == QNN_STORE_I8) {
-            QNN_REQUIRE(x_bits >= 1 && x_bits <= x_store, QNN_EINVAL, "%s: x_bits=%d does not fit %d-bit storage", who,
-                        x_bits, x_store);
-            xshift = x_bits - 1;
-        }
-    }
-    // ---- the epilogue subset ----
-    QNN_REQUIRE(epi->pool == 1, QNN_EUNSUPPORTED, "%s: epilogue field pool=%d (no pooling behind a grouped convolution)", who,
-                epi->pool);
-    QNN_REQUIRE(!epi->res, QNN_EUNSUPPORTED, "%s: epilogue field res (no residual input)", who);
-    QNN_REQUIRE(!epi->fold, QNN_EUNSUPPORTED, "%s: epilogue field fold (no folded epilogue)", who);
-    QNN_REQUIRE(!epi->proj, QNN_EUNSUPPORTED, "%s: epilogue field proj (no in-launch projection)", who);
-    QNN_REQUIRE(epi->trick_s == 0.0f, QNN_EUNSUPPORTED, "%s: epilogue field trick_s=%g (no identity trick)", who,
-                (double)epi->trick_s);
-    QNN_REQUIRE(epi->flags == 0u, QNN_EUNSUPPORTED, "%s: epilogue field flags=%u (no kernel-selection bits)", who, epi->flags);
-    QNN_REQUIRE((epi->bn_inv == nullptr) == (epi->bn_shift == nullptr), QNN_EINVAL,
-                "%s: bn_inv and bn_shift must both be set or both be NULL", who);
-    QNN_REFUSE_MAXACT(epi->fn, who);
-    const int fn = epi->fn, os = epi->out_store;
-    QNN_REQUIRE(fn == QNN_FN_NONE || fn == QNN_FN_BINARY_TANH || qnn_is_qact(fn) || fn == QNN_FN_LEAKY_RELU, QNN_EINVAL,
-                "%s: fn=%d cannot be fused", who, fn);
-    QNN_REQUIRE(fn != QNN_FN_LEAKY_RELU || os == QNN_STORE_F32, QNN_EINVAL, "%s: leaky_relu needs a float32 output", who);
-    if (qnn_is_qact(fn)) QNN_REQUIRE(epi->act_bits >= 2 && epi->act_bits <= 24, QNN_EINVAL, "%s: act_bits=%d", who, epi->act_bits);
-    QNN_REQUIRE(os == QNN_STORE_F32 || os == QNN_STORE_BIN || os == QNN_STORE_I4 || os == QNN_STORE_I8, QNN_EINVAL,
-                "%s: out_store=%d", who, os);
-    QNN_REQUIRE(os != QNN_STORE_BIN || fn == QNN_FN_BINARY_TANH, QNN_EINVAL, "%s: BIN output needs fn=binary_tanh", who);
-    QNN_REQUIRE(!(os == QNN_STORE_I4 || os == QNN_STORE_I8) || fn == QNN_FN_BINARY_TANH ||
-                    (qnn_is_qact(fn) && epi->act_bits <= os),
-                QNN_EINVAL, "%s: fn=%d act_bits=%d does not fit %d-bit output", who, fn, epi->act_bits, os);
     // ---- the int32 bound: kh * kw * Cg (tap, channel) pairs, each at most 2^(x_bits-1) * 2^wshift ----
     if (packed) {
         const double worst = (double)w->kh * w->kw * w->Cg * (double)(1u << xshift) * (double)(1u << w->wshift);
@@ -638,31 +482,17 @@ extern "C" int qnn_gconv_forward(const qnn_gconv_weights_t* w, const void* x, in
     g.kh = w->kh; g.kw = w->kw; g.stride = w->stride; g.dil_h = w->dil_h; g.dil_w = w->dil_w;
     g.xcw = packed ? w->xcw : w->cin;
     g.gw = w->gw;
-    g.ocw = os == QNN_STORE_F32 ? w->cout : qnn_words(os, w->cout);
-    const size_t owords = (size_t)N * g.Ho * g.Wo * (size_t)g.ocw;
-    QNN_REQUIRE(owords < ((size_t)1 << 31), QNN_EUNSUPPORTED, "%s: %zu output words (2^31 or more)", who, owords);
-    if (N == 0) return QNN_OK;
-    QNN_REQUIRE(x && y, QNN_EINVAL, "%s: null pointer", who);
-    const size_t xbytes = (size_t)N * H * W * g.xcw * 4, ybytes = owords * 4;
-    const uintptr_t xa = (uintptr_t)x, ya = (uintptr_t)y;
-    QNN_REQUIRE(xa + xbytes <= ya || ya + ybytes <= xa, QNN_EINVAL, "%s: x and y overlap", who);
-
-    EpiArgs e{};
-    e.bias = w->d_bias;
-    e.bn_inv = epi->bn_inv;
-    e.bn_shift = epi->bn_shift;
-    e.scale = packed ? ldexpf(1.0f, -(w->wshift + xshift)) : 1.0f;
-    e.act_m = qnn_is_qact(fn) ? (float)(1u << (epi->act_bits - 1)) : 1.0f;
-    e.fn = fn;
-    e.out_store = os;
-    e.ocw = g.ocw;
-    e.post_scale = 1.0f;
+    g.ocw = e.ocw;
+    bool run;
+    rc = qnn_side_io_check(who, N, (size_t)N * g.Ho * g.Wo * (size_t)g.ocw, x, (size_t)N * H * W * g.xcw * 4, y, &run);
+    if (!run) return rc;
 
     hipStream_t s = (hipStream_t)stream;
     GcPlan plan;
     const size_t img_bytes = (size_t)H * W * g.xcw * 4;
-    const bool fast = packed && w->d_wm &&
-                      qnn_gc_mfma_ok(&plan, w->store, x_store, os, w->kh, w->kw, w->cin, w->cout, w->groups, xa, ya, img_bytes);
+    const uintptr_t xa = (uintptr_t)x, ya = (uintptr_t)y;
+    const bool fast = packed && w->d_wm && qnn_gc_mfma_ok(&plan, w->store, x_store, e.out_store, w->kh, w->kw, w->cin, w->cout,
+                                                          w->groups, xa, ya, img_bytes);
     if (fast) {
         GcMfma p{};
         p.H = H; p.W = W; p.Ho = g.Ho; p.Wo = g.Wo;
@@ -693,16 +523,9 @@ extern "C" int qnn_gconv_forward(const qnn_gconv_weights_t* w, const void* x, in
         g.fd_ho = qnn_fastdiv((uint32_t)g.Ho);
         g.fd_fg = qnn_fastdiv((uint32_t)g.Fg);
         const uint32_t total = (uint32_t)((size_t)N * g.Ho * g.Wo * (size_t)g.groups);
-        if (x_store == QNN_STORE_F32) launch_plain<QNN_STORE_F32>(v4, x, w, y, g, e, total, s);
-        else if (x_store == QNN_STORE_BIN) launch_plain<QNN_STORE_BIN>(v4, x, w, y, g, e, total, s);
-        else if (x_store == QNN_STORE_T2) launch_plain<QNN_STORE_T2>(v4, x, w, y, g, e, total, s);
-        else if (x_store == QNN_STORE_I4) launch_plain<QNN_STORE_I4>(v4, x, w, y, g, e, total, s);
-        else launch_plain<QNN_STORE_I8>(v4, x, w, y, g, e, total, s);
+        qnn_side_for_store(x_store, [&](auto xs) { launch_plain<decltype(xs)::value>(v4, x, w, y, g, e, total, s); });
     }
     QNN_HIP(hipGetLastError());
-    char name[40];
-    const bool has_fast = x_store == QNN_STORE_I4 || x_store == QNN_STORE_I8;
-    snprintf(name, sizeof(name), "gconv_%s%s", store_name(x_store), fast ? "_mfma" : has_fast ? "_plain" : "");
-    qnn_set_kernel_name(name);
+    qnn_side_kernel_name("gconv", x_store, fast ? "_mfma" : "_plain");
     return QNN_OK;
 }

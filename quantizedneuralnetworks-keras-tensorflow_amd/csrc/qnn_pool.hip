@@ -11,7 +11,7 @@
 // the entry refuses N * Ho * Wo * groups >= 2^31; tensor offsets are 64-bit.
 #include <stdio.h>
 
-#include "qnn_common.h"
+#include "qnn_sideconv.h"
 #include "qnn_abi_pool.h"
 
 namespace {
@@ -47,22 +47,6 @@ __device__ __forceinline__ Item decode(uint32_t i, const PoolGeom& p) {
     it.xa = max(x0, 0);
     it.xb = min(x0 + p.pw, p.W);
     return it;
-}
-
-template <int V> struct Words;
-template <> struct Words<1> { typedef uint32_t type; };
-template <> struct Words<4> { typedef uint4 type; };
-
-template <int V>
-__device__ __forceinline__ void load_words(const uint32_t* p, uint32_t (&w)[V]) {
-    const typename Words<V>::type v = *reinterpret_cast<const typename Words<V>::type*>(p);
-    __builtin_memcpy(w, &v, sizeof(v));
-}
-template <int V>
-__device__ __forceinline__ void store_words(uint32_t* p, const uint32_t (&w)[V]) {
-    typename Words<V>::type v;
-    __builtin_memcpy(&v, w, sizeof(v));
-    *reinterpret_cast<typename Words<V>::type*>(p) = v;
 }
 
 template <int STORE> struct Lay {
@@ -228,10 +212,6 @@ int pool_geometry(const char* who, int H, int W, const qnn_pool2d_t* p, int* Ho,
                 QNN_EINVAL, "%s: a %dx%d window at strides %dx%d holds no cell of the %dx%d image", who, p->ph, p->pw,
                 p->sh, p->sw, H, W);
     return QNN_OK;
-}
-
-const char* store_name(int store) {
-    return store == QNN_STORE_BIN ? "bin" : store == QNN_STORE_I4 ? "i4" : store == QNN_STORE_I8 ? "i8" : "f32";
 }
 
 template <int STORE>

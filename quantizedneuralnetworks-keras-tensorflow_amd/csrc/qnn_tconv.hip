@@ -23,27 +23,17 @@
 // transpose.  No LDS.
 //
 // Index arithmetic in 32 bits by multiply-high (the entry refuses 2^31 output words), tensor offsets in 64 bits.
-#include <stdio.h>
-
 #include <new>
 
+#include "qnn_sideconv.h"
 #include "qnn_strip_device.h"
 #include "qnn_abi_tconv.h"
 
-struct qnn_tconv_weights {
-    int wkind, wbits;
-    float H;
+struct qnn_tconv_weights : SideWeights {   // d_wq, d_wcode: [kh*kw][cout][cin], Keras' (kh, kw, Cout, Cin) order
     int kh, kw, cout, cin;
     int stride, same_pad;
-    int store;
-    int wshift;              // quantized value = code * 2^-wshift
-    int xcw;                 // words per input pixel on the handle's packed store (F32: 0)
-    float* d_wq;             // [kh*kw][cout][cin] quantized values: Keras' (kh, kw, Cout, Cin) order
-    int32_t* d_wcode;        // the same order, integer codes (packed stores) or nullptr
     uint32_t* d_wpk;         // [kh*kw][cout][xcw] codes packed like an input pixel, spare bits zero, or nullptr
     uint8_t* d_wm;           // matrix-pipe image [phase 4][tap 4][K-step][32-filter block][tile 2][lane 64][16 bytes], or nullptr
-    float* d_bias;           // [cout] or nullptr
-    float* d_aux;            // ternary: the cutoff (1 float), else nullptr
 };
 
 namespace {
@@ -52,40 +42,6 @@ constexpr int kBlock = 256;
 constexpr int kPG = 4;       // 16-pixel groups a wave of k_tc_mfma takes per filter load
 
 // ---- weights ----------------------------------------------------------------------------------------------------------
-// ternary_ops.py:15-30: cutoff = 0.7 * mean(|W / H|) over the whole kernel.  One block, fixed order, float64 sums.
-__global__ __launch_bounds__(1024) void k_tc_tern_cutoff(const float* __restrict__ kernel, int n, float H,
-                                                         float* __restrict__ cutoff) {
-    __shared__ double part[1024];
-    double s = 0.0;
-    for (int i = threadIdx.x; i < n; i += 1024) s += (double)fabsf(__fdiv_rn(kernel[i], H));
-    part[threadIdx.x] = s;
-    __syncthreads();
-    for (int off = 512; off > 0; off >>= 1) {
-        if ((int)threadIdx.x < off) part[threadIdx.x] += part[threadIdx.x + off];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) cutoff[0] = __fmul_rn(0.7f, (float)(part[0] / (double)n));
-}
-
-// binarize (binary_ops.py:54-64), quantize (quantized_ops.py:49-66), ternarize (ternary_ops.py:21-41), elementwise; the
-// codes are value * 2^wshift (binary / ternary on a packed store have H = 1: the value itself)
-__global__ __launch_bounds__(kBlock) void k_tc_quantize(const float* __restrict__ kernel, float* __restrict__ wq,
-                                                        int32_t* __restrict__ wcode, int n, int wkind, float H, float m,
-                                                        const float* __restrict__ cutoff_p) {
-    const int i = blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
-    const float w = kernel[i];
-    float q = w;
-    if (wkind == QNN_W_BINARY) q = __fmul_rn(H, qnn_binary_tanh(__fdiv_rn(w, H)));
-    else if (wkind == QNN_W_QUANT) q = qnn_quantized_tanh(w, m);
-    else if (wkind == QNN_W_TERNARY) {
-        const float u = __fdiv_rn(w, H), cutoff = cutoff_p[0];
-        q = __fmul_rn(u > cutoff ? 1.0f : (u <= -cutoff ? -1.0f : 0.0f), H);
-    }
-    wq[i] = q;
-    if (wcode) wcode[i] = (int)__fmul_rn(q, m);
-}
-
 // word wi of filter row (tap, f) in the layout of an input pixel on `store`; channels beyond cin - 1 stay zero
 __global__ __launch_bounds__(kBlock) void k_tc_pack_words(const int32_t* __restrict__ wcode, uint32_t* __restrict__ wpk,
                                                           int rows, int cin, int xcw, int store) {
@@ -118,16 +74,8 @@ __host__ __device__ inline int tc_phase(int par, int pb) { return (par + pb) & 1
 __host__ __device__ inline int tc_base(int par, int pb) { return (par + pb) >> 1; }
 __host__ __device__ inline int tc_ntaps(int k, int phase) { return (k - phase + 1) >> 1; }
 
-// the channel (0 .. 15 of the lane's 16) that byte j of a B operand carries: in order for int8; for int4 the order
-// strip_widen leaves (even nibbles of a word, then odd ones)
-__host__ __device__ inline int tc_operand_channel(int store, int j) {
-    if (store == QNN_STORE_I8) return j;
-    const int wd = j >> 2, b = j & 3;
-    return (wd >> 1) * 8 + 2 * b + (wd & 1);
-}
-
 // One byte per thread of the image [phase rp * 2 + cp][tap jy * 2 + jx][kc][fb][nt][lane][16]: the weight code (int8) of
-// filter fb * 32 + 8 * (r >> 2) + 4 * nt + (r & 3) and channel kc * 64 + 16 * kq + tc_operand_channel(j); zero for a tap
+// filter fb * 32 + 8 * (r >> 2) + 4 * nt + (r & 3) and channel kc * 64 + 16 * kq + qnn_operand_channel(j); zero for a tap
 // the phase does not have and for a filter beyond cout - 1.
 __global__ __launch_bounds__(kBlock) void k_tc_mfma_image(const int32_t* __restrict__ wcode, uint8_t* __restrict__ wm, int k,
                                                           int pb, int cout, int cin, int store, uint32_t total) {
@@ -144,7 +92,7 @@ __global__ __launch_bounds__(kBlock) void k_tc_mfma_image(const int32_t* __restr
     const int r = lane & 15, kq = lane >> 4;
     const int ky = tc_phase(ph >> 1, pb) + 2 * (tap >> 1), kx = tc_phase(ph & 1, pb) + 2 * (tap & 1);
     const int f = fb * 32 + 8 * (r >> 2) + 4 * nt + (r & 3);
-    const int c = kc * 64 + 16 * kq + tc_operand_channel(store, j);
+    const int c = kc * 64 + 16 * kq + qnn_operand_channel(store, j);
     int code = 0;
     if (ky < k && kx < k && f < cout) code = wcode[((size_t)(ky * k + kx) * cout + f) * cin + c];
     wm[i] = (uint8_t)(int8_t)code;
@@ -178,17 +126,6 @@ __device__ __forceinline__ Item decode(uint32_t i, const TcGeom& p) {
     return it;
 }
 
-template <int V> struct Words;
-template <> struct Words<1> { typedef uint32_t type; };
-template <> struct Words<4> { typedef uint4 type; };
-
-template <int V>
-__device__ __forceinline__ void store_words(uint32_t* p, const uint32_t (&w)[V]) {
-    typename Words<V>::type v;
-    __builtin_memcpy(&v, w, sizeof(v));
-    *reinterpret_cast<typename Words<V>::type*>(p) = v;
-}
-
 // sum over the cin channels of one packed pixel `px` x one packed filter row `wr` (spare bits of wr are zero)
 template <int XS>
 __device__ __forceinline__ int dot_pixel(const uint32_t* __restrict__ px, const uint32_t* __restrict__ wr, int xcw, int cin,
@@ -206,14 +143,6 @@ __device__ __forceinline__ int dot_pixel(const uint32_t* __restrict__ px, const 
         for (int wi = 0; wi < xcw; ++wi) acc = qnn_dot<XS>(px[wi], wr[wi], acc);
     }
     return acc;
-}
-
-// value behind the chain -> what a float32 output stores (k_conv_generic's order)
-__device__ __forceinline__ float act_value(float v, const EpiArgs& e) {
-    if (e.fn == QNN_FN_BINARY_TANH) return qnn_binary_tanh(v);
-    if (qnn_is_qact(e.fn)) return qnn_qact(e.fn, v, e.act_m);
-    if (e.fn == QNN_FN_LEAKY_RELU) return qnn_leaky_relu(v);
-    return v;
 }
 
 // ---- the plain form ---------------------------------------------------------------------------------------------------
@@ -395,14 +324,6 @@ __global__ __launch_bounds__(kBlock) void k_tc_mfma(const uint8_t* __restrict__ 
     }
 }
 
-const char* store_name(int store) {
-    return store == QNN_STORE_BIN  ? "bin"
-           : store == QNN_STORE_I4 ? "i4"
-           : store == QNN_STORE_I8 ? "i8"
-           : store == QNN_STORE_T2 ? "t2"
-                                   : "f32";
-}
-
 // THE route rule of the matrix-pipe form (include/qnn_abi_tconv.h states it; tests/tconv_cases.py restates it).  The
 // handle's half is asked with x == y == nullptr at prepack: it decides whether the operand image is built.
 bool mfma_ok(int kh, int kw, int stride, int store, int cout, int cin, int x_store, int out_store, int H, int W,
@@ -427,6 +348,25 @@ void out_hw(const qnn_tconv_weights* w, int H, int W, TcGeom* g) {
     qnn_tconv_out_pad(W, w->kw, w->stride, w->same_pad, &g->Wo, &g->pl);
 }
 
+// prepack: the filter rows of the plain form on a packed store, and the operand image where the shape takes the matrix pipe
+int pack_images(qnn_tconv_weights* w, hipStream_t s) {
+    if (w->store != QNN_STORE_F32) {
+        const int rows = w->kh * w->kw * w->cout, nw = rows * w->xcw;
+        QNN_SIDE_HIP(hipMalloc(&w->d_wpk, (size_t)nw * sizeof(uint32_t)));
+        hipLaunchKernelGGL(k_tc_pack_words, dim3((nw + kBlock - 1) / kBlock), dim3(kBlock), 0, s, w->d_wcode, w->d_wpk, rows,
+                           w->cin, w->xcw, w->store);
+    }
+    if (mfma_ok(w->kh, w->kw, w->stride, w->store, w->cout, w->cin, w->store, w->store, 1, 1, nullptr, nullptr)) {
+        int ho, pb;
+        qnn_tconv_out_pad(1, w->kh, w->stride, w->same_pad, &ho, &pb);
+        const uint32_t total = 16u * (uint32_t)(w->cin / 64) * (uint32_t)((w->cout + 31) / 32) * 2u * 64u * 16u;
+        QNN_SIDE_HIP(hipMalloc(&w->d_wm, (size_t)total));
+        hipLaunchKernelGGL(k_tc_mfma_image, dim3((total + kBlock - 1) / kBlock), dim3(kBlock), 0, s, w->d_wcode, w->d_wm, w->kh,
+                           pb, w->cout, w->cin, w->store, total);
+    }
+    return QNN_OK;
+}
+
 }  // namespace
 
 extern "C" int qnn_tconv_prepack(int wkind, int wbits, float H, const float* kernel, int kh, int kw, int Cout, int Cin,
@@ -440,95 +380,32 @@ extern "C" int qnn_tconv_prepack(int wkind, int wbits, float H, const float* ker
     QNN_REQUIRE(kh <= QNN_TC_MAX_WINDOW, QNN_EUNSUPPORTED, "%s: kh=%d above QNN_TC_MAX_WINDOW = %d", who, kh, QNN_TC_MAX_WINDOW);
     QNN_REQUIRE(kw <= QNN_TC_MAX_WINDOW, QNN_EUNSUPPORTED, "%s: kw=%d above QNN_TC_MAX_WINDOW = %d", who, kw, QNN_TC_MAX_WINDOW);
     QNN_REQUIRE((double)Cout * Cin * kh * kw < 1.0e9, QNN_EUNSUPPORTED, "%s: %d x %d channels", who, Cout, Cin);
-    QNN_REQUIRE(wkind == QNN_W_FLOAT || wkind == QNN_W_BINARY || wkind == QNN_W_QUANT || wkind == QNN_W_TERNARY,
-                QNN_EINVAL, "%s: wkind=%d not supported", who, wkind);
-    QNN_REQUIRE(H > 0.0f, QNN_EINVAL, "%s: H=%g", who, (double)H);
-    int wshift = 0;
-    float m = 1.0f;
-    if (wkind == QNN_W_QUANT) {
-        QNN_REQUIRE(wbits >= 2 && wbits <= 24, QNN_EINVAL, "%s: wbits=%d", who, wbits);
-        wshift = wbits - 1;
-        m = (float)(1u << wshift);
-    }
-    switch (store) {
-        case QNN_STORE_F32:
-            break;
-        case QNN_STORE_BIN:
-            QNN_REQUIRE(wkind == QNN_W_BINARY && H == 1.0f, QNN_EINVAL, "%s: BIN storage needs binary weights with H=1", who);
-            break;
-        case QNN_STORE_I4:
-        case QNN_STORE_I8:
-            QNN_REQUIRE(((wkind == QNN_W_BINARY || wkind == QNN_W_TERNARY) && H == 1.0f) ||
-                            (wkind == QNN_W_QUANT && wbits <= store),
-                        QNN_EINVAL, "%s: wkind=%d wbits=%d does not fit %d-bit storage", who, wkind, wbits, store);
-            break;
-        case QNN_STORE_T2:
-            QNN_REQUIRE((wkind == QNN_W_BINARY || wkind == QNN_W_TERNARY) && H == 1.0f, QNN_EINVAL,
-                        "%s: sign / mask storage needs ternary (or binary) weights with H=1", who);
-            break;
-        default:
-            qnn_set_error("%s: store=%d", who, store);
-            return QNN_EINVAL;
-    }
+    SideWeights common{};
+    int rc = qnn_side_weights_check(who, wkind, wbits, H, store, &common);
+    if (rc != QNN_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
     qnn_tconv_weights* w = new (std::nothrow) qnn_tconv_weights();
     QNN_REQUIRE(w, QNN_ENOMEM, "%s: host allocation failed", who);
-    *w = qnn_tconv_weights{};
-    w->wkind = wkind; w->wbits = wbits; w->H = H;
+    *static_cast<SideWeights*>(w) = common;
     w->kh = kh; w->kw = kw; w->cout = Cout; w->cin = Cin;
     w->stride = stride; w->same_pad = same_pad ? 1 : 0;
-    w->store = store; w->wshift = wshift;
     w->xcw = store == QNN_STORE_F32 ? 0 : qnn_words(store, Cin);
-    const int n = kh * kw * Cout * Cin;
-#define TC_HIP(expr)                                                           \
-    do {                                                                       \
-        hipError_t _e = (expr);                                                \
-        if (_e != hipSuccess) {                                                \
-            qnn_set_error("%s failed: %s", #expr, hipGetErrorString(_e));      \
-            qnn_tconv_free(w);                                                 \
-            return _e == hipErrorOutOfMemory ? QNN_ENOMEM : QNN_EHIP;          \
-        }                                                                      \
-    } while (0)
-    TC_HIP(hipMalloc(&w->d_wq, (size_t)n * sizeof(float)));
-    if (store != QNN_STORE_F32) TC_HIP(hipMalloc(&w->d_wcode, (size_t)n * sizeof(int32_t)));
-    if (wkind == QNN_W_TERNARY) {
-        TC_HIP(hipMalloc(&w->d_aux, 16));
-        hipLaunchKernelGGL(k_tc_tern_cutoff, dim3(1), dim3(1024), 0, s, kernel, n, H, w->d_aux);
+    rc = qnn_side_quantize(w, kernel, kh * kw * Cout * Cin, bias, Cout, s);
+    if (rc == QNN_OK) rc = pack_images(w, s);
+    if (rc == QNN_OK) rc = qnn_side_hip(hipGetLastError(), "hipGetLastError()");
+    if (rc != QNN_OK) {
+        qnn_tconv_free(w);
+        return rc;
     }
-    hipLaunchKernelGGL(k_tc_quantize, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, kernel, w->d_wq, w->d_wcode, n,
-                       wkind, H, m, (const float*)w->d_aux);
-    if (bias) {
-        TC_HIP(hipMalloc(&w->d_bias, (size_t)Cout * sizeof(float)));
-        TC_HIP(hipMemcpyAsync(w->d_bias, bias, (size_t)Cout * sizeof(float), hipMemcpyDeviceToDevice, s));
-    }
-    if (store != QNN_STORE_F32) {
-        const int rows = kh * kw * Cout, nw = rows * w->xcw;
-        TC_HIP(hipMalloc(&w->d_wpk, (size_t)nw * sizeof(uint32_t)));
-        hipLaunchKernelGGL(k_tc_pack_words, dim3((nw + kBlock - 1) / kBlock), dim3(kBlock), 0, s, w->d_wcode, w->d_wpk, rows,
-                           Cin, w->xcw, store);
-    }
-    if (mfma_ok(kh, kw, stride, store, Cout, Cin, store, store, 1, 1, nullptr, nullptr)) {
-        int ho, pb;
-        qnn_tconv_out_pad(1, kh, stride, w->same_pad, &ho, &pb);
-        const uint32_t total = 16u * (uint32_t)(Cin / 64) * (uint32_t)((Cout + 31) / 32) * 2u * 64u * 16u;
-        TC_HIP(hipMalloc(&w->d_wm, (size_t)total));
-        hipLaunchKernelGGL(k_tc_mfma_image, dim3((total + kBlock - 1) / kBlock), dim3(kBlock), 0, s, w->d_wcode, w->d_wm, kh,
-                           pb, Cout, Cin, store, total);
-    }
-    TC_HIP(hipGetLastError());
-#undef TC_HIP
     *out = w;
     return QNN_OK;
 }
 
 extern "C" int qnn_tconv_free(qnn_tconv_weights_t* w) {
     if (!w) return QNN_OK;
-    if (w->d_wq) (void)hipFree(w->d_wq);
-    if (w->d_wcode) (void)hipFree(w->d_wcode);
     if (w->d_wpk) (void)hipFree(w->d_wpk);
     if (w->d_wm) (void)hipFree(w->d_wm);
-    if (w->d_bias) (void)hipFree(w->d_bias);
-    if (w->d_aux) (void)hipFree(w->d_aux);
+    qnn_side_free(w);
     delete w;
     return QNN_OK;
 }
@@ -556,45 +433,11 @@ extern "C" int qnn_tconv_forward(const qnn_tconv_weights_t* w, const void* x, in
     const char* who = "qnn_tconv_forward";
     QNN_REQUIRE(w && epi, QNN_EINVAL, "%s: null handle or epilogue", who);
     QNN_REQUIRE(N >= 0 && H > 0 && W > 0 && H < (1 << 26) && W < (1 << 26), QNN_EINVAL, "%s: N=%d H=%d W=%d", who, N, H, W);
-    QNN_REQUIRE(x_store != QNN_STORE_U8 && x_store != QNN_STORE_F32_IMAGE && x_store != QNN_STORE_F32_UNIT,
-                QNN_EUNSUPPORTED, "%s: x_store=%d (QNN_STORE_U8 and the typed float32 stores are first-layer inputs of "
-                "qnn_conv2d_forward)", who, x_store);
+    int xshift;
+    EpiArgs e;
+    int rc = qnn_side_forward_check(who, w, w->cout, x_store, x_bits, epi, "a transposed convolution", &xshift, &e);
+    if (rc != QNN_OK) return rc;
     const bool packed = x_store != QNN_STORE_F32;
-    int xshift = 0;
-    if (packed) {
-        QNN_REQUIRE(x_store == QNN_STORE_BIN || x_store == QNN_STORE_T2 || x_store == QNN_STORE_I4 || x_store == QNN_STORE_I8,
-                    QNN_EINVAL, "%s: x_store=%d", who, x_store);
-        QNN_REQUIRE(x_store == w->store, QNN_EINVAL, "%s: x_store=%d but the weights were prepacked for store=%d", who,
-                    x_store, w->store);
-        if (x_store == QNN_STORE_I4 || x_store == QNN_STORE_I8) {
-            QNN_REQUIRE(x_bits >= 1 && x_bits <= x_store, QNN_EINVAL, "%s: x_bits=%d does not fit %d-bit storage", who,
-                        x_bits, x_store);
-            xshift = x_bits - 1;
-        }
-    }
-    // ---- the epilogue subset ----
-    QNN_REQUIRE(epi->pool == 1, QNN_EUNSUPPORTED, "%s: epilogue field pool=%d (no pooling behind a transposed convolution)",
-                who, epi->pool);
-    QNN_REQUIRE(!epi->res, QNN_EUNSUPPORTED, "%s: epilogue field res (no residual input)", who);
-    QNN_REQUIRE(!epi->fold, QNN_EUNSUPPORTED, "%s: epilogue field fold (no folded epilogue)", who);
-    QNN_REQUIRE(!epi->proj, QNN_EUNSUPPORTED, "%s: epilogue field proj (no in-launch projection)", who);
-    QNN_REQUIRE(epi->trick_s == 0.0f, QNN_EUNSUPPORTED, "%s: epilogue field trick_s=%g (no identity trick)", who,
-                (double)epi->trick_s);
-    QNN_REQUIRE(epi->flags == 0u, QNN_EUNSUPPORTED, "%s: epilogue field flags=%u (no kernel-selection bits)", who, epi->flags);
-    QNN_REQUIRE((epi->bn_inv == nullptr) == (epi->bn_shift == nullptr), QNN_EINVAL,
-                "%s: bn_inv and bn_shift must both be set or both be NULL", who);
-    QNN_REFUSE_MAXACT(epi->fn, who);
-    const int fn = epi->fn, os = epi->out_store;
-    QNN_REQUIRE(fn == QNN_FN_NONE || fn == QNN_FN_BINARY_TANH || qnn_is_qact(fn) || fn == QNN_FN_LEAKY_RELU, QNN_EINVAL,
-                "%s: fn=%d cannot be fused", who, fn);
-    QNN_REQUIRE(fn != QNN_FN_LEAKY_RELU || os == QNN_STORE_F32, QNN_EINVAL, "%s: leaky_relu needs a float32 output", who);
-    if (qnn_is_qact(fn)) QNN_REQUIRE(epi->act_bits >= 2 && epi->act_bits <= 24, QNN_EINVAL, "%s: act_bits=%d", who, epi->act_bits);
-    QNN_REQUIRE(os == QNN_STORE_F32 || os == QNN_STORE_BIN || os == QNN_STORE_I4 || os == QNN_STORE_I8, QNN_EINVAL,
-                "%s: out_store=%d", who, os);
-    QNN_REQUIRE(os != QNN_STORE_BIN || fn == QNN_FN_BINARY_TANH, QNN_EINVAL, "%s: BIN output needs fn=binary_tanh", who);
-    QNN_REQUIRE(!(os == QNN_STORE_I4 || os == QNN_STORE_I8) || fn == QNN_FN_BINARY_TANH ||
-                    (qnn_is_qact(fn) && epi->act_bits <= os),
-                QNN_EINVAL, "%s: fn=%d act_bits=%d does not fit %d-bit output", who, fn, epi->act_bits, os);
     // ---- the int32 bound: the most (tap, channel) pairs one output value sums, each at most 2^(x_bits-1) * 2^wshift ----
     if (packed) {
         const int s = w->stride;
@@ -610,28 +453,14 @@ extern "C" int qnn_tconv_forward(const qnn_tconv_weights_t* w, const void* x, in
     g.H = H; g.W = W; g.cin = w->cin; g.cout = w->cout;
     g.kh = w->kh; g.kw = w->kw; g.stride = w->stride;
     g.xcw = packed ? w->xcw : w->cin;
-    g.ocw = os == QNN_STORE_F32 ? w->cout : qnn_words(os, w->cout);
-    const size_t owords = (size_t)N * g.Ho * g.Wo * (size_t)g.ocw;
-    QNN_REQUIRE(owords < ((size_t)1 << 31), QNN_EUNSUPPORTED, "%s: %zu output words (2^31 or more)", who, owords);
-    if (N == 0) return QNN_OK;
-    QNN_REQUIRE(x && y, QNN_EINVAL, "%s: null pointer", who);
-    const size_t xbytes = (size_t)N * H * W * g.xcw * 4, ybytes = owords * 4;
-    const uintptr_t xa = (uintptr_t)x, ya = (uintptr_t)y;
-    QNN_REQUIRE(xa + xbytes <= ya || ya + ybytes <= xa, QNN_EINVAL, "%s: x and y overlap", who);
-
-    EpiArgs e{};
-    e.bias = w->d_bias;
-    e.bn_inv = epi->bn_inv;
-    e.bn_shift = epi->bn_shift;
-    e.scale = packed ? ldexpf(1.0f, -(w->wshift + xshift)) : 1.0f;
-    e.act_m = qnn_is_qact(fn) ? (float)(1u << (epi->act_bits - 1)) : 1.0f;
-    e.fn = fn;
-    e.out_store = os;
-    e.ocw = g.ocw;
-    e.post_scale = 1.0f;
+    g.ocw = e.ocw;
+    bool run;
+    rc = qnn_side_io_check(who, N, (size_t)N * g.Ho * g.Wo * (size_t)g.ocw, x, (size_t)N * H * W * g.xcw * 4, y, &run);
+    if (!run) return rc;
 
     hipStream_t s = (hipStream_t)stream;
-    const bool fast = packed && w->d_wm && mfma_ok(w->kh, w->kw, w->stride, w->store, w->cout, w->cin, x_store, os, H, W, x, y);
+    const bool fast = packed && w->d_wm &&
+                      mfma_ok(w->kh, w->kw, w->stride, w->store, w->cout, w->cin, x_store, e.out_store, H, W, x, y);
     if (fast) {
         TcMfma p{};
         p.H = H; p.W = W; p.Ho = g.Ho; p.Wo = g.Wo; p.cout = w->cout;
@@ -653,23 +482,16 @@ extern "C" int qnn_tconv_forward(const qnn_tconv_weights_t* w, const void* x, in
         else
             hipLaunchKernelGGL((k_tc_mfma<QNN_STORE_I8>), grid, block, 0, s, (const uint8_t*)x, w->d_wm, (uint32_t*)y, p, e);
     } else {
-        const bool v4 = xa % 16 == 0 && ya % 16 == 0 && g.ocw % 4 == 0;
+        const bool v4 = (uintptr_t)x % 16 == 0 && (uintptr_t)y % 16 == 0 && g.ocw % 4 == 0;
         g.groups = v4 ? g.ocw / 4 : g.ocw;
         g.fd_g = qnn_fastdiv((uint32_t)g.groups);
         g.fd_wo = qnn_fastdiv((uint32_t)g.Wo);
         g.fd_ho = qnn_fastdiv((uint32_t)g.Ho);
         g.fd_s = qnn_fastdiv((uint32_t)g.stride);
         const uint32_t total = (uint32_t)((size_t)N * g.Ho * g.Wo * (size_t)g.groups);
-        if (x_store == QNN_STORE_F32) launch_plain<QNN_STORE_F32>(v4, x, w, y, g, e, total, s);
-        else if (x_store == QNN_STORE_BIN) launch_plain<QNN_STORE_BIN>(v4, x, w, y, g, e, total, s);
-        else if (x_store == QNN_STORE_T2) launch_plain<QNN_STORE_T2>(v4, x, w, y, g, e, total, s);
-        else if (x_store == QNN_STORE_I4) launch_plain<QNN_STORE_I4>(v4, x, w, y, g, e, total, s);
-        else launch_plain<QNN_STORE_I8>(v4, x, w, y, g, e, total, s);
+        qnn_side_for_store(x_store, [&](auto xs) { launch_plain<decltype(xs)::value>(v4, x, w, y, g, e, total, s); });
     }
     QNN_HIP(hipGetLastError());
-    char name[40];
-    const bool has_fast = x_store == QNN_STORE_I4 || x_store == QNN_STORE_I8;
-    snprintf(name, sizeof(name), "tconv_%s%s", store_name(x_store), fast ? "_mfma" : has_fast ? "_plain" : "");
-    qnn_set_kernel_name(name);
+    qnn_side_kernel_name("tconv", x_store, fast ? "_mfma" : "_plain");
     return QNN_OK;
 }
