@@ -335,6 +335,90 @@ def make_inputs(c, seed=0):
     return x, kernel, bias, bn
 
 
+# ---- maps on which a kernel's item decode is not trivial ---------------------------------------------------------------------
+K_ROWS = 4               # output rows an item of k_dw_pk16 walks (csrc/qnn_depthwise.hip)
+BLOCK = 256              # lanes of a workgroup of every kernel of the three side convolutions
+TINY_MAP = (70, 1, 1)    # more images than a workgroup has waves, one pixel each
+
+
+def pk16_items(c):
+    """(row blocks per image, rows of the last one, items) of k_dw_pk16's launch: an item is (image, block of K_ROWS output
+    rows, output column, word), the word fastest."""
+    N, H, W = c["map"]
+    Ho = out_pad(H, 3, 1, c["same"])[0]
+    Wo = out_pad(W, 3, 1, c["same"])[0]
+    blocks = -(-Ho // K_ROWS)
+    return blocks, Ho - (blocks - 1) * K_ROWS, N * blocks * Wo * words(c["store"], c["C"])
+
+
+def plain_items(out_store, cout, pixels, misalign):
+    """(V, items) of a plain-form launch of the three side convolutions: a lane owns V = 4 words (float32: channels) of one
+    output pixel where the words per pixel divide by 4 and the pointers are 16-byte aligned, V = 1 otherwise."""
+    ocw = cout if out_store == F32 else words(out_store, cout)
+    V = 4 if ocw % 4 == 0 and not misalign else 1
+    return V, pixels * (ocw // V)
+
+
+def clip_ends(c):
+    """(lowest, highest) output of a case's activation as `reference` returns it; None where nothing clips."""
+    if c["fn"] in QACTS:
+        m = 2 ** (c["act_bits"] - 1)
+        lo = 0 if c["fn"] == FN_QUANTIZED_RELU else -m
+        return (lo, m - 1) if c["out_store"] != F32 else (f32(lo) / f32(m), f32(m - 1) / f32(m))
+    if c["fn"] == FN_BINARY_TANH:
+        return (0, 1) if c["out_store"] == BIN else (-1, 1)
+    return None
+
+
+def degenerate(c, want, groups=None):
+    """Why the expected output `want` (N, Ho, Wo, cout) of case `c` could not tell one pixel mapping from another, as a list
+    of sentences (empty: it can).  More than half of the outputs at the activation's two clip ends (a 1-bit output has no
+    other code: there the rarer code must hold a quarter); two images with equal outputs; two 16-pixel groups of an image
+    with equal outputs, a ragged last group compared over its own pixels.  `groups`: per image the groups as arrays
+    (pixels, cout); the default cuts the flattened map into 16-pixel runs."""
+    why = []
+    N = want.shape[0]
+    ends = clip_ends(c)
+    if ends is not None:
+        lo, hi = np.mean(want == ends[0]), np.mean(want == ends[1])
+        if c["out_store"] == BIN or c["fn"] == FN_BINARY_TANH:
+            if min(lo, hi) < 0.25:
+                why.append("one of the two codes holds %.3f of the outputs" % min(lo, hi))
+        elif lo + hi > 0.5:
+            why.append("%.3f of the outputs sit at a clip end" % (lo + hi))
+    flat = want.reshape(N, -1, want.shape[-1])
+    for a, b in itertools.combinations(range(N), 2):
+        if np.array_equal(flat[a], flat[b]):
+            why.append("images %d and %d are equal" % (a, b))
+    for n in range(N):
+        gs = groups[n] if groups is not None else [flat[n, i:i + 16] for i in range(0, flat.shape[1], 16)]
+        for (i, a), (j, b) in itertools.combinations(enumerate(gs), 2):
+            k = min(len(a), len(b))
+            if k and np.array_equal(a[:k], b[:k]):
+                why.append("image %d: groups %d and %d are equal" % (n, i, j))
+    return why
+
+
+def multitask_cases():
+    """Maps on which k_dw_pk16's item decode (image, row block, column, word) and the plain form's (pixel, word group) leave
+    the first workgroup and the first row block.  Every case carries the `seed` of its inputs.
+    pk16, I4 C = 33 (5 words) and I8 C = 16 (4 words; 4-bit weights keep the 16-bit bound) with 4-bit outputs, so that the
+    other packed store takes the same codes through the plain form:
+      (3, 10, 9)  3 row blocks, the last with 2 rows; 405 and 324 items: a second workgroup, partly filled
+      (2, 8, 17)  Ho % 4 == 0: no ragged row block; 340 and 272 items
+      (2, 13, 5)  4 row blocks, the last with 1 row
+      TINY_MAP    I4 only: 350 items, the image index runs to 69
+    plain form, BIN C = 256 (8 words) on (2, 9, 9): 324 items at V = 4, and off alignment 1296 at V = 1."""
+    out = []
+    for store, C, kw in ((I4, 33, {}), (I8, 16, dict(wbits=4))):
+        for m in ((3, 10, 9), (2, 8, 17), (2, 13, 5)):
+            out.append(_case(store, C, map=m, act_bits=4, seed=0, **kw))
+    out.append(_case(I4, 33, map=TINY_MAP, seed=0))
+    for misalign in (False, True):
+        out.append(_case(BIN, 256, map=(2, 9, 9), misalign=misalign, seed=0))
+    return out
+
+
 def overflow_case():
     """3x3, 8-bit codes x 8-bit weights, every input code -128 and every weight code -128: the interior sum is
     9 * 16384 = 147456 and already the second tap's partial sum 32768 leaves a signed 16-bit lane."""

@@ -223,6 +223,52 @@ def boundary_cases():
             _case(I8, 32, 4, 2)]
 
 
+# ---- maps on which a kernel's wave or item decode is not trivial ----------------------------------------------------------------
+K_PG = 4                 # 16-pixel groups a wave of k_gc_mfma takes (csrc/qnn_gconv.hip)
+MULTITASK_GEOMS = (      # stride, same, map: all 3x3
+    (1, True, (2, 9, 9)), (1, True, (2, 5, 29)), (2, False, (3, 17, 9)), (2, True, (2, 19, 15)))
+MULTITASK_SHAPES = ((4, 4, 4), (16, 32, 2), (2, 1, 16))        # one tile of 4 groups, 4 tiles, one tile of 16 groups
+
+
+def wave_tasks(c):
+    """(output pixels of an image, its 16-pixel groups, GT, waves) of k_gc_mfma's launch: GT wave tasks of K_PG groups per
+    (image, 16-filter tile), the tile fastest."""
+    N, H, W = c["map"]
+    npix = out_pad(H, c["window"][0], c["stride"], c["same"], c["dil"][0])[0] * \
+        out_pad(W, c["window"][1], c["stride"], c["same"], c["dil"][1])[0]
+    groups = -(-npix // 16)
+    GT = -(-groups // K_PG)
+    return npix, groups, GT, N * GT * (c["Cout"] // 16)
+
+
+def multitask_cases():
+    """Maps on which k_gc_mfma's wave decode (image, K_PG groups from g0, tile) and the plain form's (pixel, word group) are
+    not trivial.  Every case carries the `seed` of its inputs.
+    matrix pipe, I4 and I8, every shape of MULTITASK_SHAPES at 3x3:
+      'same'  / 1 (2, 9, 9)    81 pixels = 6 groups, GT = 2: the second task holds a full group, a one-pixel group and two
+                               groups beyond the image
+      'same'  / 1 (2, 5, 29)   145 pixels = 10 groups, GT = 3: the third task's pair is a full group and a one-pixel group,
+                               so 15 lanes of an int4 pair have one valid member; with one tile 6 waves: the second workgroup
+                               is half filled
+      'valid' / 2 (3, 17, 9)   8 x 4 = 32 pixels, GT = 1: the control
+      'same'  / 2 (2, 19, 15)  10 x 8 = 80 pixels = 5 groups, GT = 2: the second task is group 4 alone, its int4 pair
+                               partner beyond the image
+      'same'  / 1 (70, 1, 1)   I4 (4, 4, 4) only: one pixel per image, 70 waves, the image index runs to 69
+    plain form, I4 (Cg 8, Fg 8, g 4) to float32 (the route rule wants out_store == store) on (2, 9, 11): 1584 items at V = 4,
+    and off alignment 6336 at V = 1."""
+    out = []
+    for store in (I4, I8):
+        for Cg, Fg, g in MULTITASK_SHAPES:
+            for stride, same, m in MULTITASK_GEOMS:
+                # seed 0 leaves 0.518 of this case's codes at the clip ends (test_gconv_cpu.py caps that at a half), seed 5 0.351
+                seed = 5 if (store, Cg, m) == (I4, 2, (3, 17, 9)) else 0
+                out.append(_case(store, Cg, Fg, g, stride=stride, same=same, map=m, seed=seed))
+    out.append(_case(I4, 4, 4, 4, map=(70, 1, 1), seed=0))
+    for misalign in (False, True):
+        out.append(_case(I4, 8, 8, 4, map=(2, 9, 11), out_store=F32, misalign=misalign, seed=0))
+    return out
+
+
 # the route rule on its boundary table: (kh, kw, Cin, Cout, groups) -> eligible
 ROUTE_TABLE = (
     ((3, 3, 16, 16, 4), True), ((3, 3, 12, 16, 4), False), ((3, 3, 32, 48, 2), False), ((3, 3, 32, 8, 2), False),

@@ -185,6 +185,61 @@ def boundary_cases():
             _case(I4, 64, 16, **dict(base, window=(2, 3))), _case(I4, 64, 16, **dict(base, stride=3))]
 
 
+# ---- maps on which a kernel's wave or item decode is not trivial ----------------------------------------------------------------
+K_PG = 4                 # 16-pixel groups a wave of k_tc_mfma takes (csrc/qnn_tconv.hip)
+MULTITASK_MAPS = (       # window, same, map
+    (3, False, (2, 2, 21)), (3, True, (2, 4, 40)), (2, False, (2, 2, 21)), (4, False, (2, 2, 21)))
+
+
+def phase_pixels(c):
+    """Output pixels of one image per sub-pixel phase (row parity, column parity) of a stride-2 case, phase (0, 0) first."""
+    _, H, W = c["map"]
+    Ho = out_pad(H, c["window"][0], 2, c["same"])[0]
+    Wo = out_pad(W, c["window"][1], 2, c["same"])[0]
+    return [((Ho - rp + 1) // 2) * ((Wo - cp + 1) // 2) for rp in (0, 1) for cp in (0, 1)]
+
+
+def wave_tasks(c):
+    """(GT, waves) of k_tc_mfma's launch: GT wave tasks of K_PG groups per (image, phase, 32-filter block), sized by phase
+    (0, 0), the largest; a task whose first group lies beyond its own phase returns at once."""
+    GT = -(-(-(-phase_pixels(c)[0] // 16)) // K_PG)
+    return GT, c["map"][0] * 4 * GT * (-(-c["Cout"] // 32))
+
+
+def phase_groups(c, want):
+    """Per image the 16-pixel groups of k_tc_mfma as arrays (pixels, Cout): each phase's pixels flattened row by row."""
+    out = []
+    for n in range(want.shape[0]):
+        gs = []
+        for rp in (0, 1):
+            for cp in (0, 1):
+                ph = want[n, rp::2, cp::2].reshape(-1, want.shape[-1])
+                gs += [ph[i:i + 16] for i in range(0, len(ph), 16)]
+        out.append(gs)
+    return out
+
+
+def multitask_cases():
+    """Maps on which k_tc_mfma's wave decode (image, phase, K_PG groups from g0, filter block) and the plain form's (pixel,
+    word group) are not trivial.  Every case carries the `seed` of its inputs.
+    matrix pipe, I4 and I8, (Cin, Cout) = (64, 16) (a half-filled filter block) and (128, 48) (two blocks):
+      k = 3 'valid' (2, 2, 21)  phases of 66 / 63 / 44 / 42 pixels, GT = 2: three phases return early at g0 == 4
+      k = 3 'same'  (2, 4, 40)  160 pixels per phase, GT = 3
+      k = 2 'valid' (2, 2, 21)  42 per phase, GT = 1   } equal phases
+      k = 4 'valid' (2, 2, 21)  66 per phase, GT = 2   }
+      k = 3 'same'  (70, 1, 1)  I4 only: one pixel per phase, the image index runs to 69 over 70 workgroups
+    plain form, I8 16 -> 16 at 3x3 / 2 'same' on (2, 5, 9): 360 items at V = 4, and off alignment 1440 at V = 1."""
+    out = []
+    for store in (I4, I8):
+        for cin, cout in ((64, 16), (128, 48)):
+            for k, same, m in MULTITASK_MAPS:
+                out.append(_case(store, cin, cout, window=(k, k), same=same, map=m, seed=0))
+    out.append(_case(I4, 64, 16, map=(70, 1, 1), seed=0))
+    for misalign in (False, True):
+        out.append(_case(I8, 16, 16, map=(2, 5, 9), misalign=misalign, seed=0))
+    return out
+
+
 def make_inputs(c, seed=0):
     """Deterministic inputs of a case: (x codes or float32 values, kernel (kh, kw, Cout, Cin), bias or None, (inv, shift)
     or None).  Kernel values and float inputs are multiples of 1/64 in [-1, 1]; bias and BN constants are small dyadic

@@ -110,6 +110,52 @@ def test_encode_decode_round_trip():
     np.testing.assert_array_equal((mask * (2 * sign.astype(np.int64) - 1)).reshape(3, -1)[:, :33], t)
 
 
+# ---- the multitask table: what it reaches, and that its expected values can tell pixel mappings apart ------------------------
+FILL = 0x5A5A5A5A                                # what test_gpu_depthwise.py lays under every output
+
+
+def test_multitask_table_reaches_the_decodes_it_names():
+    cases = D.multitask_cases()
+    assert len({D.case_id(c) for c in cases}) == len(cases) == 9 and all(c["map"][0] >= 2 for c in cases)
+    fast = [c for c in cases if D.takes_pk16(c)]
+    assert len(fast) == 7 and {(c["store"], c["C"]) for c in fast} == {(D.I4, 33), (D.I8, 16)}
+    # row blocks, rows of the last block and items, restated from the map alone ('same' at stride 1: Ho = H, Wo = W)
+    by_map = {(3, 10, 9): (3, 2, {D.I4: 405, D.I8: 324}), (2, 8, 17): (2, 4, {D.I4: 340, D.I8: 272}),
+              (2, 13, 5): (4, 1, {D.I4: 200, D.I8: 160}), (70, 1, 1): (1, 1, {D.I4: 350})}
+    for c in fast:
+        N, H, W = c["map"]
+        blocks, last, items = D.pk16_items(c)
+        assert (blocks, last, items) == (-(-H // 4), (H - 1) % 4 + 1, N * -(-H // 4) * W * -(-c["C"] // (32 // c["store"])))
+        assert (blocks, last, items) == by_map[c["map"]][:2] + (by_map[c["map"]][2][c["store"]],), D.case_id(c)
+    for store in (D.I4, D.I8):
+        mine = [D.pk16_items(c) for c in fast if c["store"] == store]
+        # past the first workgroup with a second, partly filled one; every raggedness of the last row block but 3
+        assert any(items > D.BLOCK and items % D.BLOCK for _, _, items in mine)
+        assert {last % D.K_ROWS for blocks, last, items in mine if items > D.BLOCK or blocks > 2} >= {0, 1, 2}
+        assert max(blocks for blocks, _, _ in mine) >= 3
+    assert any(items > D.BLOCK and last % D.K_ROWS in (0, 1, 2) for _, last, items in map(D.pk16_items, fast))
+    assert any(c["map"] == D.TINY_MAP and D.pk16_items(c)[2] == 350 for c in fast)
+    # the plain form past one workgroup at V = 4, and the same case at V = 1
+    plain = [c for c in cases if not D.takes_pk16(c)]
+    assert [c["misalign"] for c in plain] == [False, True] and all((c["store"], c["C"]) == (D.BIN, 256) for c in plain)
+    items = [D.plain_items(c["out_store"], c["C"], 2 * 9 * 9, c["misalign"]) for c in plain]
+    assert items == [(4, 324), (1, 1296)] and items[0][1] > D.BLOCK and items[0][1] % D.BLOCK
+
+
+@pytest.mark.parametrize("c", D.multitask_cases(), ids=D.case_id)
+def test_multitask_expected_values_tell_pixel_mappings_apart(c):
+    """At most half of the codes at the clip ends (the 1-bit store: each code at least a quarter), no two images, no two
+    16-pixel runs and no two row blocks of an image alike, and no expected word equal to the pattern the GPU test lays
+    under the output."""
+    want = D.reference(c, *D.make_inputs(c, c["seed"]))
+    assert D.degenerate(c, want) == []
+    blocks = [[img[r:r + D.K_ROWS].reshape(-1, img.shape[-1]) for r in range(0, img.shape[0], D.K_ROWS)] for img in want]
+    assert D.degenerate(c, want, blocks) == []
+    assert not (D.encode(want, c["out_store"]) == FILL).any()
+    if D.takes_pk16(c):                          # the GPU test writes the same codes to the other packed store as well
+        assert c["act_bits"] == 4 and not (D.encode(want, D.I4 + D.I8 - c["out_store"]) == FILL).any()
+
+
 LAYERS = [(qnn_amd.DepthwiseConv2D, {}), (qnn_amd.BinaryDepthwiseConv2D, {"H": 1.0}),
           (qnn_amd.QuantizedDepthwiseConv2D, {"nb": 4}), (qnn_amd.TernaryDepthwiseConv2D, {})]
 

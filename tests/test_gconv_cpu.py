@@ -22,7 +22,7 @@ ENTRIES = _abi.EXPORTS_GCONV                     # read at import: without the f
 
 def _geometries():
     seen, out = set(), []
-    for c in G.plain_cases() + G.mfma_cases() + G.boundary_cases():
+    for c in G.plain_cases() + G.mfma_cases() + G.boundary_cases() + G.multitask_cases():
         key = (c["Cg"], c["Fg"], c["groups"], c["window"], c["stride"], c["same"], c["dil"], c["map"])
         if key not in seen:
             seen.add(key)
@@ -97,6 +97,55 @@ def test_route_rule_on_its_boundary_table():
     assert shapes == set(G.MFMA_SHAPES)
     assert G.int32_refused(7, 7, 4096, 8, 7) and not G.int32_refused(7, 7, 4096, 7, 7)
     assert 7 * 7 * G.MAX_RUN * 8 * 8 * 16 < (1 << 31)        # the code * 16 int4 operands of the matrix-pipe form fit too
+
+
+# ---- the multitask table: what it reaches, and that its expected values can tell pixel mappings apart ------------------------
+FILL = 0x5A5A5A5A                                # what test_gpu_gconv.py lays under every output
+
+
+def test_multitask_table_reaches_the_decodes_it_names():
+    cases = G.multitask_cases()
+    assert len({G.case_id(c) for c in cases}) == len(cases) == 27 and all(c["map"][0] >= 2 for c in cases)
+    fast = [c for c in cases if G.takes_mfma(c)]
+    assert len(fast) == 25 and {c["store"] for c in fast} == {G.I4, G.I8}
+    assert {(c["Cg"], c["Fg"], c["groups"]) for c in fast} == set(G.MULTITASK_SHAPES) <= set(G.MFMA_SHAPES)
+    assert {G.plan(3, 3, c["Cin"], c["Cout"], c["groups"])["t"] for c in fast} == {1, 4, 16}
+    # the task count, restated from the map alone: GT = ceil(ceil(Ho * Wo / 16) / 4), waves = N * GT * tiles
+    by_map = {(2, 9, 9): (81, 2), (2, 5, 29): (145, 3), (3, 17, 9): (32, 1), (2, 19, 15): (80, 2), (70, 1, 1): (1, 1)}
+    for c in fast:
+        N, H, W = c["map"]
+        Ho, Wo = (G.out_pad(v, 3, c["stride"], c["same"])[0] for v in (H, W))
+        npix, groups, GT, waves = G.wave_tasks(c)
+        assert (npix, GT) == (Ho * Wo, -(-(-(-Ho * Wo // 16)) // 4)) == by_map[c["map"]], G.case_id(c)
+        assert waves == N * GT * c["Cout"] // 16
+    tasks = [G.wave_tasks(c) for c in fast]
+    assert max(t[2] for t in tasks) >= 3                                  # g0 = 8
+    i4 = [G.wave_tasks(c) for c in fast if c["store"] == G.I4]
+    # int4 pairs (2 k, 2 k + 1) of a later task: a last group with an even index has no partner at all ...
+    assert any((groups - 1) % 2 == 0 and groups - 1 >= G.K_PG for _, groups, _, _ in i4)
+    # ... and a ragged last group with an odd index leaves 15 lanes of the pair with one valid member
+    assert any((groups - 1) % 2 == 1 and groups - 1 >= G.K_PG and npix % 16 == 1 for npix, groups, _, _ in i4)
+    # a later task that ends in two groups beyond the image
+    assert any(GT * G.K_PG - groups >= 2 and GT >= 2 for _, groups, GT, _ in tasks)
+    # the wave >= waves exit inside a partly filled workgroup, behind several tasks per image, and on the tiny images
+    assert any(waves % (D.BLOCK // 64) and GT >= 2 for _, _, GT, waves in tasks)
+    assert any(c["map"] == D.TINY_MAP and G.wave_tasks(c)[3] == 70 for c in fast)
+    # the plain form past one workgroup at V = 4, and the same case at V = 1
+    plain = [c for c in cases if not G.takes_mfma(c)]
+    assert [c["misalign"] for c in plain] == [False, True] and all(c["store"] == G.I4 for c in plain)
+    assert G.plan(3, 3, plain[0]["Cin"], plain[0]["Cout"], plain[0]["groups"]) is not None and plain[0]["out_store"] == G.F32
+    items = [D.plain_items(c["out_store"], c["Cout"], 2 * 9 * 11, c["misalign"]) for c in plain]
+    assert items == [(4, 1584), (1, 6336)] and items[0][1] > D.BLOCK and items[0][1] % D.BLOCK
+
+
+@pytest.mark.parametrize("c", G.multitask_cases(), ids=G.case_id)
+def test_multitask_expected_values_tell_pixel_mappings_apart(c):
+    """At most half of the codes at the clip ends, no two images and no two 16-pixel groups of an image alike, and no
+    expected word equal to the pattern the GPU test lays under the output."""
+    want = G.reference(c, *G.make_inputs(c, c["seed"]))
+    assert D.degenerate(c, want) == []
+    words = want.view(np.uint32) if c["out_store"] == G.F32 else G.encode(want, c["out_store"])
+    assert not (words == FILL).any()
 
 
 # ---- the layer classes' host surface ------------------------------------------------------------------------------------------

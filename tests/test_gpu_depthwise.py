@@ -1,7 +1,8 @@
 """The depthwise convolution on the GPU (include/qnn_abi_depthwise.h, csrc/qnn_depthwise.hip) against the numpy reference
 of depthwise_cases.py, bit for bit, with the kernel name asserted: every store, channel count, window, stride, padding,
 dilation and depth multiplier of the case table with the input's spare bits set, both pointers moved off their 16-byte
-alignment, every weight kind, every epilogue, both sides of the 16-bit bound, the block-diagonal expansion through
+alignment, every weight kind, every epilogue, both sides of the 16-bit bound, both forms beyond one workgroup and the
+16-bit-lane form beyond two row blocks (D.multitask_cases()), the block-diagonal expansion through
 qnn_conv2d_forward, every refusal, the empty batch, and the layer classes."""
 import ctypes
 
@@ -106,6 +107,7 @@ def test_both_sides_of_the_16_bit_bound(c):
     x = np.where(np.random.RandomState(3).rand(*x.shape) < 0.7, -(1 << (c["x_bits"] - 1)), x)
     kernel = np.where(np.random.RandomState(4).rand(*kernel.shape) < 0.7, np.float32(-1), kernel).astype(np.float32)
     run_case(c, (x, kernel, bias, bn))
+    _beyond_two_row_blocks_and_one_workgroup(c)
 
 
 def test_constructed_overflow_takes_the_32_bit_form():
@@ -121,6 +123,47 @@ def test_aligned_and_misaligned_agree():
         a = run_case(c)
         b = run_case(dict(c, misalign=True))
         np.testing.assert_array_equal(a.view(np.uint32), b.view(np.uint32))
+    # the same on more than 256 items (the plain case of D.multitask_cases()): blockIdx.x > 0 in the item decode
+    cases = [c for c in D.multitask_cases() if not D.takes_pk16(c)]
+    assert [c["misalign"] for c in cases] == [False, True]
+    a, b = (run_multitask(c) for c in cases)
+    assert _abi.last_kernel() == "depthwise_bin"
+    np.testing.assert_array_equal(a, b)
+
+
+def run_multitask(c):
+    """run_case on a case of D.multitask_cases() with its own seed; on top of it, no word of the output is the pattern
+    laid under it (test_depthwise_cpu.py: no expected word is).  Returns the codes."""
+    try:
+        got = run_case(c, D.make_inputs(c, c["seed"]))
+        assert not (got == FILL).any(), "an output word was not written"
+    except AssertionError as e:
+        raise AssertionError("case %s: %s" % (D.case_id(c), e)) from e
+    return D.decode(got, c["out_store"], c["C"])[0]          # (pixels, words) -> (pixels, C)
+
+
+def _beyond_two_row_blocks_and_one_workgroup(host):
+    """Behind the first 16-bit-lane case of D.bound_cases() on each store, the cases of D.multitask_cases() on that store:
+    blockIdx.x > 0, three and four row blocks per image with a last block of 2, 4 and 1 rows, n > 0 behind them -- against
+    the reference and, the same 4-bit codes written to the other packed store, the plain form.  Every case runs; the
+    failures are reported together, each under its case id."""
+    store = host["store"]
+    first = next(c for c in D.bound_cases() if c["store"] == store and D.takes_pk16(c))
+    if D.case_id(host) != D.case_id(first):
+        return
+    cases = [c for c in D.multitask_cases() if c["store"] == store and D.takes_pk16(c)]
+    assert len(cases) == (4 if store == D.I4 else 3)
+    failures = []
+    for c in cases:
+        try:
+            fast = run_multitask(c)
+            assert _abi.last_kernel() == "depthwise_" + NAMES[store], D.case_id(c)
+            plain = run_multitask(dict(c, out_store=D.I8 if store == D.I4 else D.I4))
+            assert _abi.last_kernel() == "depthwise_%s_plain" % NAMES[store], D.case_id(c)
+            np.testing.assert_array_equal(fast, plain, err_msg=D.case_id(c))
+        except AssertionError as e:
+            failures.append(str(e))
+    assert not failures, "%d of %d multitask cases:\n%s" % (len(failures), len(cases), "\n".join(failures))
 
 
 @pytest.mark.parametrize("store,C,wbits,x_bits,M", [(D.I4, 9, 4, 4, 1), (D.I4, 32, 2, 4, 1), (D.I8, 5, 8, 8, 1),

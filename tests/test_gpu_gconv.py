@@ -2,8 +2,9 @@
 gconv_cases.py, bit for bit, with the kernel name asserted in every case: the plain form on every store with group edges
 inside words, every window, stride, dilation, padding, weight kind and epilogue, the input's spare bits set and pointers
 moved off their 16-byte alignment; the cross-checks against qnn_conv2d_forward (g = 1) and qnn_depthwise_forward
-(g = Cin); the matrix-pipe form against the reference and against the plain form; the route's edges; every refusal;
-capture; the layer classes; the spec op on the engines."""
+(g = Cin); the matrix-pipe form against the reference and against the plain form, on one and on several wave tasks per
+image; the plain form beyond one workgroup; the route's edges; every refusal; capture; the layer classes; the spec op on
+the engines."""
 import ctypes
 
 import numpy as np
@@ -51,8 +52,9 @@ def expected_name(c):
     return "gconv_" + NAMES[c["store"]]
 
 
-def run_case(c, inputs=None, seed=0, w=None, check_weights=True, misalign_y=False):
-    """One forward call of case `c` compared with the reference; returns the decoded output (values or codes)."""
+def run_case(c, inputs=None, seed=0, w=None, check_weights=True, misalign_y=False, guard=0):
+    """One forward call of case `c` compared with the reference; returns the decoded output (values or codes).  `guard`:
+    that many pixels' words of FILL lie behind an aligned, packed output and must still be FILL after the call."""
     x, kernel, bias, bn = inputs if inputs is not None else G.make_inputs(c, seed)
     N, H, W = c["map"]
     cout = c["Cout"]
@@ -71,13 +73,20 @@ def run_case(c, inputs=None, seed=0, w=None, check_weights=True, misalign_y=Fals
         shape, dt = (N, Ho, Wo, cout), np.float32
     else:
         shape, dt = (N * Ho * Wo, G.words(c["out_store"], cout)), np.uint32
-    out = dev(np.full(shape, FILL, np.uint32).view(dt), c["misalign"] or misalign_y)
+    if guard:
+        assert dt == np.uint32 and not (c["misalign"] or misalign_y)
+        behind = dev(np.full((shape[0] + guard, shape[1]), FILL, np.uint32))
+        out = behind[:shape[0]]
+    else:
+        out = dev(np.full(shape, FILL, np.uint32).view(dt), c["misalign"] or misalign_y)
     bnd = (dev(bn[0]), dev(bn[1])) if bn is not None else (None, None)
     y, ho, wo = _abi.gconv(w, xd, c["store"], c["x_bits"], N, H, W, bnd[0], bnd[1], c["fn"], c["act_bits"], c["out_store"],
                            out=out)
     assert _abi.last_kernel() == expected_name(dict(c, misalign=c["misalign"] or misalign_y))
     assert (ho, wo) == (Ho, Wo)
     got = host(y)
+    if guard:
+        assert (host(behind)[shape[0]:] == FILL).all(), "words behind the output were written"
     if c["out_store"] == G.F32:
         np.testing.assert_array_equal(got.view(np.uint32), want.view(np.uint32))
         return got
@@ -131,6 +140,12 @@ def test_aligned_and_misaligned_agree():
         b = run_case(dict(c, misalign=True))
         np.testing.assert_array_equal(a.view(np.uint32) if a.dtype == np.float32 else a,
                                       b.view(np.uint32) if b.dtype == np.float32 else b)
+    # the same on more than 256 items (the plain case of G.multitask_cases()): blockIdx.x > 0 in the item decode
+    cases = [c for c in G.multitask_cases() if not G.takes_mfma(c)]
+    assert [c["misalign"] for c in cases] == [False, True]
+    a, b = (run_multitask(c) for c in cases)
+    assert _abi.last_kernel() == "gconv_i4_plain"
+    np.testing.assert_array_equal(a.view(np.uint32), b.view(np.uint32))
 
 
 # ---- cross-checks against the existing entries ------------------------------------------------------------------------------
@@ -164,7 +179,8 @@ def test_groups_equal_channels_equals_depthwise_forward(store, C, M):
 @pytest.mark.parametrize("shape", G.MFMA_SHAPES, ids=lambda v: "%dx%dg%d" % v)
 @pytest.mark.parametrize("store", [G.I4, G.I8], ids=lambda v: NAMES[v])
 def test_matrix_pipe_equals_reference_and_plain_form(store, shape):
-    """One (Cg, Fg, g) on one store at its three geometries: against the reference and against the plain form."""
+    """One (Cg, Fg, g) on one store at its three geometries: against the reference and against the plain form.  The shapes of
+    G.MULTITASK_SHAPES then run their maps of several wave tasks per image."""
     cases = [c for c in G.mfma_cases() if c["store"] == store and (c["Cg"], c["Fg"], c["groups"]) == shape]
     assert len(cases) == 3
     for c in cases:
@@ -176,6 +192,39 @@ def test_matrix_pipe_equals_reference_and_plain_form(store, shape):
         off = run_case(dict(c, misalign=True), inputs, w=w, check_weights=False)
         assert _abi.last_kernel() == "gconv_%s_plain" % NAMES[store], G.case_id(c)
         np.testing.assert_array_equal(fast, off, err_msg=G.case_id(c))
+    _several_wave_tasks_per_image(store, shape)
+
+
+def run_multitask(c, **kw):
+    """run_case on a case of G.multitask_cases() with its own seed; on top of it, no word of the output is the pattern
+    laid under it (test_gconv_cpu.py: no expected word is)."""
+    try:
+        got = run_case(c, G.make_inputs(c, c["seed"]), **kw)
+        words = got.view(np.uint32) if c["out_store"] == G.F32 else G.encode(got, c["out_store"])
+        assert not (words == FILL).any(), "an output word was not written"
+    except AssertionError as e:
+        raise AssertionError("case %s: %s" % (G.case_id(c), e)) from e
+    return got
+
+
+def _several_wave_tasks_per_image(store, shape):
+    """The cases of G.multitask_cases() on one (store, shape): g0 > 0 with n > 0, ragged and empty groups in a later task,
+    the int4 exchange with one valid member, a partly filled last workgroup -- against the reference and against the plain
+    form.  Every case runs; the failures are reported together, each under its case id."""
+    cases = [c for c in G.multitask_cases() if G.takes_mfma(c) and (c["store"], c["Cg"], c["Fg"], c["groups"]) == (store,) + shape]
+    assert len(cases) == (0 if shape not in G.MULTITASK_SHAPES else 5 if (store, shape) == (G.I4, (4, 4, 4)) else 4)
+    failures = []
+    for c in cases:
+        try:
+            w = handle(c, *G.make_inputs(c, c["seed"])[1:3])
+            fast = run_multitask(c, w=w, guard=16 * G.K_PG)      # a task's pixels beyond the last image would land there
+            assert _abi.last_kernel() == "gconv_%s_mfma" % NAMES[store], G.case_id(c)
+            off = run_multitask(dict(c, misalign=True), w=w, check_weights=False)
+            assert _abi.last_kernel() == "gconv_%s_plain" % NAMES[store], G.case_id(c)
+            np.testing.assert_array_equal(fast, off, err_msg=G.case_id(c))
+        except AssertionError as e:
+            failures.append(str(e))
+    assert not failures, "%d of %d multitask cases:\n%s" % (len(failures), len(cases), "\n".join(failures))
 
 
 @pytest.mark.parametrize("store", [G.I4, G.I8])

@@ -2,7 +2,8 @@
 tconv_cases.py, bit for bit, with the kernel name asserted wherever a route is claimed: the plain form on every store,
 window, stride, padding, map and channel count of the case table with the input's spare bits set, pointers moved off
 their 16-byte alignment, every weight kind and epilogue; the matrix-pipe form against the reference and against the plain
-form; the route's edges; every refusal; capture into a hipGraph; the layer classes; the spec op on the engines."""
+form, on one and on several wave tasks per phase; the plain form beyond one workgroup; the route's edges;
+every refusal; capture into a hipGraph; the layer classes; the spec op on the engines."""
 import ctypes
 
 import numpy as np
@@ -115,6 +116,12 @@ def test_aligned_and_misaligned_agree():
         b = run_case(dict(c, misalign=True))
         np.testing.assert_array_equal(a.view(np.uint32) if a.dtype == np.float32 else a,
                                       b.view(np.uint32) if b.dtype == np.float32 else b)
+    # the same on more than 256 items (the plain case of T.multitask_cases()): blockIdx.x > 0 in the item decode
+    cases = [c for c in T.multitask_cases() if not T.takes_mfma(c)]
+    assert [c["misalign"] for c in cases] == [False, True]
+    a, b = (run_multitask(c) for c in cases)
+    assert _abi.last_kernel() == "tconv_i8_plain"
+    np.testing.assert_array_equal(a, b)
 
 
 # ---- the matrix-pipe form ----------------------------------------------------------------------------------------------------
@@ -139,6 +146,57 @@ def test_matrix_pipe_equals_reference_and_plain_form(c):
     off = run_case(dict(c, misalign=True), inputs, w=w, check_weights=False)
     assert _abi.last_kernel() == "tconv_%s_plain" % NAMES[c["store"]]
     np.testing.assert_array_equal(fast, off)
+    _several_wave_tasks_per_phase(c)
+
+
+def run_multitask(c, **kw):
+    """run_case on a case of T.multitask_cases() with its own seed; on top of it, no word of the output is the pattern
+    laid under it (test_tconv_cpu.py: no expected word is)."""
+    try:
+        codes = run_case(c, T.make_inputs(c, c["seed"]), **kw)
+        assert not (T.encode(codes, c["out_store"]) == FILL).any(), "an output word was not written"
+    except AssertionError as e:
+        raise AssertionError("case %s: %s" % (T.case_id(c), e)) from e
+    return codes
+
+
+def _shape_key(c):
+    return c["store"], c["window"], c["same"], c["Cin"], c["Cout"]
+
+
+def _multitask_hosts():
+    """(shape, map) of the first case of T.mfma_cases() on a (store, window, padding, Cin, Cout) -> the matrix-pipe cases of
+    T.multitask_cases() on the same: every one of them runs behind exactly one test id of the matrix-pipe form."""
+    first, hosts = {}, {}
+    for c in T.mfma_cases():
+        first.setdefault(_shape_key(c), (_shape_key(c), c["map"]))
+    for m in T.multitask_cases():
+        if T.takes_mfma(m):
+            hosts.setdefault(first[_shape_key(m)], []).append(m)
+    assert sum(len(v) for v in hosts.values()) == 17
+    return hosts
+
+
+MULTITASK_HOSTS = _multitask_hosts()
+
+
+def _several_wave_tasks_per_phase(host):
+    """The cases of T.multitask_cases() on the host's (store, window, padding, Cin, Cout): GT = 2 and 3 with n > 0, phases
+    that end before a later task's first group next to a phase that does not -- against the reference and against the plain
+    form.  Every case runs; the failures are reported together, each under its case id."""
+    cases = MULTITASK_HOSTS.get((_shape_key(host), host["map"]), [])
+    failures = []
+    for c in cases:
+        try:
+            w = handle(c, *T.make_inputs(c, c["seed"])[1:3])
+            fast = run_multitask(c, w=w)
+            assert _abi.last_kernel() == "tconv_%s_mfma" % NAMES[c["store"]], T.case_id(c)
+            off = run_multitask(dict(c, misalign=True), w=w, check_weights=False)
+            assert _abi.last_kernel() == "tconv_%s_plain" % NAMES[c["store"]], T.case_id(c)
+            np.testing.assert_array_equal(fast, off, err_msg=T.case_id(c))
+        except AssertionError as e:
+            failures.append(str(e))
+    assert not failures, "%d of %d multitask cases:\n%s" % (len(failures), len(cases), "\n".join(failures))
 
 
 @pytest.mark.parametrize("store,fn,act_bits,x_bits,wkind,wbits", [

@@ -15,6 +15,7 @@ import torch
 import qnn_amd                                   # noqa: F401  (the package alias of conftest.py)
 from qnn_amd import _abi, engine, nets
 
+import depthwise_cases as D
 import tconv_cases as T
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -83,7 +84,7 @@ def test_header_and_reference_agree_on_the_grid(rule):
             assert out >= (n - 1) * s + k                                  # the whole scatter is kept
 
 
-ALL_CASES = T.geometry_cases() + T.channel_cases() + T.mfma_cases() + T.boundary_cases()
+ALL_CASES = T.geometry_cases() + T.channel_cases() + T.mfma_cases() + T.boundary_cases() + T.multitask_cases()
 GEOMETRIES = sorted({(c["window"], c["stride"], c["same"], c["map"]) for c in ALL_CASES})
 
 
@@ -127,6 +128,53 @@ def test_the_case_tables_cover_what_they_claim():
         mine = [c for c in m if (c["store"], c["window"], c["same"]) == (store, (k, k), same)]
         assert {c["map"] for c in mine} == set(T.MFMA_MAPS)
         assert {(c["Cin"], c["Cout"]) for c in mine} == {(64, 16), (128, 48)}
+
+
+# ---- the multitask table: what it reaches, and that its expected values can tell pixel mappings apart ------------------------
+FILL = 0x5A5A5A5A                                # what test_gpu_tconv.py lays under every output
+
+
+def test_multitask_table_reaches_the_decodes_it_names():
+    cases = T.multitask_cases()
+    assert len({T.case_id(c) for c in cases}) == len(cases) == 19 and all(c["map"][0] >= 2 for c in cases)
+    fast = [c for c in cases if T.takes_mfma(c)]
+    assert len(fast) == 17
+    for store in (T.I4, T.I8):
+        for k, same, m in T.MULTITASK_MAPS:
+            mine = [c for c in fast if (c["store"], c["window"], c["same"], c["map"]) == (store, (k, k), same, m)]
+            assert {(c["Cin"], c["Cout"]) for c in mine} == {(64, 16), (128, 48)}          # FB = 1 half filled, FB = 2
+    # the phases and the task count, restated from the map alone
+    by_geom = {(3, False, (2, 2, 21)): ([66, 63, 44, 42], 2), (3, True, (2, 4, 40)): ([160] * 4, 3),
+               (2, False, (2, 2, 21)): ([42] * 4, 1), (4, False, (2, 2, 21)): ([66] * 4, 2), (3, True, (70, 1, 1)): ([1] * 4, 1)}
+    for c in fast:
+        N, H, W = c["map"]
+        k = c["window"][0]
+        Ho, Wo = (v * 2 + (0 if c["same"] else max(k - 2, 0)) for v in (H, W))
+        phases = [(Ho + 1) // 2 * ((Wo + 1) // 2), (Ho + 1) // 2 * (Wo // 2), Ho // 2 * ((Wo + 1) // 2), Ho // 2 * (Wo // 2)]
+        GT, waves = T.wave_tasks(c)
+        assert (T.phase_pixels(c), GT) == (phases, -(-(-(-phases[0] // 16)) // 4)) == by_geom[(k, c["same"], c["map"])]
+        assert sum(phases) == Ho * Wo and waves == N * 4 * GT * -(-c["Cout"] // 32)
+    # a phase that ends at or before the first group of a later task, so that task returns early with g0 > 0
+    assert any(T.wave_tasks(c)[0] >= 2 and min(T.phase_pixels(c)) <= 16 * T.K_PG for c in fast)
+    assert max(T.wave_tasks(c)[0] for c in fast) >= 3
+    assert any(c["map"] == D.TINY_MAP and T.wave_tasks(c)[1] == 280 for c in fast)
+    # the plain form past one workgroup at V = 4, and the same case at V = 1
+    plain = [c for c in cases if not T.takes_mfma(c)]
+    assert [c["misalign"] for c in plain] == [False, True] and all((c["store"], c["stride"]) == (T.I8, 2) for c in plain)
+    items = [D.plain_items(c["out_store"], c["Cout"], 2 * 10 * 18, c["misalign"]) for c in plain]
+    assert items == [(4, 360), (1, 1440)] and items[0][1] > D.BLOCK and items[0][1] % D.BLOCK
+
+
+@pytest.mark.parametrize("c", T.multitask_cases(), ids=T.case_id)
+def test_multitask_expected_values_tell_pixel_mappings_apart(c):
+    """At most half of the codes at the clip ends, no two images and no two 16-pixel groups of an image alike -- the groups
+    of the matrix-pipe form run over one phase --, and no expected word equal to the pattern the GPU test lays under the
+    output."""
+    want = T.reference(c, *T.make_inputs(c, c["seed"]))
+    assert D.degenerate(c, want) == []
+    if T.takes_mfma(c):
+        assert D.degenerate(c, want, T.phase_groups(c, want)) == []
+    assert not (T.encode(want, c["out_store"]) == FILL).any()
 
 
 def test_route_rule_restated():
