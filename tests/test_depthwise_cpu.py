@@ -284,3 +284,13 @@ def test_fused_engines_decline_and_epilogue_cases_hold_ties_and_clips():
         assert (t > m - 1).any() or (t < lo).any(), D.case_id(c)      # a value beyond the grid: it is clipped
         seen += 1
     assert seen > 100
+    # one tie and one clipped value are a low bar for random inputs.  The counted points -- at least 32 ties strictly inside
+    # the clip range and 8 points on each clip edge, per kernel form, activation, width and BN sign -- are conditions of the
+    # cases of sideconv_grid_cases.py; test_sideconv_grid_cpu.py asserts them on every case and says what is exempt.  Here
+    # only that those cases exist for every depthwise form, and the counts on the one this test used to speak of
+    import sideconv_grid_cases as S
+    grid = [c for c in S.cases() if c["op"] == "dw" and c["fn"] in D.QACTS and S.claims(c, c["act_bits"])]
+    assert len(grid) > 300 and {c["form"] for c in grid} == {"depthwise_" + s for s in ("i4", "i8", "i4_plain", "i8_plain", "bin", "t2", "f32")}
+    for c in (k for k in grid if k["form"] == "depthwise_i4" and k["act_bits"] == 4):
+        n = S.counts(c, S.preactivation(c))
+        assert n["ties"] >= S.MIN_TIES and n["hi"] >= S.MIN_EDGE and n["beyond"] >= S.MIN_EDGE, (c["id"], n)

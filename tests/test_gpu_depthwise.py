@@ -95,9 +95,18 @@ def test_weight_kinds(c):
     run_case(c)
 
 
+EPILOGUE_IDS = [D.case_id(c) for c in D.epilogue_cases()]
+EPILOGUE_STORES = [c["store"] for c in D.epilogue_cases()]
+
+
 @pytest.mark.parametrize("c", D.epilogue_cases(), ids=D.case_id)
 def test_epilogues(c):
-    run_case(c)
+    import test_gpu_sideconv_grid as grid
+    try:
+        run_case(c)
+    finally:
+        # on exact ties, zeros and clip edges: the groups of sideconv_grid_cases.py that this id carries (its own input store)
+        grid.run_hosted("dw", EPILOGUE_STORES, EPILOGUE_IDS.index(D.case_id(c)))
 
 
 @pytest.mark.parametrize("c", D.bound_cases(), ids=D.case_id)

@@ -123,13 +123,21 @@ def test_weight_kinds(store):
     run_all([c for c in G.weight_cases() if c["store"] == store])
 
 
+EPILOGUE_HOST_STORES = [s_ for s_ in G.STORES for _ in range(2)]          # test_epilogues: store x (bias, bn)
+
+
 @pytest.mark.parametrize("bias,bn", [(True, True), (False, False)])
 @pytest.mark.parametrize("store", G.STORES, ids=lambda v: NAMES[v])
 def test_epilogues(store, bias, bn):
     """Every fn to every legal out_store on one input store."""
     cases = [c for c in G.epilogue_cases() if c["store"] == store and (c["bias"], c["bn"]) == (bias, bn)]
     assert len(cases) == len(G._fn_pairs())
-    run_all(cases)
+    import test_gpu_sideconv_grid as grid
+    try:
+        run_all(cases)
+    finally:
+        # on exact ties, zeros and clip edges: the groups of sideconv_grid_cases.py that this id carries (its own input store)
+        grid.run_hosted("gc", EPILOGUE_HOST_STORES, 2 * G.STORES.index(store) + (0 if bias else 1))
 
 
 def test_aligned_and_misaligned_agree():

@@ -103,9 +103,18 @@ def test_weight_kinds(c):
     run_case(c)
 
 
+EPILOGUE_IDS = [T.case_id(c) for c in T.epilogue_cases()]
+EPILOGUE_STORES = [c["store"] for c in T.epilogue_cases()]
+
+
 @pytest.mark.parametrize("c", T.epilogue_cases(), ids=T.case_id)
 def test_epilogues(c):
-    run_case(c)
+    import test_gpu_sideconv_grid as grid
+    try:
+        run_case(c)
+    finally:
+        # on exact ties, zeros and clip edges: the groups of sideconv_grid_cases.py that this id carries (its own input store)
+        grid.run_hosted("tc", EPILOGUE_STORES, EPILOGUE_IDS.index(T.case_id(c)))
 
 
 def test_aligned_and_misaligned_agree():
