@@ -172,6 +172,8 @@ struct ConvCall {
 int qnn_route_first_f32(const ConvCall& c, char* name, size_t name_len);
 int qnn_route_strip(const ConvCall& c, char* name, size_t name_len);
 int qnn_route_gemm(const ConvCall& c, char* name, size_t name_len);
+// hidden dense layers that route_dense declines: the register-fed GEMM of qnn_dense_mfma.hip
+int qnn_route_dense_mfma(const ConvCall& c, char* name, size_t name_len);
 // the one route for dilated calls besides k_conv_generic (qnn_mfma_strip_dil.hip)
 int qnn_route_strip_dil(const ConvCall& c, char* name, size_t name_len);
 

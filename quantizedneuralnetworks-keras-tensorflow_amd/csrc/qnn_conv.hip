@@ -1406,6 +1406,7 @@ struct Route {
 // in order of preference; k_conv_generic last takes every call without a projection
 const Route kRoutes[] = {
     {route_dense, CAP_DENSE | CAP_QACT | CAP_XSCALE, false},
+    {qnn_route_dense_mfma, CAP_DENSE | CAP_QACT, true},                     // what route_dense declines: packed outputs, > 256 units
     {route_pw, CAP_CONV, false},
     {route_first_u8, CAP_CONV, true},
     {route_stem, CAP_CONV, true},

@@ -69,6 +69,8 @@ TAG_PATTERNS = [
     (r"^mfma_i(\d)_(\d+)x(\d+)$", None),          # tile sizes -> waves, handled below
     (r"^dense_i(\d)$", r"^k_dense_packed(_split)?<\1,"),
     (r"^dense_bin$", r"^k_dense_packed(_split)?<1,"),
+    (r"^dense_mfma_i(\d)$", r"^k_dense_mfma<\1,"),
+    (r"^dense_mfma_bin$", r"^k_dense_mfma<1,"),
     (r"^dense_f32$", r"^k_dense_f32in"),
     (r"^xnor_f32_cw(\d+)$", r"^k_conv_xnor_f32<\1>"),
     (r"^xnor_pk_cw(\d+)", r"^k_conv_xnor_pk<\1,"),
